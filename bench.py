@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — training-step throughput of the Apertis hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1.5b-moe] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1.5b-moe] [--batch B] [--dump-outputs DIR]
 
 A "step" is one data-parallel training step (bf16-autocast forward + loss + backward +
 gradient all-reduce + clip + AdamW) of the BASELINE.json model on synthetic random tokens,
@@ -192,6 +192,49 @@ def decode_bench(args, model, dev, seq, log):
     return 0
 
 
+DUMP_SAMPLES = 1 << 21     # sampled elements per state array (x 3 arrays x 4 bytes: 24 MB, under the 64 MB cap)
+DUMP_MIN_PER_TENSOR = 256  # every parameter tensor is represented, however small
+
+
+def dump_outputs(out_dir, loss, model, optimizer):
+    """What the caller of the timed step holds after its last call, as float32 / float64 .npy files in out_dir:
+      loss.npy             [1] float64  the loss the last timed step returned
+      grad_norm.npy        [1] float64  its global gradient norm before clipping (ApertisAdamW.last_grad_norm)
+      params.npy           [S] float32  a fixed sample of the updated parameters
+      exp_avg.npy          [S] float32  AdamW's first moment at the same elements
+      exp_avg_sq.npy       [S] float32  AdamW's second moment at the same elements
+    The sample is drawn from a CPU generator with a fixed seed, per parameter in named_parameters() order (each tensor
+    contributes max(256, its share of 2^21) elements, sorted, with replacement), so it depends only on the model's shapes."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    total = sum(p.numel() for _, p in named)
+    gen = torch.Generator().manual_seed(0)
+    parts = {"params": [], "exp_avg": [], "exp_avg_sq": []}
+    for _, p in named:
+        n = p.numel()
+        k = min(n, max(DUMP_MIN_PER_TENSOR, DUMP_SAMPLES * n // total))
+        idx = torch.arange(n) if k == n else torch.randint(0, n, (k,), generator=gen).sort().values
+        idx = idx.to(p.device)
+        st = optimizer.state.get(p, {})
+        for key, t in (("params", p), ("exp_avg", st.get("exp_avg")), ("exp_avg_sq", st.get("exp_avg_sq"))):
+            if t is None:          # (a parameter that never received a gradient has no moments yet)
+                t = torch.full_like(p, float("nan"))
+            parts[key].append(t.detach().reshape(-1)[idx].float().cpu())
+    arrays = {"loss": np.array([float(loss)], dtype=np.float64)}
+    gn = getattr(optimizer, "last_grad_norm", None)
+    if gn is not None:
+        arrays["grad_norm"] = np.array([float(gn)], dtype=np.float64)
+    for key, ts in parts.items():
+        arrays[key] = torch.cat(ts).numpy().astype(np.float32)
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= 64 << 20, nbytes
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays), nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -211,12 +254,22 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU/gloo self-test of the rank launcher and the timing protocol (tests/): no GPU work, "
                          "the line says so and is not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step computed to DIR/<name>.npy (see "
+                         "dump_outputs()), so that two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.decode or args.launcher_selftest):
+        raise SystemExit("bench.py: --dump-outputs covers the training step only (not --decode or --launcher-selftest)")
     if args.gpus > 1 and "RANK" not in os.environ:
         # not under a launcher: be the launcher.  Nothing above this line imports torch or touches HIP.
-        raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
+        argv = sys.argv[1:]
+        if args.dump_outputs:      # the ranks run from ROOT: a relative DIR is the caller's (argparse keeps the last value)
+            argv = argv + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        raise SystemExit(launch_ranks(args.gpus, argv))
 
     import torch
     import torch.distributed as dist
@@ -323,6 +376,9 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:     # after the timed region: the replicas hold the same parameters
+        names, nbytes = dump_outputs(args.dump_outputs, loss, model, step.optimizer)
+        log(f"outputs of the last timed step: {', '.join(names)} ({nbytes / 2**20:.1f} MB) in {args.dump_outputs}")
 
     tokens = B * seq * world * args.steps
     result = {
