@@ -393,6 +393,193 @@ dwconv_silu_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict
   }
 }
 
+// ---- widths 5..16 (an ssm_conv_kernel other than 2..4; off the model's default path): the run-per-thread forms above with the
+// tap count k a runtime value.  Window, dpre history and taps are CONV_KMAX-long register arrays, right-aligned - tap q sits in
+// slot off + q, off = CONV_KMAX - k - so every index is a constant once the loops unroll, and the wave-uniform tests `m >= off`
+// skip the unused slots (no 0 * x terms: a non-finite value outside the window stays outside).  The backward emits dx
+// CONV_KMAX - 1 tokens behind the walk instead of k - 1: dx[t - (KMAX-1)] = sum_q w[q] * dp[k-1-q] and w[q] = wv[KMAX-k+q],
+// i.e. slot KMAX-1-m of the taps meets slot m of the history.  Same geometry, grid and partial layout as the templated kernels;
+// the sums run in the same order.
+constexpr int CONV_KMAX = 16;
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+dwconv_silu_fwd_kn(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
+                   T *__restrict__ out, int64_t out_rs, int64_t B, int64_t L, int Dn, int k) {
+  constexpr int KM = CONV_KMAX;
+  const int off = KM - k;
+  const Geo g = make_geo(Dn);
+  const int rr = threadIdx.x / g.CPR;
+  if (rr >= g.RP) return;
+  const int64_t runs_per_seq = ceil_div64(L, CONV_TT);
+  for (int c = threadIdx.x - rr * g.CPR; c < g.CPR; c += 256) {
+    float wv[4][KM], bv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      bv[j] = bias[c * 4 + j];
+#pragma unroll
+      for (int m = 0; m < KM; ++m) wv[j][m] = m >= off ? w[(c * 4 + j) * k + (m - off)] : 0.f;
+    }
+    for (int64_t run = (int64_t)blockIdx.x * g.RP + rr; run < B * runs_per_seq; run += (int64_t)gridDim.x * g.RP) {
+      const int64_t b = run / runs_per_seq, t0 = (run - b * runs_per_seq) * CONV_TT;
+      const T *xb = x + b * L * x_rs + c * 4;
+      T *ob = out + b * L * out_rs + c * 4;
+      float win[KM][4];  // win[m] = x[t-(KM-1)+m]
+#pragma unroll
+      for (int m = 0; m < KM - 1; ++m) {
+        const int64_t tt = t0 - (KM - 1) + m;
+        float4 v = (m >= off && tt >= 0) ? ld4<T>(xb + tt * x_rs) : make_float4(0, 0, 0, 0);
+        win[m + 1][0] = v.x; win[m + 1][1] = v.y; win[m + 1][2] = v.z; win[m + 1][3] = v.w;
+      }
+      const int64_t t1 = min(t0 + CONV_TT, L);
+      for (int64_t t = t0; t < t1; ++t) {
+#pragma unroll
+        for (int m = 0; m < KM - 1; ++m)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) win[m][j] = win[m + 1][j];
+        float4 v = ld4<T>(xb + t * x_rs);
+        win[KM - 1][0] = v.x; win[KM - 1][1] = v.y; win[KM - 1][2] = v.z; win[KM - 1][3] = v.w;
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float s = bv[j];
+#pragma unroll
+          for (int m = 0; m < KM; ++m)
+            if (m >= off) s += wv[j][m] * win[m][j];
+          s = to_f32(from_f32<T>(s));  // conv output is stored in the activation dtype before SiLU
+          o[j] = siluf_(s);
+        }
+        st4<T>(ob + t * out_rs, make_float4(o[0], o[1], o[2], o[3]));
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+dwconv_silu_bwd_kn(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
+                   const T *__restrict__ dout, int64_t dout_rs, const T *__restrict__ dout2, int64_t dout2_rs,
+                   T *__restrict__ dx, int64_t dx_rs,
+                   float *__restrict__ dw_part, float *__restrict__ db_part, int64_t B, int64_t L, int Dn, int k) {
+  constexpr int KM = CONV_KMAX;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float *red = reinterpret_cast<float *>(smem);  // [RP][CPR][4*(k+1)]
+  const int off = KM - k, NA = 4 * (k + 1);
+  const Geo g = make_geo(Dn);
+  const int rr = threadIdx.x / g.CPR;
+  const bool on = rr < g.RP;
+  const int64_t runs_per_seq = ceil_div64(L, CONV_TT);
+  for (int c0 = 0; c0 < g.CPR; c0 += 256) {
+    const int c = c0 + (on ? threadIdx.x - rr * g.CPR : 0);
+    float accw[4][KM], accb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { accb[j] = 0.f;
+#pragma unroll
+      for (int m = 0; m < KM; ++m) accw[j][m] = 0.f; }
+    if (on && c < g.CPR) {
+      float wv[4][KM], bv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        bv[j] = bias[c * 4 + j];
+#pragma unroll
+        for (int m = 0; m < KM; ++m) wv[j][m] = m >= off ? w[(c * 4 + j) * k + (m - off)] : 0.f;
+      }
+      for (int64_t run = (int64_t)blockIdx.x * g.RP + rr; run < B * runs_per_seq; run += (int64_t)gridDim.x * g.RP) {
+        const int64_t b = run / runs_per_seq, t0 = (run - b * runs_per_seq) * CONV_TT;
+        const T *xb = x + b * L * x_rs + c * 4;
+        const T *gb = dout + b * L * dout_rs + c * 4;
+        const T *gb2 = dout2 ? dout2 + b * L * dout2_rs + c * 4 : nullptr;
+        T *dxb = dx + b * L * dx_rs + c * 4;
+        const int64_t t1 = min(t0 + CONV_TT, L), te = min(t1 + (k - 1), L);
+        // win[m] = x[t-(KM-1)+m], dp[m] = dpre[t-(KM-1)+m]; dpre is formed on [t0, te) - the next run's first k-1 tokens feed
+        // our dx - and taken as zero outside it
+        float win[KM][4], dp[KM][4];
+#pragma unroll
+        for (int m = 0; m < KM; ++m)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { win[m][j] = 0.f; dp[m][j] = 0.f; }
+#pragma unroll
+        for (int m = 0; m < KM - 1; ++m) {
+          const int64_t tt = t0 - (KM - 1) + m;
+          if (m >= off && tt >= 0) { float4 v = ld4<T>(xb + tt * x_rs); win[m + 1][0] = v.x; win[m + 1][1] = v.y; win[m + 1][2] = v.z; win[m + 1][3] = v.w; }
+        }
+        for (int64_t t = t0; t < t1 + (KM - 1); ++t) {
+#pragma unroll
+          for (int m = 0; m < KM - 1; ++m)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { win[m][j] = win[m + 1][j]; dp[m][j] = dp[m + 1][j]; }
+          if (t < te) {
+            float4 v = ld4<T>(xb + t * x_rs), gv = ld4<T>(gb + t * dout_rs);
+            if (gb2) {
+              const float4 g2 = ld4<T>(gb2 + t * dout2_rs);
+              gv = make_float4(to_f32(from_f32<T>(gv.x + g2.x)), to_f32(from_f32<T>(gv.y + g2.y)), to_f32(from_f32<T>(gv.z + g2.z)),
+                               to_f32(from_f32<T>(gv.w + g2.w)));
+            }
+            win[KM - 1][0] = v.x; win[KM - 1][1] = v.y; win[KM - 1][2] = v.z; win[KM - 1][3] = v.w;
+            const float g_[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              float s = bv[j];
+#pragma unroll
+              for (int m = 0; m < KM; ++m)
+                if (m >= off) s += wv[j][m] * win[m][j];
+              s = to_f32(from_f32<T>(s));
+              float d = g_[j] * silu_grad(s);
+              dp[KM - 1][j] = d;
+              if (t < t1) {  // own tokens only: parameter gradients are not double counted
+                accb[j] += d;
+#pragma unroll
+                for (int m = 0; m < KM; ++m)
+                  if (m >= off) accw[j][m] += d * win[m][j];
+              }
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { win[KM - 1][j] = 0.f; dp[KM - 1][j] = 0.f; }
+          }
+          const int64_t tp = t - (KM - 1);
+          if (tp >= t0) {  // (tp < t1 by the loop bound)
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              float s = 0.f;
+#pragma unroll
+              for (int m = KM - 1; m >= 0; --m)  // q = k-1-m ascending, as in the templated kernel
+                if (m < k) s += wv[j][KM - 1 - m] * dp[m][j];
+              o[j] = s;
+            }
+            st4<T>(dxb + tp * dx_rs, make_float4(o[0], o[1], o[2], o[3]));
+          }
+        }
+      }
+    }
+    const int cw = min(g.CPR, 256);
+    __syncthreads();
+    if (on && c < g.CPR) {
+      float *r = red + ((int64_t)rr * cw + (c - c0)) * NA;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        r[j * (k + 1) + k] = accb[j];
+#pragma unroll
+        for (int m = 0; m < KM; ++m)
+          if (m >= off) r[j * (k + 1) + (m - off)] = accw[j][m];
+      }
+    }
+    __syncthreads();
+    if (on && rr == 0 && c < g.CPR) {
+      for (int j = 0; j < 4; ++j) {
+        for (int q = 0; q <= k; ++q) {
+          float s = 0.f;
+          for (int r = 0; r < g.RP; ++r) s += red[((int64_t)r * cw + (c - c0)) * NA + j * (k + 1) + q];
+          if (q < k) dw_part[((int64_t)blockIdx.x * Dn + c * 4 + j) * k + q] = s;
+          else db_part[(int64_t)blockIdx.x * Dn + c * 4 + j] = s;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // out[c] = sum_r in[r][c], fixed order (16 row groups, four independent loads in flight)
 __global__ void __launch_bounds__(1024)
 colsum_rows_k(const float *__restrict__ in, float *__restrict__ out, int64_t rows, int64_t cols) {
@@ -582,10 +769,16 @@ int conv_blocks(int64_t B, int64_t L, int64_t Dn) {
   int64_t runs = B * ceil_div64(L, CONV_TT);
   return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div64(runs, g.RP), 4096));
 }
+// the tile form's LDS: TT + k - 1 rows of PCS = Dn / EPC 16-byte pieces; one work-group may hold at most the CU's 160 KiB
+constexpr int64_t CONV_TILE_LDS_MAX = 160 * 1024;
+int64_t conv_tile_lds(int64_t Dn, int64_t k, int dtype_io) {
+  return (CONV_TILE_T + k - 1) * (Dn / (dtype_io == APERTIS_BF16 ? 8 : 4)) * 16;
+}
 bool conv_tile_ok(int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io, std::initializer_list<const void *> ptrs,
                   std::initializer_list<int64_t> strides) {
   const int64_t es = dtype_io == APERTIS_BF16 ? 2 : 4, epc = 16 / es;
   if (Dn % epc != 0 || Dn / epc > 256 || B * ceil_div64(L, CONV_TILE_T) >= 0x7fffffffLL || k < 2 || k > 4) return false;
+  if (conv_tile_lds(Dn, k, dtype_io) > CONV_TILE_LDS_MAX) return false;
   for (const void *q : ptrs) if (((uintptr_t)q) % 16) return false;
   for (int64_t r : strides) if ((r * es) % 16) return false;
   return true;
@@ -649,6 +842,13 @@ extern "C" int apertis_ssm_gate_bwd(const void *dout, int64_t dout_rs, const voi
     else return APERTIS_ERR_ARG;                                                                \
   } while (0)
 
+#define CONV_TYPES(dt_, ...)                                                                    \
+  do {                                                                                          \
+    if ((dt_) == APERTIS_F32) { typedef float T; __VA_ARGS__; }                                 \
+    else if ((dt_) == APERTIS_BF16) { typedef bf16_t T; __VA_ARGS__; }                          \
+    else return APERTIS_ERR_ARG;                                                                \
+  } while (0)
+
 extern "C" int apertis_dwconv_silu_fwd(const void *x, int64_t x_rs, const float *w, const float *bias, void *out,
                                        int64_t out_rs, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
                                        void *stream) {
@@ -656,16 +856,26 @@ extern "C" int apertis_dwconv_silu_fwd(const void *x, int64_t x_rs, const float 
   if (!rows_ok(Dn) || (x_rs | out_rs) % 4) return APERTIS_ERR_UNSUPPORTED;
   if (B == 0 || L == 0) return APERTIS_OK;
   hipStream_t st = (hipStream_t)stream;
-  // tile form when every row is whole 16-byte pieces at 16-byte-aligned addresses (the model's shapes), else run per thread
+  // tile form when every row is whole 16-byte pieces at 16-byte-aligned addresses (the model's shapes) and the tile fits the
+  // LDS, else run per thread (widths 5..16: the runtime-width kernel)
   if (conv_tile_ok(B, L, Dn, k, dtype_io, {x, out}, {x_rs, out_rs})) {
     const int64_t epc = dtype_io == APERTIS_BF16 ? 8 : 4;
     const int PCS = (int)(Dn / epc), RG = 256 / PCS, nchunks = (int)ceil_div64(L, CONV_TILE_T);
-    const size_t lds = (size_t)(CONV_TILE_T + k - 1) * PCS * 16;
-    CONV_DISPATCH(k, dtype_io, hipLaunchKernelGGL((dwconv_silu_fwd_tile_k<T, KW>), dim3((unsigned)(B * nchunks)), dim3(256), lds, st,
-                                                  (const T *)x, x_rs, w, bias, (T *)out, out_rs, L, PCS, RG, nchunks));
+    const size_t lds = (size_t)conv_tile_lds(Dn, k, dtype_io);
+    CONV_DISPATCH(k, dtype_io, {
+      auto kf = dwconv_silu_fwd_tile_k<T, KW>;
+      if (lds > 48 * 1024) hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kf, dim3((unsigned)(B * nchunks)), dim3(256), lds, st, (const T *)x, x_rs, w, bias, (T *)out, out_rs, L,
+                         PCS, RG, nchunks);
+    });
     return apertis_check_launch();
   }
   dim3 grid(conv_blocks(B, L, Dn)), block(256);
+  if (k > 4 && k <= CONV_KMAX) {
+    CONV_TYPES(dtype_io, hipLaunchKernelGGL(dwconv_silu_fwd_kn<T>, grid, block, 0, st, (const T *)x, x_rs, w, bias, (T *)out,
+                                            out_rs, B, L, (int)Dn, (int)k));
+    return apertis_check_launch();
+  }
   CONV_DISPATCH(k, dtype_io, hipLaunchKernelGGL((dwconv_silu_fwd_k<T, KW>), grid, block, 0, st, (const T *)x, x_rs, w, bias,
                                                 (T *)out, out_rs, B, L, (int)Dn));
   return apertis_check_launch();
@@ -677,16 +887,25 @@ extern "C" int apertis_dwconv_silu_bwd2(const void *x, int64_t x_rs, const float
                                         int64_t k, int dtype_io, void *stream) {
   if (!x || !w || !bias || !dout || !dx || !dw_part || !db_part || !dw || !db || B < 0 || L < 0) return APERTIS_ERR_ARG;
   if (!dout2) dout2_rs = 0;
-  if (!rows_ok(Dn) || (x_rs | dout_rs | dout2_rs | dx_rs) % 4 || k < 2 || k > 4) return APERTIS_ERR_UNSUPPORTED;
+  if (!rows_ok(Dn) || (x_rs | dout_rs | dout2_rs | dx_rs) % 4 || k < 2 || k > CONV_KMAX) return APERTIS_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int nblk = conv_blocks(B, L, Dn);
   {
     Geo g = make_geo(Dn);
     size_t lds = (size_t)g.RP * std::min(g.CPR, 256) * 4 * (k + 1) * sizeof(float);
     dim3 grid(nblk), block(256);
-    CONV_DISPATCH(k, dtype_io, hipLaunchKernelGGL((dwconv_silu_bwd_k<T, KW>), grid, block, lds, st, (const T *)x, x_rs, w,
-                                                  bias, (const T *)dout, dout_rs, (const T *)dout2, dout2_rs, (T *)dx, dx_rs,
-                                                  dw_part, db_part, B, L, (int)Dn));
+    if (k > 4) {  // (up to 68 KiB at k = 16)
+      CONV_TYPES(dtype_io, {
+        auto kf = dwconv_silu_bwd_kn<T>;
+        if (lds > 48 * 1024) hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kf, grid, block, lds, st, (const T *)x, x_rs, w, bias, (const T *)dout, dout_rs, (const T *)dout2,
+                           dout2_rs, (T *)dx, dx_rs, dw_part, db_part, B, L, (int)Dn, (int)k);
+      });
+    } else {
+      CONV_DISPATCH(k, dtype_io, hipLaunchKernelGGL((dwconv_silu_bwd_k<T, KW>), grid, block, lds, st, (const T *)x, x_rs, w,
+                                                    bias, (const T *)dout, dout_rs, (const T *)dout2, dout2_rs, (T *)dx, dx_rs,
+                                                    dw_part, db_part, B, L, (int)Dn));
+    }
   }
   hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn * k, 64)), dim3(1024), 0, st, dw_part, dw, (int64_t)nblk,
                      Dn * k);

@@ -265,7 +265,8 @@ int apertis_dropout_bwd(const void *g, void *dx, int64_t n, float drop_p, uint64
 
 /* Depthwise causal conv1d (k taps, left pad k-1, keep first L) + SiLU on token-major data
  * (replaces core.py:368-375: transpose -> nn.Conv1d(groups=Dn, padding=k-1)[:, :, :L] ->
- * transpose -> F.silu).  x,out: [B,L,Dn] with row strides; w: [Dn,k] fp32; bias: [Dn] fp32. */
+ * transpose -> F.silu).  x,out: [B,L,Dn] with row strides; w: [Dn,k] fp32; bias: [Dn] fp32.
+ * 2 <= k <= 16 (the widths the decode entry points accept), forward and backward; any other k: APERTIS_ERR_UNSUPPORTED. */
 int apertis_dwconv_silu_fwd(const void *x, int64_t x_rs, const float *w, const float *bias,
                             void *out, int64_t out_rs, int64_t B, int64_t L, int64_t Dn,
                             int64_t k, int dtype_io, void *stream);
