@@ -7,7 +7,8 @@ What differs is underneath: the selective scan, the depthwise conv, the gate, th
 dense projections, LayerNorm and the sub-block boundaries, the whole MoE dispatch, the expert
 GEMMs, the dense FFN, the cross-entropy and the optimizer step run as HIP kernels through
 libapertis_hip.so (apertis_llm_amd.ops); stock torch (hipBLASLt) keeps the embedding, the LM head's
-GEMMs, the ViT body and the `standard_mha` fallback.  There is no eager fallback for the kernel
+GEMMs, the ViT body and the `standard_mha` paths the attention kernels do not take (decode with a KV cache,
+output_attentions, head dims other than 64 / 128, left padding).  There is no eager fallback for the kernel
 paths: off-GPU they raise ApertisHipError.
 """
 import functools
@@ -780,6 +781,29 @@ class ApertisAttention(nn.Module):
         y, gated = r
         return y, impl.decode_finish(gated, past_kv)
 
+    def _fused_ok(self, q, att_mask, past_kv, output_att):
+        """Whether this call takes the HIP RoPE + causal attention kernels: on the GPU, fp32 or bf16, D 64 or 128, no KV cache
+        to extend, no attention weights asked for, and every query row keeps at least one valid key (a row without one gets a
+        uniform average over all keys in the reference, finfo.min saturating; the model's mask says so, _AttnMask)."""
+        if not (ops.ATTN_FUSED and q.is_cuda and past_kv is None and not output_att
+                and ops.attention_supported(q, self.num_attention_heads)):
+            return False
+        if att_mask is None:
+            return True
+        if not isinstance(att_mask, _AttnMask):          # an additive mask handed in directly: only the stock path reads it
+            return False
+        kv = att_mask.key_valid
+        return att_mask.fused_ok and (kv is None or tuple(kv.shape) == tuple(q.shape[:2]))
+
+    def _fused_attention(self, q, k, v, att_mask, pos_ids, use_c):
+        key_valid, default_pos = (att_mask.key_valid, att_mask.default_pos) if att_mask is not None else (None, False)
+        if self.rope is not None:
+            # (the model's own positions 0..L-1 go in as None: explicit ones are range-checked on the host, a sync per call)
+            q, k = ops.rope_qk(q, k, None if default_pos else pos_ids, self.rope.cos_cached, self.rope.sin_cached)
+        cache = (k, v) if use_c else None
+        ctxv = ops.causal_attention(q, k, v, self.num_attention_heads, key_valid, self.attention_dropout.p, self.training)
+        return self.out_proj(ctxv), cache
+
     def _heads(self, t):
         B, L, _ = t.shape
         return t.view(B, L, self.num_attention_heads, self.attention_head_size).transpose(1, 2)
@@ -798,9 +822,14 @@ class ApertisAttention(nn.Module):
             out, proxy, cache = self.attention_mechanism_impl(x, attention_mask=att_mask, position_ids=pos_ids,
                                                               past_key_value=past_kv, output_attentions=output_att,
                                                               use_cache=use_c)
+        elif self._fused_ok(q := self.q_proj(x), att_mask, past_kv, output_att):
+            out, cache = self._fused_attention(q, self.k_proj(x), self.v_proj(x), att_mask, pos_ids, use_c)
+            proxy = None
         else:
-            # standard_mha is outside the accelerated path: stock torch.
-            q, k, v = self.q_proj(x), self.k_proj(x), self.v_proj(x)
+            # decode with a KV cache, output_attentions, other head dims, CPU, left padding: stock torch.
+            if isinstance(att_mask, _AttnMask):
+                att_mask = att_mask.additive()
+            k, v = self.k_proj(x), self.v_proj(x)
             if self.rope is not None:
                 q, k = self.rope(q, pos_ids), self.rope(k, pos_ids)
             if use_c and past_kv is not None:
@@ -940,6 +969,22 @@ def _ffn_small_entry(self, h, defer):
 ApertisFeedForward._small_entry = _ffn_small_entry
 
 
+class _AttnMask:
+    """What a standard_mha layer receives as its mask from ApertisModel.forward: the raw key validity [B, L] (None: nothing
+    padded) for the fused kernels, whether the fused path may run (no query row without a valid key), whether the positions
+    are the model's own 0..L-1, and the additive mask of the stock path, built only if that path asks for it."""
+    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive")
+
+    def __init__(self, key_valid, fused_ok, default_pos, make_additive):
+        self.key_valid, self.fused_ok, self.default_pos = key_valid, fused_ok, default_pos
+        self._make, self._additive = make_additive, None
+
+    def additive(self):
+        if self._make is not None:
+            self._additive, self._make = self._make(), None
+        return self._additive
+
+
 class ApertisLayer(nn.Module):
     def __init__(self, config: ApertisConfig):
         super().__init__()
@@ -1045,6 +1090,20 @@ class ApertisModel(nn.Module):
             return None
         return (1.0 - allow.to(inputs_embeds.dtype)) * torch.finfo(inputs_embeds.dtype).min
 
+    def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos):
+        """The standard_mha layers' mask (_AttnMask).  One host sync when a mask is given, as before: whether anything is
+        padded and whether key 0 of every sequence is valid (with no cache, then every query row has a valid key: right
+        padding, the trainer's form, stays on the fused path) come back together."""
+        default_pos = default_pos and past_len == 0
+        if attention_mask is None:
+            return _AttnMask(None, True, default_pos, None)
+        valid = attention_mask.bool()
+        all_valid, col0 = torch.stack((valid.all(), valid[:, 0].all())).tolist()
+        if all_valid:
+            return _AttnMask(None, True, default_pos, None)
+        return _AttnMask(attention_mask, bool(col0) and past_len == 0, default_pos,
+                         lambda: self._prepare_decoder_attention_mask(attention_mask, input_shape, inputs_embeds, past_len))
+
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, pixel_values=None, use_cache=None, output_attentions=None,
@@ -1083,7 +1142,8 @@ class ApertisModel(nn.Module):
         elif cfg.multimodal and pixel_values is not None:
             logger.warning("pixel_values provided with past_key_values: image ignored for this step")
         x = self.embed_dropout(x)
-        mask = None if ssm else self._prepare_decoder_attention_mask(attention_mask, (B, x.shape[1]), x, past_len)
+        mask = None if ssm else self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len,
+                                                     position_ids is None and pos_layers is pos)
 
         all_hs, all_att, all_cache = [], [], []
         lbs, rzs = [], []
@@ -1229,6 +1289,20 @@ class ApertisForCausalLM(nn.Module):
             self.lm_head.weight.data[:n] = old.weight.data[:n]
         self.config.vocab_size = self.lm_head.out_features
         return self.lm_head
+
+    def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos):
+        """The standard_mha layers' mask (_AttnMask).  One host sync when a mask is given, as before: whether anything is
+        padded and whether key 0 of every sequence is valid (with no cache, then every query row has a valid key: right
+        padding, the trainer's form, stays on the fused path) come back together."""
+        default_pos = default_pos and past_len == 0
+        if attention_mask is None:
+            return _AttnMask(None, True, default_pos, None)
+        valid = attention_mask.bool()
+        all_valid, col0 = torch.stack((valid.all(), valid[:, 0].all())).tolist()
+        if all_valid:
+            return _AttnMask(None, True, default_pos, None)
+        return _AttnMask(attention_mask, bool(col0) and past_len == 0, default_pos,
+                         lambda: self._prepare_decoder_attention_mask(attention_mask, input_shape, inputs_embeds, past_len))
 
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,

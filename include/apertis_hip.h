@@ -49,10 +49,11 @@ extern "C" {
  * kernel; measured 15 % SLOWER at the bench shape (profiles/r6_probe_nt2i_vs_nt4r.log), so no caller sets it by default. */
 #define APERTIS_ACT_INTERLEAVED 0x400
 
-/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (round 6: 4.7 - apertis_cross_entropy_fwd_bwd, apertis_layernorm_combine_bwd; round 5: 4.5 - apertis_scan_lookback_*, apertis_tiny_linear_bwd_pad; round 4: 4.4 - lean scan
+/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.8 - apertis_rope_qk_fwd / _bwd,
+ * apertis_attention_fwd / _bwd, apertis_attention_bwd_workspace_bytes: standard_mha; round 6: 4.7 - apertis_cross_entropy_fwd_bwd, apertis_layernorm_combine_bwd; round 5: 4.5 - apertis_scan_lookback_*, apertis_tiny_linear_bwd_pad; round 4: 4.4 - lean scan
  * entry points, apertis_scan_lean_fwd_dt, apertis_grouped_gemm_tn_dense_variant, apertis_weight_prep, apertis_ssm_decode_state_dt).  A host binding should
  * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does). */
-#define APERTIS_ABI_VERSION ((4 << 16) | 7)
+#define APERTIS_ABI_VERSION ((4 << 16) | 8)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
 const char *apertis_arch(void);
@@ -709,6 +710,51 @@ int apertis_clip_coef(const float *partials, int64_t n, float max_norm, float *n
 int apertis_adamw_step(const void *tensors, const int32_t *chunk_tensor, const int32_t *chunk_index,
                        int64_t n_chunks, double lr, double beta1, double beta2, double eps, double weight_decay,
                        int64_t step, const float *norm_coef, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * standard_mha: RoPE and causal attention (RotaryEmbedding.forward, core.py:258-293, and the attention of
+ * ApertisAttention.forward, core.py:639-700, with F.scaled_dot_product_attention's causal / padding mask)
+ *
+ * RoPE rotates interleaved pairs (2j, 2j+1) across the FULL width W of q and of k (the reference's quirk: not per head):
+ *   out[2j] = x[2j]*cos[p][j] - x[2j+1]*sin[p][j],  out[2j+1] = x[2j]*sin[p][j] + x[2j+1]*cos[p][j]
+ * in fp32, each product rounded before the add (bit-identical to the stock module), stored in the io dtype.
+ *   q, k          : [B,L,W] with row strides q_rs / k_rs (batch stride L*rs); q_out, k_out: packed [B,L,W]
+ *   position_ids  : int64 [1 or B, L] with batch stride pos_batch_stride (0 broadcasts one row), or NULL for p = l
+ *   cos/sin_cached: fp32 [max_pos, W/2]; a negative position p reads row p + max_pos (torch's wrap); the CALLER checks
+ *                   explicit positions against [-max_pos, max_pos) (an out-of-range
+ *                   position is never read: its pair comes out NaN); with NULL positions L > max_pos is an argument error
+ * The backward applies the transposed rotation: dx[2j] = g0*cos + g1*sin, dx[2j+1] = -g0*sin + g1*cos.
+ */
+int apertis_rope_qk_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const int64_t *position_ids,
+                        int64_t pos_batch_stride, const float *cos_cached, const float *sin_cached, int64_t max_pos,
+                        void *q_out, void *k_out, int64_t B, int64_t L, int64_t W, int dtype, void *stream);
+int apertis_rope_qk_bwd(const void *dq_out, int64_t dq_rs, const void *dk_out, int64_t dk_rs, const int64_t *position_ids,
+                        int64_t pos_batch_stride, const float *cos_cached, const float *sin_cached, int64_t max_pos,
+                        void *dq, void *dk, int64_t B, int64_t L, int64_t W, int dtype, void *stream);
+
+/* Causal softmax attention, flash style (scores never reach memory):
+ *   O[b,i,h] = sum_{j <= i, key_valid[b,j] != 0} drop(P[i,j]) V[b,j,h],  P = softmax_j(scale * Q[b,i,h].K[b,j,h]),
+ *   scale = 1/sqrt(D) in fp32.
+ *   q, k, v, out  : [B,L,H*D] token-major, head h in columns [h*D, (h+1)*D), row strides *_rs (batch stride L*rs);
+ *                   row starts and strides on 16-byte boundaries (else APERTIS_ERR_UNSUPPORTED)
+ *   key_valid     : int64 [B,L] (the raw attention_mask, nonzero = attend) or NULL for no padding.  A query row with
+ *                   no valid key gets O = 0 and LSE = +inf (callers keep such rows off this path: the reference averages)
+ *   lse           : fp32 [B,H,L] output, natural-log softmax normaliser, kept for the backward
+ *   D             : 64 or 128 (else APERTIS_ERR_UNSUPPORTED); dtype fp32 (v_mfma_f32_16x16x4_f32) or bf16
+ *                   (v_mfma_f32_16x16x32_bf16, P rounded to bf16 for P.V); fp32 accumulation either way
+ *   dropout_p     : in [0,1); element (i,j) of head (b,h) is kept iff drop_keep(seed, (b*H+h)*L + i, j, L, p*65536)
+ *                   (common.h), kept probabilities scaled by 1/(1-p); the backward regenerates the same mask
+ * The backward recomputes P from q, k and lse: workspace = apertis_attention_bwd_workspace_bytes() bytes (fp32 [B,H,L],
+ * rowsum(dout*out)), then one kernel per 64-key block writes dK, dV and one per 64-query block writes dQ: no atomics,
+ * the same bits on every run.  dq, dk, dv: [B,L,H*D] with row stride d_rs, in the io dtype. */
+int apertis_attention_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                          const int64_t *key_valid, void *out, int64_t out_rs, float *lse, int64_t B, int64_t L, int64_t H,
+                          int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
+int64_t apertis_attention_bwd_workspace_bytes(int64_t B, int64_t L, int64_t H);
+int apertis_attention_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                          const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
+                          const int64_t *key_valid, float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B,
+                          int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,432 @@
+"""standard_mha on the HIP kernels (csrc/attention.hip, ops/attention.py): RoPE, causal attention forward and backward.
+
+  - the reference capture of config 1 (create-model 125M, standard_mha) on the fused path AND on the stock GPU path
+  - RoPE bit-identical to RotaryEmbedding; its backward against stock autograd
+  - attention forward / backward against an fp64 explicit softmax (causal + key padding, dropout with the kernel's mask
+    restated in numpy); bf16 held relative to stock bf16 SDPA on the same inputs
+  - determinism, training parity with ATTN_FUSED off, the cases that stay on the stock path
+"""
+import json
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import load_golden, rel_error_report
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture
+def fused_switch():
+    from apertis_llm_amd import ops
+    prev = ops.ATTN_FUSED
+    yield ops
+    ops.ATTN_FUSED = prev
+
+
+def _spy(monkeypatch):
+    """Count the fused attention calls the model makes (ops.causal_attention is looked up on the package at call time)."""
+    from apertis_llm_amd import ops
+    calls = []
+    real = ops.causal_attention
+
+    def spy(*a, **k):
+        calls.append(a[0].shape)
+        return real(*a, **k)
+    monkeypatch.setattr(ops, "causal_attention", spy)
+    return calls
+
+
+# ------------------------------------------------------------------------------------------------ reference capture
+@pytest.mark.parametrize("fused", [True, False])
+def test_config1_125m_standard_mha_matches_reference_capture(dev, fused, fused_switch, monkeypatch):
+    """create-model 125M (standard_mha, vocab 32000), B=2, L=512, fp32 eval: the bars of the selective_ssm capture test."""
+    import apertis_llm_amd as A
+    from oracle import seeded
+    ops = fused_switch
+    ops.ATTN_FUSED = fused
+    calls = _spy(monkeypatch)
+    g = load_golden("config1_125m")
+    model = A.create_apertis_model("125M", vocab_size_override=32000)
+    assert model.config.to_dict() == json.loads(str(g["standard_mha::config_json"]))
+    model.load_state_dict(seeded.fill_state_dict(model.state_dict()))
+    model = model.to(dev).eval()
+    ids = g["input_ids"].to(dev)
+    with torch.no_grad():
+        loss, logits = model(input_ids=ids, attention_mask=torch.ones_like(ids), labels=ids)[:2]
+    assert len(calls) == (10 if fused else 0)
+    tag = "fused" if fused else "stock"
+    rel_error_report(f"config1_125m standard_mha ({tag}, GPU) logits[:, ::37, ::251]", logits[:, ::37, ::251],
+                     g["standard_mha::logits_sample"])
+    assert abs(float(loss) - float(g["standard_mha::loss"])) <= 1e-5 * float(g["standard_mha::loss"])
+    assert abs(float(logits.abs().max()) - float(g["standard_mha::logits_absmax"])) <= \
+        1e-4 * float(g["standard_mha::logits_absmax"])
+
+
+# ------------------------------------------------------------------------------------------------ RoPE
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("offset", [None, "shifted", "per_batch"])
+def test_rope_forward_bit_identical_and_backward(dev, dtype, offset):
+    import apertis_llm_amd as A
+    from apertis_llm_amd import ops
+    B, L, W = 3, 77, 896
+    rope = A.model.RotaryEmbedding(W, 2048).to(dev)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    q = torch.randn(B, L, W, device=dev, generator=gen).to(dtype).requires_grad_()
+    k = torch.randn(B, L, W, device=dev, generator=gen).to(dtype).requires_grad_()
+    pos = None
+    if offset == "shifted":
+        pos = torch.arange(100, 100 + L, device=dev).unsqueeze(0)
+    elif offset == "per_batch":
+        pos = torch.arange(L, device=dev).unsqueeze(0) + torch.tensor([[0], [5], [1900]], device=dev)
+    qs, ks = rope(q, pos), rope(k, pos)
+    qf, kf = ops.rope_qk(q, k, pos, rope.cos_cached, rope.sin_cached)
+    assert qf.dtype == dtype and torch.equal(qf, qs) and torch.equal(kf, ks)
+    gq = torch.randn(qs.shape, device=dev, generator=gen).to(dtype)
+    gk = torch.randn(ks.shape, device=dev, generator=gen).to(dtype)
+    ref = torch.autograd.grad((qs, ks), (q, k), (gq, gk))
+    got = torch.autograd.grad((qf, kf), (q, k), (gq, gk))
+    for r, t in zip(ref, got):
+        if dtype == torch.float32:
+            torch.testing.assert_close(t, r, rtol=1e-6, atol=1e-7)
+        else:
+            torch.testing.assert_close(t.float(), r.float(), rtol=1e-2, atol=1e-2)
+
+
+def test_rope_out_of_range_positions_raise(dev):
+    """Positions outside the rotary table: the stock module's gather raises IndexError (checked on the CPU only - on the GPU
+    the same gather is a device-side fault), and so does the op, on the host before any launch.  Negative positions wrap as
+    torch indexing wraps them."""
+    import apertis_llm_amd as A
+    from apertis_llm_amd import ops
+    rope_cpu = A.model.RotaryEmbedding(128, 64)
+    rope = A.model.RotaryEmbedding(128, 64).to(dev)
+    q = torch.randn(1, 8, 128)
+    for bad in (torch.arange(60, 68)[None], torch.arange(-65, -57)[None]):
+        with pytest.raises(IndexError):
+            rope_cpu(q, bad)
+        with pytest.raises(IndexError):
+            ops.rope_qk(q.to(dev), q.to(dev), bad.to(dev), rope.cos_cached, rope.sin_cached)
+    with pytest.raises(IndexError):
+        ops.rope_qk(torch.randn(1, 65, 128, device=dev), torch.randn(1, 65, 128, device=dev), None, rope.cos_cached,
+                    rope.sin_cached)
+    wrap = torch.arange(-4, 4)[None]
+    qf, _ = ops.rope_qk(q.to(dev), q.to(dev), wrap.to(dev), rope.cos_cached, rope.sin_cached)
+    assert torch.equal(qf.cpu(), rope_cpu(q, wrap))
+
+
+# ------------------------------------------------------------------------------------------------ attention vs fp64
+def _drop_keep_np(seed, row, col, ncols, thresh16):
+    """common.h drop_keep restated: 16 random bits per element from a 32-bit avalanche of (element pair, seed)."""
+    lin = row.astype(np.uint64) * np.uint64(ncols) + col.astype(np.uint64)
+    s_lo, s_hi = np.uint32(seed & 0xffffffff), np.uint32((seed >> 32) & 0xffffffff)
+    with np.errstate(over="ignore"):
+        h = (lin >> np.uint64(1)).astype(np.uint32) ^ s_lo
+        h = h + (lin >> np.uint64(33)).astype(np.uint32) * np.uint32(0x9E3779B9) + s_hi
+        h ^= h >> np.uint32(16)
+        h = h * np.uint32(0x85ebca6b)
+        h ^= h >> np.uint32(13)
+        h = h * np.uint32(0xc2b2ae35)
+        h ^= h >> np.uint32(16)
+    r16 = np.where((lin & np.uint64(1)) != 0, h >> np.uint32(16), h & np.uint32(0xffff))
+    return r16 >= thresh16
+
+
+def _keep_mask(seed, B, H, L, p):
+    bh, i, j = np.meshgrid(np.arange(B * H), np.arange(L), np.arange(L), indexing="ij")
+    return _drop_keep_np(seed, bh * L + i, j, L, int(p * 65536)).reshape(B, H, L, L)
+
+
+def _ref_attention(q, k, v, H, key_valid=None, keep=None, p=0.0):
+    """Explicit softmax in whatever dtype q has: [B, L, H*D] in and out."""
+    B, L, W = q.shape
+    D = W // H
+    qh, kh, vh = (t.view(B, L, H, D).transpose(1, 2) for t in (q, k, v))
+    s = qh @ kh.transpose(-1, -2) * (1.0 / float(np.sqrt(np.float32(D))))
+    allow = torch.ones(L, L, dtype=torch.bool, device=q.device).tril()[None, None]
+    if key_valid is not None:
+        allow = allow & key_valid.bool()[:, None, None, :]
+    s = s.masked_fill(~allow, float("-inf"))
+    pr = torch.softmax(s, dim=-1)
+    if keep is not None:
+        pr = pr * torch.as_tensor(keep, device=q.device).to(pr.dtype) / (1.0 - p)
+    return (pr @ vh).transpose(1, 2).reshape(B, L, W)
+
+
+def _inputs(dev, B, L, H, D, dtype, seed, padded):
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    q, k, v, do = (torch.randn(B, L, H * D, device=dev, generator=gen).to(dtype) for _ in range(4))
+    kv = None
+    if padded:
+        kv = torch.ones(B, L, dtype=torch.long, device=dev)
+        for b in range(B):
+            kv[b, max(1, (L * (b + 1)) // (B + 1)):] = 0        # right padding, a different length per sequence
+    return q, k, v, do, kv
+
+
+def _fwd_bwd(fn, q, k, v, do):
+    q, k, v = (t.detach().clone().requires_grad_() for t in (q, k, v))
+    o = fn(q, k, v)
+    grads = torch.autograd.grad(o, (q, k, v), do)
+    return (o.detach(), *grads)
+
+
+def _zero_floor(v, do):
+    """Absolute bound for a product whose exact value is zero: 1e-5 of the size of one dP = dO . V term."""
+    return 1e-5 * float(v.abs().max().float() * do.abs().max().float()) * v.shape[-1] ** 0.5
+
+
+SHAPES = [(64, 1, 2, 3), (64, 7, 2, 3), (64, 64, 3, 2), (64, 257, 2, 3), (64, 512, 1, 4), (64, 2048, 1, 2),
+          (128, 1, 1, 2), (128, 7, 2, 1), (128, 64, 2, 2), (128, 257, 2, 2), (128, 512, 2, 1), (128, 2048, 1, 2)]
+NAMES = ("O", "dQ", "dK", "dV")
+
+
+@pytest.mark.parametrize("D,L,B,H", SHAPES)
+@pytest.mark.parametrize("padded", [False, True])
+def test_attention_fp32_matches_fp64(dev, D, L, B, H, padded):
+    from apertis_llm_amd import ops
+    q, k, v, do, kv = _inputs(dev, B, L, H, D, torch.float32, 11 + L + D, padded)
+    got = _fwd_bwd(lambda a, b, c: ops.causal_attention(a, b, c, H, kv), q, k, v, do)
+    ref = _fwd_bwd(lambda a, b, c: _ref_attention(a, b, c, H, kv), q.double(), k.double(), v.double(), do.double())
+    for n, g_, r in zip(NAMES, got, ref):
+        name = f"attention fp32 D{D} L{L} B{B} H{H} pad{int(padded)} {n}"
+        if float(r.abs().max()) == 0.0:
+            # (dQ at L = 1 is exactly zero: P (dP - rowsum(dO*O)) cancels, to the summation order of two fp32 dot products)
+            rep = rel_error_report(name, g_, r, check=False)
+            assert rep["max_abs"] <= _zero_floor(v, do), rep
+        else:
+            rel_error_report(name, g_, r, rtol=1e-4)
+
+
+@pytest.mark.parametrize("D,L,B,H", SHAPES)
+@pytest.mark.parametrize("padded", [False, True])
+def test_attention_bf16_within_twice_stock_sdpa_error(dev, D, L, B, H, padded):
+    """No absolute bf16 bound has been measured: the kernel's max error against fp64 is held to twice that of stock bf16
+    SDPA on the same inputs (plus 1e-6 of the reference's magnitude, and _zero_floor for dQ at L = 1, exactly zero)."""
+    from apertis_llm_amd import ops
+    q, k, v, do, kv = _inputs(dev, B, L, H, D, torch.bfloat16, 23 + L + D, padded)
+    allow = torch.ones(L, L, dtype=torch.bool, device=dev).tril()[None, None]
+    if kv is not None:
+        allow = allow & kv.bool()[:, None, None, :]
+
+    def stock(a, b, c):
+        ah, bh, ch = (t.view(B, L, H, D).transpose(1, 2) for t in (a, b, c))
+        return F.scaled_dot_product_attention(ah, bh, ch, attn_mask=allow).transpose(1, 2).reshape(B, L, H * D)
+    got = _fwd_bwd(lambda a, b, c: ops.causal_attention(a, b, c, H, kv), q, k, v, do)
+    base = _fwd_bwd(stock, q, k, v, do)
+    ref = _fwd_bwd(lambda a, b, c: _ref_attention(a, b, c, H, kv), q.double(), k.double(), v.double(), do.double())
+    for n, g_, s_, r in zip(NAMES, got, base, ref):
+        rep = rel_error_report(f"attention bf16 D{D} L{L} B{B} H{H} pad{int(padded)} {n}", g_, r, check=False)
+        srep = rel_error_report(f"stock SDPA bf16 D{D} L{L} B{B} H{H} pad{int(padded)} {n}", s_, r, check=False)
+        assert rep["max_abs"] <= 2 * srep["max_abs"] + 1e-6 * rep["ref_absmax"] + \
+            (_zero_floor(v, do) if rep["ref_absmax"] == 0.0 else 0.0), (n, rep, srep)
+
+
+# ------------------------------------------------------------------------------------------------ dropout
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_attention_dropout_mask_matches_numpy_hash(dev, dtype):
+    from apertis_llm_amd import ops
+    B, L, H, D, p, seed = 2, 200, 2, 64, 0.1, 0x1234_5678_9abc
+    q, k, v, do, kv = _inputs(dev, B, L, H, D, dtype, 5, True)
+    keep = _keep_mask(seed, B, H, L, p)
+    # the keep fraction over all L x L elements: binomial, 6 sigma
+    n, pk = keep.size, 1.0 - int(p * 65536) / 65536
+    assert abs(keep.mean() - pk) <= 6 * np.sqrt(pk * (1 - pk) / n), keep.mean()
+    fn = lambda a, b, c: ops.attention._CausalAttention.apply(a, b, c, H, kv, p, seed)     # noqa: E731
+    got = _fwd_bwd(fn, q, k, v, do)
+    ref = _fwd_bwd(lambda a, b, c: _ref_attention(a, b, c, H, kv, keep, p), q.double(), k.double(), v.double(), do.double())
+    if dtype == torch.float32:
+        for n_, g_, r in zip(NAMES, got, ref):
+            rel_error_report(f"attention dropout fp32 {n_}", g_, r, rtol=1e-4)
+    else:
+        base = _fwd_bwd(lambda a, b, c: _ref_attention(a, b, c, H, kv, keep, p), q, k, v, do)   # the same math in bf16
+        for n_, g_, s_, r in zip(NAMES, got, base, ref):
+            rep = rel_error_report(f"attention dropout bf16 {n_}", g_, r, check=False)
+            srep = rel_error_report(f"explicit bf16 dropout {n_}", s_, r, check=False)
+            assert rep["max_abs"] <= 2 * srep["max_abs"] + 1e-6 * rep["ref_absmax"], (n_, rep, srep)
+    # same seed: the same bits; another seed: another mask
+    again = _fwd_bwd(fn, q, k, v, do)
+    assert all(torch.equal(a, b) for a, b in zip(got, again))
+    other = _fwd_bwd(lambda a, b, c: ops.attention._CausalAttention.apply(a, b, c, H, kv, p, seed + 1), q, k, v, do)
+    assert not torch.equal(got[0], other[0])
+
+
+def test_attention_dropout_seed_comes_from_torch_rng(dev):
+    from apertis_llm_amd import ops
+    q, k, v, _, _ = _inputs(dev, 1, 64, 2, 64, torch.float32, 3, False)
+    torch.manual_seed(7)
+    a = ops.causal_attention(q, k, v, 2, None, 0.3, training=True)
+    torch.manual_seed(7)
+    b = ops.causal_attention(q, k, v, 2, None, 0.3, training=True)
+    c = ops.causal_attention(q, k, v, 2, None, 0.3, training=True)
+    assert torch.equal(a, b) and not torch.equal(a, c)
+    assert torch.equal(ops.causal_attention(q, k, v, 2, None, 0.3, training=False),
+                       ops.causal_attention(q, k, v, 2, None, 0.0))
+
+
+def _small_cfg(A, **kw):
+    base = dict(vocab_size=512, hidden_size=256, num_hidden_layers=2, num_attention_heads=4, intermediate_size=512,
+                attention_type="standard_mha", max_position_embeddings=512)
+    base.update(kw)
+    return A.ApertisConfig(**base)
+
+
+def test_checkpointed_layer_sees_the_same_dropout_mask(dev):
+    import apertis_llm_amd as A
+    torch.manual_seed(0)
+    model = A.ApertisForCausalLM(_small_cfg(A, attention_probs_dropout_prob=0.1, hidden_dropout_prob=0.0)).to(dev).train()
+    ids = torch.randint(4, 512, (2, 96), device=dev)
+    grads = []
+    for ckpt in (False, True):
+        model.model.gradient_checkpointing = ckpt
+        model.zero_grad(set_to_none=True)
+        torch.manual_seed(42)
+        loss = model(input_ids=ids, labels=ids, use_cache=False)[0]
+        loss.backward()
+        grads.append({n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None})
+    assert grads[0].keys() == grads[1].keys() and len(grads[0]) > 0
+    for n in grads[0]:
+        torch.testing.assert_close(grads[1][n], grads[0][n], rtol=1e-5, atol=1e-7, msg=n)
+
+
+# ------------------------------------------------------------------------------------------------ determinism
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_attention_backward_is_deterministic(dev, dtype):
+    from apertis_llm_amd import ops
+    q, k, v, do, kv = _inputs(dev, 2, 2048, 2, 64, dtype, 9, True)
+    fn = lambda a, b, c: ops.attention._CausalAttention.apply(a, b, c, 2, kv, 0.1, 99)     # noqa: E731
+    r1, r2 = _fwd_bwd(fn, q, k, v, do), _fwd_bwd(fn, q, k, v, do)
+    assert all(torch.equal(a, b) for a, b in zip(r1, r2))
+
+
+# ------------------------------------------------------------------------------------------------ training parity
+def _grads(model, ids, mask=None, autocast=False):
+    model.zero_grad(set_to_none=True)
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+        loss = model(input_ids=ids, attention_mask=mask, labels=ids, use_cache=False)[0]
+    loss.backward()
+    return float(loss), {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None}
+
+
+@pytest.mark.parametrize("padded", [False, True])
+def test_training_gradients_match_stock_path(dev, fused_switch, monkeypatch, padded):
+    import apertis_llm_amd as A
+    ops = fused_switch
+    torch.manual_seed(0)
+    model = A.ApertisForCausalLM(_small_cfg(A, attention_probs_dropout_prob=0.0, hidden_dropout_prob=0.0)).to(dev).train()
+    ids = torch.randint(4, 512, (2, 160), device=dev)
+    mask = None
+    if padded:
+        mask = torch.ones_like(ids)
+        mask[1, 100:] = 0
+    calls = _spy(monkeypatch)
+    ops.ATTN_FUSED = True
+    lf, gf = _grads(model, ids, mask)
+    assert len(calls) == 2
+    ops.ATTN_FUSED = False
+    ls, gs = _grads(model, ids, mask)
+    assert len(calls) == 2 and gf.keys() == gs.keys()
+    assert abs(lf - ls) <= 1e-5 * abs(ls)
+    for n in gs:
+        rel_error_report(f"train grad fp32 pad{int(padded)} {n}", gf[n], gs[n], rtol=1e-4)
+    if padded:
+        return
+    # bf16 autocast: finite, and close to the stock path's gradients (relative L2 per parameter)
+    ops.ATTN_FUSED = True
+    lf, gf = _grads(model, ids, mask, autocast=True)
+    ops.ATTN_FUSED = False
+    ls, gs = _grads(model, ids, mask, autocast=True)
+    assert np.isfinite(lf) and abs(lf - ls) <= 2e-2 * abs(ls)
+    for n in gs:
+        assert torch.isfinite(gf[n]).all(), n
+        rel = float((gf[n] - gs[n]).norm() / (gs[n].norm() + 1e-12))
+        assert rel < 5e-2, (n, rel)
+
+
+# ------------------------------------------------------------------------------------------------ stock-path cases
+def _both_ways(ops, fn):
+    ops.ATTN_FUSED = True
+    a = fn()
+    ops.ATTN_FUSED = False
+    b = fn()
+    ops.ATTN_FUSED = True
+    return a, b
+
+
+def _flat(x):
+    if isinstance(x, torch.Tensor):
+        return [x]
+    if isinstance(x, (tuple, list)):
+        return [t for e in x for t in _flat(e)]
+    return []
+
+
+@pytest.mark.parametrize("case", ["output_attentions", "decode", "head_dim_48", "left_padded"])
+def test_fallback_cases_run_the_stock_path(dev, fused_switch, monkeypatch, case):
+    import apertis_llm_amd as A
+    ops = fused_switch
+    torch.manual_seed(0)
+    cfg = _small_cfg(A, hidden_size=192) if case == "head_dim_48" else _small_cfg(A)
+    model = A.ApertisForCausalLM(cfg).to(dev).eval()
+    ids = torch.randint(4, 512, (2, 40), device=dev)
+    past = None
+    if case == "decode":
+        ops.ATTN_FUSED = False
+        with torch.no_grad():
+            past = model(input_ids=ids[:, :-1], use_cache=True)[4]
+    mask = None
+    if case == "left_padded":
+        mask = torch.ones_like(ids)
+        mask[0, :5] = 0
+    calls = _spy(monkeypatch)
+
+    def run():
+        with torch.no_grad():
+            if case == "decode":
+                pos = torch.full((2, 1), ids.shape[1] - 1, dtype=torch.long, device=dev)
+                return model(input_ids=ids[:, -1:], past_key_values=past, position_ids=pos, use_cache=True,
+                             attention_mask=torch.ones_like(ids))
+            return model(input_ids=ids, attention_mask=mask, output_attentions=case == "output_attentions", use_cache=False)
+    a, b = _both_ways(ops, run)
+    assert calls == []
+    fa, fb = _flat(a), _flat(b)
+    assert len(fa) == len(fb) and len(fa) > 0
+    assert all(torch.equal(x, y) for x, y in zip(fa, fb))
+
+
+def test_generate_same_tokens_fused_and_stock(dev, fused_switch, monkeypatch):
+    import apertis_llm_amd as A
+    ops = fused_switch
+    torch.manual_seed(0)
+    model = A.ApertisForCausalLM(_small_cfg(A)).to(dev).eval()
+    ids = torch.randint(4, 512, (2, 24), device=dev)
+    calls = _spy(monkeypatch)
+    a, b = _both_ways(ops, lambda: model.generate(input_ids=ids, max_new_tokens=12, do_sample=False))
+    assert len(calls) == 2                      # the prefill of the fused run, one per layer
+    assert torch.equal(a, b)
+
+
+def test_prefill_cache_is_the_stock_cache(dev, fused_switch, monkeypatch):
+    """Prefill with use_cache on the fused path returns what the stock path returns: (k after RoPE, v) per layer (RoPE is
+    bit-identical and v is the same projection)."""
+    import apertis_llm_amd as A
+    ops = fused_switch
+    torch.manual_seed(0)
+    model = A.ApertisForCausalLM(_small_cfg(A)).to(dev).eval()
+    ids = torch.randint(4, 512, (2, 33), device=dev)
+    calls = _spy(monkeypatch)
+
+    def run():
+        with torch.no_grad():
+            return model(input_ids=ids, use_cache=True)[4]
+    a, b = _both_ways(ops, run)
+    assert len(calls) == 2
+    assert len(a) == len(b) == 2
+    # layer 0 sees the same input both ways: the same bits; deeper layers' inputs differ by the attention's rounding
+    assert torch.equal(a[0][0], b[0][0]) and torch.equal(a[0][1], b[0][1])
+    for (ka, va), (kb, vb) in zip(a[1:], b[1:]):
+        assert ka.shape == kb.shape and va.shape == vb.shape
+        torch.testing.assert_close(ka, kb, rtol=1e-4, atol=1e-5)
+        torch.testing.assert_close(va, vb, rtol=1e-4, atol=1e-5)
