@@ -635,6 +635,25 @@ __device__ __forceinline__ float wave_sum(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// Mean of a wave's row held as IT float4 chunks per lane (chunk i of lane l: columns (l + 64 i) * 4 .. + 3, ignored past H):
+// sum / H, and for a row whose elements are all equal that value itself.  sum / H misses it by an ulp (260 copies of 0.3),
+// and then x - mean is that ulp in every column: at the default eps (1e-12) rstd = 1e6 turned it into an error of up to 0.67
+// in the normalised row, where the stock LayerNorm is exact.  Every other row keeps the sum's bits.
+template <int IT>
+__device__ __forceinline__ float row_mean(const float4 (&v)[IT], int lane, int H) {
+  const float x0 = __shfl(v[0].x, 0);
+  float s = 0.f;
+  bool same = true;
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+    if ((lane + 64 * i) * 4 < H) {
+      s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+      same = same && v[i].x == x0 && v[i].y == x0 && v[i].z == x0 && v[i].w == x0;
+    }
+  const float m = wave_sum(s) * inv_h(H);
+  return __builtin_amdgcn_ballot_w64(!same) == 0 ? x0 : m;
+}
+
 __device__ __forceinline__ int expert_of_row(const int32_t *offsets, int E, int r) {
   int e = 0;
   while (e + 1 < E && offsets[e + 1] <= r) ++e;
@@ -656,14 +675,12 @@ gather_ln_fwd_k(const TX *__restrict__ x, const int32_t *__restrict__ row_token,
   const int e = offsets ? expert_of_row(offsets, E, (int)r) : 0;
   const TX *src = x + (row_token ? (int64_t)row_token[r] : r) * H;   // row_token == NULL: plain LayerNorm
   float4 v[IT];
-  float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     int c = (lane + 64 * i) * 4;
     v[i] = c < H ? load4s<TX>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   }
-  const float mean = wave_sum(sum) * inv_h(H);
+  const float mean = row_mean<IT>(v, lane, H);
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
@@ -719,14 +736,12 @@ moe_route_small_k(const float *__restrict__ logits, float *__restrict__ gates, i
     const int e = expert_of_row(s_off, E, r);
     const TX *src = x + (int64_t)s_rtok[r] * H;
     float4 v[IT];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       int c = (lane + 64 * i) * 4;
       v[i] = c < H ? load4s<TX>(src + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-      sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float mean = wave_sum(sum) * inv_h(H);
+    const float mean = row_mean<IT>(v, lane, H);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -1008,7 +1023,6 @@ dropadd_ln_fwd_k(const TO *__restrict__ blk, const int32_t *__restrict__ slot_of
   const float ks = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
   const uint32_t th = (uint32_t)(drop_p * 65536.f);
   float4 v[IT];
-  float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     const int c = (lane + 64 * i) * 4;
@@ -1041,12 +1055,11 @@ dropadd_ln_fwd_k(const TO *__restrict__ blk, const int32_t *__restrict__ slot_of
       store4<TX>(y + r * H + c, v[i]);
       // the norm sees y as stored (a no-op for the fp32 stream)
       v[i] = make_float4(to_f32(from_f32<TX>(v[i].x)), to_f32(from_f32<TX>(v[i].y)), to_f32(from_f32<TX>(v[i].z)), to_f32(from_f32<TX>(v[i].w)));
-      sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     } else {
       v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
-  const float mean = wave_sum(sum) * inv_h(H);
+  const float mean = row_mean<IT>(v, lane, H);
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
@@ -1703,13 +1716,11 @@ router_fwd_k(const TX *__restrict__ x, const float *__restrict__ gamma, const fl
   for (int64_t r = wave; r < T; r += nw) {
     fetch(nxt, r + nw);   // the wave's next row is in flight while this one is reduced
     float4 v[IT];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       v[i] = raw_to_f4(cur[i]);
-      sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float mean = wave_sum(sum) * inv_h(H);
+    const float mean = row_mean<IT>(v, lane, H);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -1794,7 +1805,6 @@ dropadd_ln_router_fwd_k(const TO *__restrict__ blk, const TX *__restrict__ res, 
     fetch(bn, rn, r + nw);
     // ---- boundary: y = res + dropout(blk); statistics of y as stored
     float4 v[IT];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int c = (lane + 64 * i) * 4;
@@ -1810,12 +1820,11 @@ dropadd_ln_router_fwd_k(const TO *__restrict__ blk, const TX *__restrict__ res, 
         v[i] = make_float4(rr.x + e[0], rr.y + e[1], rr.z + e[2], rr.w + e[3]);
         store4<TX>(y + r * H + c, v[i]);
         v[i] = make_float4(to_f32(from_f32<TX>(v[i].x)), to_f32(from_f32<TX>(v[i].y)), to_f32(from_f32<TX>(v[i].z)), to_f32(from_f32<TX>(v[i].w)));
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       } else {
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
-    const float mean = wave_sum(sum) * inv_h(H);
+    const float mean = row_mean<IT>(v, lane, H);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -1827,7 +1836,6 @@ dropadd_ln_router_fwd_k(const TO *__restrict__ blk, const TX *__restrict__ res, 
     }
     const float rstd = rsqrtf(wave_sum(sq) * inv_h(H) + eps);
     // ---- xn = LayerNorm(y), stored; the router continues on xn AS STORED
-    float rsum = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int c = (lane + 64 * i) * 4;
@@ -1837,12 +1845,11 @@ dropadd_ln_router_fwd_k(const TO *__restrict__ blk, const TX *__restrict__ res, 
                                      (v[i].z - mean) * rstd * g4.z + b4.z, (v[i].w - mean) * rstd * g4.w + b4.w);
         store4<TO>(xn + r * H + c, o);
         v[i] = make_float4(to_f32(from_f32<TO>(o.x)), to_f32(from_f32<TO>(o.y)), to_f32(from_f32<TO>(o.z)), to_f32(from_f32<TO>(o.w)));
-        rsum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       }
     }
     if (lane == 0) { mean_o[r] = mean; rstd_o[r] = rstd; }
     // ---- router: logits = Linear(router_norm(xn))  (router_fwd_k)
-    const float rmean = wave_sum(rsum) * inv_h(H);
+    const float rmean = row_mean<IT>(v, lane, H);
     float rsq = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -2160,7 +2167,6 @@ moe_enter_small_k(const TO *__restrict__ blk, const TX *__restrict__ res, const 
       }
     }
     float4 v[IT];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int c = (lane + 64 * i) * 4;
@@ -2169,12 +2175,11 @@ moe_enter_small_k(const TO *__restrict__ blk, const TX *__restrict__ res, const 
         v[i] = make_float4(rr.x + a.x, rr.y + a.y, rr.z + a.z, rr.w + a.w);
         store4<TX>(y + (int64_t)r * H + c, v[i]);
         v[i] = make_float4(to_f32(from_f32<TX>(v[i].x)), to_f32(from_f32<TX>(v[i].y)), to_f32(from_f32<TX>(v[i].z)), to_f32(from_f32<TX>(v[i].w)));
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       } else {
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
-    const float mean = wave_sum(sum) * inv_h(H);
+    const float mean = row_mean<IT>(v, lane, H);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -2185,7 +2190,6 @@ moe_enter_small_k(const TO *__restrict__ blk, const TX *__restrict__ res, const 
       }
     }
     const float rstd = rsqrtf(wave_sum(sq) * inv_h(H) + eps);
-    float rsum = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int c = (lane + 64 * i) * 4;
@@ -2202,10 +2206,9 @@ moe_enter_small_k(const TO *__restrict__ blk, const TX *__restrict__ res, const 
         } else {
           sXN[r * Q + lane + 64 * i] = __builtin_bit_cast(rawo_t, o);
         }
-        rsum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       }
     }
-    const float rmean = wave_sum(rsum) * inv_h(H);
+    const float rmean = row_mean<IT>(v, lane, H);
     float rsq = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -2256,13 +2259,11 @@ moe_enter_small_k(const TO *__restrict__ blk, const TX *__restrict__ res, const 
     const int e = expert_of_row(s_off, NN, r);
     const rawo_t *src = sXN + s_rtok[r] * Q;
     float4 v[IT];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       v[i] = lane + 64 * i < Q ? raw_to_f4(src[lane + 64 * i]) : make_float4(0.f, 0.f, 0.f, 0.f);
-      sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float mean = wave_sum(sum) * inv_h(H);
+    const float mean = row_mean<IT>(v, lane, H);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
@@ -2334,7 +2335,6 @@ decode_ln_inproj_k(const bf16_t *__restrict__ blk, const int32_t *__restrict__ s
   // ---- the boundary: a wave per row (dropadd_ln_fwd_k, drop_p = 0) ----
   for (int r = ks; LN && r < S; r += KS) {
     float4 v[IT];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int c = (lane + 64 * i) * 4;
@@ -2356,12 +2356,11 @@ decode_ln_inproj_k(const bf16_t *__restrict__ blk, const int32_t *__restrict__ s
         const float4 rr = load4s<float>(res + (int64_t)r * H + c);
         v[i] = make_float4(rr.x + a.x, rr.y + a.y, rr.z + a.z, rr.w + a.w);
         if (blockIdx.x == 0) store4<float>(y + (int64_t)r * H + c, v[i]);
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       } else {
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
-    const float mean = wave_sum(sum) * inv_h(H);
+    const float mean = row_mean<IT>(v, lane, H);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
