@@ -26,6 +26,55 @@ static inline int apertis_check_launch() {
 
 __host__ __device__ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// hipLaunchKernelGGL with `lds` bytes of dynamic LDS: a request above the default 48 KiB raises the kernel's limit first
+template <typename... P, typename... A>
+static inline void launch_lds(void (*kf)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  if (lds > 48 * 1024) hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kf, grid, block, lds, st, args...);
+}
+
+// The fixed-order column fold of per-block partial rows, in[*][cols] fp32: the 1024-thread block x sums rows [r0, r1) of the
+// columns c = 64 x + lane - 16 waves take every 16th row with four loads in flight, then wave 0 adds their 16 sums in order
+// and hands each column's total to store(c, t) (c < cols).  The body of colsum_kernel, colsum_rows_k, fold_rows_k, ln_fold_k.
+template <typename Store>
+__device__ __forceinline__ void colsum_block(const float *__restrict__ in, int64_t r0, int64_t r1, int64_t cols, Store store) {
+  __shared__ float part[16][64];
+  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
+  const int64_t c = (int64_t)blockIdx.x * 64 + lane;
+  float s = 0.f;
+  if (c < cols) {
+    int64_t r = r0 + seg;
+    for (; r + 48 < r1; r += 64) {
+      float a0 = in[r * cols + c], a1 = in[(r + 16) * cols + c], a2 = in[(r + 32) * cols + c], a3 = in[(r + 48) * cols + c];
+      s += (a0 + a1) + (a2 + a3);
+    }
+    for (; r < r1; r += 16) s += in[r * cols + c];
+  }
+  part[seg][lane] = s;
+  __syncthreads();
+  if (seg == 0 && c < cols) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t += part[i][lane];
+    store(c, t);
+  }
+}
+
+// The launches of that fold over rows [0, rows): one level, or for groups > 0 two - rows [g*rpg, (g+1)*rpg) into tmp[g][:]
+// (rpg = ceil(rows / groups)), then those ng rows.  The level count changes the rounding: it stays each caller's choice.
+// level(grid, in, rows, rpg, tmp) launches one level of the caller's fold kernel, into tmp if that is not NULL.
+template <typename Level>
+static inline void fold_levels(const float *in, float *tmp, int64_t rows, int64_t cols, int64_t groups, Level level) {
+  const unsigned gx = (unsigned)ceil_div64(cols, 64);
+  if (groups > 0) {
+    const int64_t rpg = ceil_div64(rows, groups), ng = ceil_div64(rows, rpg);
+    level(dim3(gx, (unsigned)ng), in, rows, rpg, tmp);
+    level(dim3(gx), (const float *)tmp, ng, ng, (float *)nullptr);
+  } else {
+    level(dim3(gx), in, rows, rows, (float *)nullptr);
+  }
+}
+
 // largest power-of-two byte width (<=16) that divides every value in the list
 static inline int common_align(std::initializer_list<uint64_t> vals) {
   uint64_t o = 0;

@@ -169,27 +169,8 @@ __device__ __forceinline__ float chunk_carry(const float2 *__restrict__ agg, con
 // cols/64 work-groups - 3 at Dn = 176, 15.6 us for 1.4 MB at the bench shape, a tenth of the backward.
 __global__ void __launch_bounds__(1024)
 colsum_kernel(const float *__restrict__ in, float *__restrict__ out, int64_t rows, int64_t cols, int64_t rpg) {
-  __shared__ float part[16][TC];
-  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  const int64_t c = (int64_t)blockIdx.x * TC + lane;
-  const int64_t r0 = (int64_t)blockIdx.y * rpg, r1 = min(r0 + rpg, rows);
-  float s = 0.f;
-  if (c < cols) {
-    int64_t r = r0 + seg;
-    for (; r + 48 < r1; r += 64) {
-      float a0 = in[r * cols + c], a1 = in[(r + 16) * cols + c], a2 = in[(r + 32) * cols + c], a3 = in[(r + 48) * cols + c];
-      s += (a0 + a1) + (a2 + a3);
-    }
-    for (; r < r1; r += 16) s += in[r * cols + c];
-  }
-  part[seg][lane] = s;
-  __syncthreads();
-  if (seg == 0 && c < cols) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += part[i][lane];
-    out[(int64_t)blockIdx.y * cols + c] = t;
-  }
+  const int64_t r0 = (int64_t)blockIdx.y * rpg;
+  colsum_block(in, r0, min(r0 + rpg, rows), cols, [&](int64_t c, float t) { out[(int64_t)blockIdx.y * cols + c] = t; });
 }
 
 int ilog2_exact(int64_t n) {

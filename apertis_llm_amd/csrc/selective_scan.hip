@@ -357,15 +357,11 @@ int launch_bwd(const float *dlt, const float *A_log, const void *Bt, int64_t bt_
                      (const TIN *)Bt, bt_rs, (const TIN *)C, c_rs, (const TY *)dy, dy_rs, h_in,
                      (const float2 *)agg, (TIN *)dBt, dbt_rs, (TIN *)dC, dc_rs, d_dlt, dA_part, d);
   const int64_t rows = d.B * d.nchunks;
-  const unsigned ctiles = (unsigned)ceil_div64(d.Dn, TC);
-  if (rows <= 128) {
-    hipLaunchKernelGGL(colsum_kernel, dim3(ctiles), dim3(1024), 0, st, dA_part, dA_log, rows, d.Dn, rows);
-  } else {
-    const int64_t groups = std::min<int64_t>(64, ceil_div64(rows, 64)), rpg = ceil_div64(rows, groups);
-    const int64_t ng = ceil_div64(rows, rpg);   // <= groups <= rows: fits the head of mu_in
-    hipLaunchKernelGGL(colsum_kernel, dim3(ctiles, (unsigned)ng), dim3(1024), 0, st, dA_part, mu_in, rows, d.Dn, rpg);
-    hipLaunchKernelGGL(colsum_kernel, dim3(ctiles), dim3(1024), 0, st, mu_in, dA_log, ng, d.Dn, ng);
-  }
+  // (two levels above 128 rows: their ng <= 64 group sums fit the head of mu_in)
+  fold_levels(dA_part, mu_in, rows, d.Dn, rows <= 128 ? 0 : std::min<int64_t>(64, ceil_div64(rows, 64)),
+              [&](dim3 grid, const float *in, int64_t n, int64_t rpg, float *fold) {
+                hipLaunchKernelGGL(colsum_kernel, grid, dim3(1024), 0, st, in, fold ? fold : dA_log, n, d.Dn, rpg);
+              });
   return apertis_check_launch();
 }
 

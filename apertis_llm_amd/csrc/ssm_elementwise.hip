@@ -583,26 +583,7 @@ dwconv_silu_bwd_kn(const T *__restrict__ x, int64_t x_rs, const float *__restric
 // out[c] = sum_r in[r][c], fixed order (16 row groups, four independent loads in flight)
 __global__ void __launch_bounds__(1024)
 colsum_rows_k(const float *__restrict__ in, float *__restrict__ out, int64_t rows, int64_t cols) {
-  __shared__ float part[16][64];
-  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  const int64_t c = (int64_t)blockIdx.x * 64 + lane;
-  float s = 0.f;
-  if (c < cols) {
-    int64_t r = seg;
-    for (; r + 48 < rows; r += 64) {
-      float a0 = in[r * cols + c], a1 = in[(r + 16) * cols + c], a2 = in[(r + 32) * cols + c], a3 = in[(r + 48) * cols + c];
-      s += (a0 + a1) + (a2 + a3);
-    }
-    for (; r < rows; r += 16) s += in[r * cols + c];
-  }
-  part[seg][lane] = s;
-  __syncthreads();
-  if (seg == 0 && c < cols) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += part[i][lane];
-    out[c] = t;
-  }
+  colsum_block(in, 0, rows, cols, [&](int64_t c, float t) { out[c] = t; });
 }
 
 // ---------------------------------------------------------------- residual + dropout
@@ -823,7 +804,7 @@ extern "C" int apertis_ssm_gate_bwd(const void *dout, int64_t dout_rs, const voi
   Geo g = make_geo(Dn);
   size_t lds = (size_t)g.RP * std::min(g.CPR, 256) * sizeof(float4);
   dim3 grid(nblk), block(256);
-  GATE_TYPES(dtype_y, dtype_io, hipLaunchKernelGGL((ssm_gate_bwd_k<TY, TIO>), grid, block, lds, st, (const TIO *)dout,
+  GATE_TYPES(dtype_y, dtype_io, launch_lds(ssm_gate_bwd_k<TY, TIO>, grid, block, lds, st, (const TIO *)dout,
                                                    dout_rs, (const TY *)y, y_rs, (const TIO *)xc, xc_rs, (const TIO *)z,
                                                    z_rs, D, (TY *)dy, dy_rs, (TIO *)dxc, dxc_rs, (TIO *)dz, dz_rs, dD_part,
                                                    T, (int)Dn));
@@ -862,12 +843,8 @@ extern "C" int apertis_dwconv_silu_fwd(const void *x, int64_t x_rs, const float 
     const int64_t epc = dtype_io == APERTIS_BF16 ? 8 : 4;
     const int PCS = (int)(Dn / epc), RG = 256 / PCS, nchunks = (int)ceil_div64(L, CONV_TILE_T);
     const size_t lds = (size_t)conv_tile_lds(Dn, k, dtype_io);
-    CONV_DISPATCH(k, dtype_io, {
-      auto kf = dwconv_silu_fwd_tile_k<T, KW>;
-      if (lds > 48 * 1024) hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kf, dim3((unsigned)(B * nchunks)), dim3(256), lds, st, (const T *)x, x_rs, w, bias, (T *)out, out_rs, L,
-                         PCS, RG, nchunks);
-    });
+    CONV_DISPATCH(k, dtype_io, launch_lds(dwconv_silu_fwd_tile_k<T, KW>, dim3((unsigned)(B * nchunks)), dim3(256), lds, st,
+                                          (const T *)x, x_rs, w, bias, (T *)out, out_rs, L, PCS, RG, nchunks));
     return apertis_check_launch();
   }
   dim3 grid(conv_blocks(B, L, Dn)), block(256);
@@ -895,14 +872,10 @@ extern "C" int apertis_dwconv_silu_bwd2(const void *x, int64_t x_rs, const float
     size_t lds = (size_t)g.RP * std::min(g.CPR, 256) * 4 * (k + 1) * sizeof(float);
     dim3 grid(nblk), block(256);
     if (k > 4) {  // (up to 68 KiB at k = 16)
-      CONV_TYPES(dtype_io, {
-        auto kf = dwconv_silu_bwd_kn<T>;
-        if (lds > 48 * 1024) hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kf, grid, block, lds, st, (const T *)x, x_rs, w, bias, (const T *)dout, dout_rs, (const T *)dout2,
-                           dout2_rs, (T *)dx, dx_rs, dw_part, db_part, B, L, (int)Dn, (int)k);
-      });
+      CONV_TYPES(dtype_io, launch_lds(dwconv_silu_bwd_kn<T>, grid, block, lds, st, (const T *)x, x_rs, w, bias, (const T *)dout,
+                                      dout_rs, (const T *)dout2, dout2_rs, (T *)dx, dx_rs, dw_part, db_part, B, L, (int)Dn, (int)k));
     } else {
-      CONV_DISPATCH(k, dtype_io, hipLaunchKernelGGL((dwconv_silu_bwd_k<T, KW>), grid, block, lds, st, (const T *)x, x_rs, w,
+      CONV_DISPATCH(k, dtype_io, launch_lds(dwconv_silu_bwd_k<T, KW>, grid, block, lds, st, (const T *)x, x_rs, w,
                                                     bias, (const T *)dout, dout_rs, (const T *)dout2, dout2_rs, (T *)dx, dx_rs,
                                                     dw_part, db_part, B, L, (int)Dn));
     }

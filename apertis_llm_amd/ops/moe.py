@@ -183,7 +183,7 @@ def moe_enter_small_supported(blk, res, E, K):
     """Shapes apertis_moe_enter_small takes: <= 16 rows of an fp32 residual stream under no_grad (the decode step)."""
     S = res.numel() // res.shape[-1]
     H = res.shape[-1]
-    # the kernel's own LDS bound (csrc/moe_routing.hip, apertis_moe_enter_small: the boundary / router / expert affine vectors
+    # the kernel's own LDS bound (csrc/layernorm.hip, apertis_moe_enter_small: the boundary / router / expert affine vectors
     # in fp32 plus the S block rows in their own dtype, plus 4 KiB for its static tables, <= 160 KiB): a shape past it must
     # take the general path HERE - by the time the launch declined it, _decode_prepass has already advanced every layer's SSM state
     lds = (3 * E + 4) * H * 4 + S * H * blk.element_size() + 4096

@@ -35,9 +35,9 @@ OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -2
 NAN = float("nan")
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# mirror of the dispatch in csrc/moe_routing.hip (check_H, DISPATCH_IT, DISPATCH_2T, ln_part_rows / ln_two_level, the
-# backward launches' dynamic LDS) and csrc/ssm_elementwise.hip (apertis_dropout_add_fwd's grid cap): a change there must be
-# made here too, and then test_case_tables_cover_every_dispatch_path says whether the cases still reach every path
+# mirror of the dispatch in csrc/layernorm.hip and csrc/row_common.h (check_H, DISPATCH_IT, DISPATCH_2T, ln_part_rows /
+# ln_two_level, the backward launches' dynamic LDS) and csrc/ssm_elementwise.hip (apertis_dropout_add_fwd's grid cap): a change
+# there must be made here too, and then test_case_tables_cover_every_dispatch_path says whether the cases still reach every path
 IT_BUCKETS = (1, 2, 3, 4, 6, 8, 12, 16)
 H_MAX = 4096
 LN_ROWS_PER_BLOCK = 4 * 8           # four waves x APERTIS_LN_RPW (8) rows
