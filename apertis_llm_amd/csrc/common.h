@@ -84,13 +84,19 @@ static inline int common_align(std::initializer_list<uint64_t> vals) {
   return a;
 }
 
+// the 32-bit avalanche (murmur3 finaliser) behind every counter hash of the library: dropout masks, the sampling draw
+__host__ __device__ __forceinline__ uint32_t hash_avalanche32(uint32_t h) {
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h;
+}
+
 // counter-based keep mask: 16 random bits per element from a 32-bit avalanche of
 // (element pair index, seed); the backward regenerates it from the same (seed,row,col)
 __device__ __forceinline__ bool drop_keep(uint64_t seed, int64_t row, int64_t col, int64_t ncols, uint32_t thresh16) {
   uint64_t lin = (uint64_t)row * (uint64_t)ncols + (uint64_t)col;
   uint32_t h = (uint32_t)(lin >> 1) ^ (uint32_t)seed;
   h += (uint32_t)(lin >> 33) * 0x9E3779B9u + (uint32_t)(seed >> 32);
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  h = hash_avalanche32(h);
   uint32_t r16 = (lin & 1) ? (h >> 16) : (h & 0xffffu);
   return r16 >= thresh16;
 }
@@ -107,8 +113,7 @@ __device__ __forceinline__ uint32_t drop_hash_pair(uint64_t seed, uint64_t pair)
     asm volatile("" : "+v"(hi));
     h += hi * 0x9E3779B9u;
   }
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
+  return hash_avalanche32(h);
 }
 __device__ __forceinline__ void drop_keep4(uint64_t seed, uint64_t lin0, uint32_t thresh16, bool (&keep)[4]) {
   const uint32_t h0 = drop_hash_pair(seed, lin0 >> 1), h1 = drop_hash_pair(seed, (lin0 >> 1) + 1);

@@ -1398,6 +1398,10 @@ class ApertisForCausalLM(nn.Module):
             pos = torch.cat([torch.arange(n_img, device=input_ids.device).unsqueeze(0).expand(B, -1), pos + n_img], dim=1)
         tokens, past = input_ids, None
         alive = torch.ones(B, dtype=torch.long, device=input_ids.device)
+        # sampling or a repetition penalty on the GPU: one kernel per step selects the token (ops.sample_next); the stock block
+        # below stays for CPU tensors, vocabularies the kernel does not take and SAMPLE_FUSED = False
+        fused = ops.SAMPLE_FUSED and input_ids.is_cuda and (do_sample or repetition_penalty != 1.0)
+        sampler = None
         for _ in range(max_new_tokens):
             inp = self.prepare_inputs_for_generation(tokens if past is None else tokens[:, -1:], past_key_values=past,
                                                      attention_mask=mask,
@@ -1407,8 +1411,28 @@ class ApertisForCausalLM(nn.Module):
             out = self(input_ids=inp["input_ids"], attention_mask=inp["attention_mask"],
                        position_ids=inp["position_ids"], past_key_values=inp["past_key_values"],
                        pixel_values=inp.get("pixel_values"), use_cache=inp["use_cache"])
-            nxt_logits = out[1][:, -1, :].float()
             past = out[4] if use_cache else None
+            if fused and sampler is None:
+                fused = ops.sample_supported(out[1][:, -1, :])
+                if fused:
+                    sampler = ops.Sampler(out[1][:, -1, :], tokens, do_sample=do_sample, temperature=temperature, top_k=top_k,
+                                          top_p=top_p, repetition_penalty=repetition_penalty, eos=eos, pad=pad)
+            if sampler is not None:
+                nxt, new_alive = sampler.step(out[1][:, -1, :], alive, tokens.shape[1] - prompt_len)
+                tokens = torch.cat([tokens, nxt.unsqueeze(-1)], dim=-1)
+                mask = torch.cat([mask, alive.unsqueeze(-1).to(mask.dtype)], dim=1)
+                alive = new_alive
+                any_alive, code = torch.cat((alive.max().reshape(1), sampler.err.to(alive.dtype))).tolist()
+                sampler.check(code)
+                if any_alive == 0 and tokens.shape[1] - prompt_len >= min_new_tokens:
+                    break
+                left = max_new_tokens - (tokens.shape[1] - prompt_len)
+                if (past is not None and left >= DECODE_GRAPH_MIN_STEPS
+                        and self._decode_graph_ok(tokens, do_sample, repetition_penalty, sampler)):
+                    return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad,
+                                                     sampler=sampler)
+                continue
+            nxt_logits = out[1][:, -1, :].float()
             if repetition_penalty != 1.0:
                 for b in range(B):
                     if alive[b]:
@@ -1444,17 +1468,22 @@ class ApertisForCausalLM(nn.Module):
                 return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad)
         return tokens
 
-    def _decode_graph_ok(self, tokens, do_sample, repetition_penalty):
+    def _decode_graph_ok(self, tokens, do_sample, repetition_penalty, sampler=None):
         cfg = self.config
-        return (DECODE_GRAPH and tokens.is_cuda and not do_sample and repetition_penalty == 1.0 and not torch.is_grad_enabled()
-                and cfg.attention_type != "standard_mha" and cfg.position_embedding_type != "absolute" and not self.training)
+        # (sampling and the penalty replay too when the fused sampler selects the tokens: its kernel reads the step counter
+        #  and the occurrence table from device buffers)
+        return (DECODE_GRAPH and tokens.is_cuda and (sampler is not None or (not do_sample and repetition_penalty == 1.0))
+                and not torch.is_grad_enabled() and cfg.attention_type != "standard_mha"
+                and cfg.position_embedding_type != "absolute" and not self.training)
 
-    def _generate_graph_tail(self, tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad):
+    def _generate_graph_tail(self, tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, sampler=None):
         """Greedy decoding of `left` more tokens through a captured HIP graph of the single-token step (reference
         core.py:1578-1644: the same forward through the cache, argmax, eos / pad bookkeeping - attention mask and position ids
         do not enter an SSM model's step).  An eager token step is ~2 600 small launches, 18 ms of mostly host time at 44
         layers; the replay is 10 ms (tools/decode_graph_try.py).  Token, cache, alive flags, the step counter and the outputs
-        live in static buffers that the graph updates in place; the host looks at the alive flags every 16 steps only."""
+        live in static buffers that the graph updates in place; the host looks at the alive flags every 16 steps only.
+        With a `sampler` (ops.Sampler: sampling or a repetition penalty) its kernel replaces the argmax and the pad / eos
+        updates; its occurrence table and error word are static buffers too, and its draw counter is the step index."""
         B, dev = tokens.shape[0], tokens.device
         s_tok = tokens[:, -1:].clone()
         # (contiguous copies: the prefill hands the conv window over as a transposed view, and a cache that is not contiguous
@@ -1472,38 +1501,59 @@ class ApertisForCausalLM(nn.Module):
         s_out = torch.full((B, left), pad, dtype=tokens.dtype, device=dev)
         s_any = torch.ones(left, dtype=alive.dtype, device=dev)          # max over the batch of `alive` after each step
 
-        def body():
-            out = self(input_ids=s_tok, past_key_values=s_past, use_cache=True)
-            nxt = torch.argmax(out[1][:, -1, :].float(), dim=-1)
-            nxt = nxt * s_alive + pad * (1 - s_alive)
-            s_out.scatter_(1, s_idx.expand(B, 1), nxt.unsqueeze(1).to(s_out.dtype))
-            al = s_alive
-            for e_ in eos:
-                if e_ is not None:
-                    al = al.masked_fill((nxt == e_) & (al == 1), 0)
-            s_alive.copy_(al)
-            s_any.scatter_(0, s_idx, al.max().reshape(1))
-            s_idx.add_(1)
-            s_tok.copy_(nxt.unsqueeze(1))
+        def copy_back(out):
             for (sc, ss), (nc, ns) in zip(s_past, out[4]):
                 if nc.data_ptr() != sc.data_ptr():     # (both updated in place by the step: _inplace_cache)
                     sc.copy_(nc)
                 if ns.data_ptr() != ss.data_ptr():
                     ss.copy_(ns)
 
+        if sampler is None:
+            def body():
+                out = self(input_ids=s_tok, past_key_values=s_past, use_cache=True)
+                nxt = torch.argmax(out[1][:, -1, :].float(), dim=-1)
+                nxt = nxt * s_alive + pad * (1 - s_alive)
+                s_out.scatter_(1, s_idx.expand(B, 1), nxt.unsqueeze(1).to(s_out.dtype))
+                al = s_alive
+                for e_ in eos:
+                    if e_ is not None:
+                        al = al.masked_fill((nxt == e_) & (al == 1), 0)
+                s_alive.copy_(al)
+                s_any.scatter_(0, s_idx, al.max().reshape(1))
+                s_idx.add_(1)
+                s_tok.copy_(nxt.unsqueeze(1))
+                copy_back(out)
+            extra = ()
+        else:
+            s_nxt = torch.empty(B, dtype=torch.long, device=dev)
+            off = tokens.shape[1] - prompt_len                  # (steps already decoded: the draw counter goes on from there)
+
+            def body():
+                out = self(input_ids=s_tok, past_key_values=s_past, use_cache=True)
+                sampler.step(out[1][:, -1, :], s_alive, off, step=s_idx, alive_out=s_alive, out=s_nxt)
+                s_out.scatter_(1, s_idx.expand(B, 1), s_nxt.unsqueeze(1).to(s_out.dtype))
+                s_any.scatter_(0, s_idx, s_alive.max().reshape(1))
+                s_idx.add_(1)
+                s_tok.copy_(s_nxt.unsqueeze(1))
+                copy_back(out)
+            extra = tuple(t for t in (sampler.counts, sampler.err) if t is not None)
         ssm_blocks = [m for m in self.modules() if isinstance(m, SelectiveLinearAttention)]
         for m in ssm_blocks:
             m._inplace_cache = True
         try:
-            return self._generate_graph_run(body, tokens, s_tok, s_past, s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens, pad)
+            return self._generate_graph_run(body, tokens, s_tok, s_past, s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens, pad,
+                                            extra=extra, sampler=sampler)
         finally:
             for m in ssm_blocks:
                 m._inplace_cache = False
 
-    def _generate_graph_run(self, body, tokens, s_tok, s_past, s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens, pad):
+    def _generate_graph_run(self, body, tokens, s_tok, s_past, s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens, pad,
+                            extra=(), sampler=None):
         dev = tokens.device
         # warm-up on a side stream (lazy bindings, prepared-weight cache, allocator), then restore the state it advanced
+        # (`extra`: further buffers the body updates in place - the sampler's occurrence table and error word)
         keep = (s_tok.clone(), [(c.clone(), st.clone()) for (c, st) in s_past], s_alive.clone())
+        keep_extra = [t.clone() for t in extra]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -1517,6 +1567,8 @@ class ApertisForCausalLM(nn.Module):
                 sc.copy_(c)
                 ss.copy_(st)
             s_alive.copy_(keep[2])
+            for t, k in zip(extra, keep_extra):
+                t.copy_(k)
             s_idx.zero_()
             s_out.fill_(pad)
             s_any.fill_(1)
@@ -1531,6 +1583,8 @@ class ApertisForCausalLM(nn.Module):
             graph.replay()
             if (i + 1) % 16 == 0 or i + 1 == left:
                 flags = s_any[:i + 1].tolist()                         # the only host sync: every 16 steps
+                if sampler is not None:
+                    sampler.check()
                 stop = next((j for j, a in enumerate(flags)
                              if a == 0 and tokens.shape[1] - prompt_len + j + 1 >= min_new_tokens), None)
                 if stop is not None:

@@ -14,6 +14,7 @@ One module per subsystem (round 6: the 2 500-line ops.py split up):
     moe      gate, plan, gather-LN, combine, small-batch entrance, expert MLP
     loss     cross-entropy, fused LM head + cross-entropy
     attention  standard_mha: RoPE, causal flash attention
+    sample   generate()'s next-token selection (penalty, temperature, top-k, top-p, draw) in one launch
 `from apertis_llm_amd import ops; ops.<name>` reaches every name of every module, private helpers included (tests and tools use
 them).  The module-level SWITCHES (SCAN_LOOKBACK, TRAIN_PREP, GEMM_DYNAMIC_QUEUE, ...) live in the module whose code reads them;
 `ops.SWITCH` reads and `ops.SWITCH = v` writes that module's variable (the package forwards both), so a test that flips a switch
@@ -22,9 +23,9 @@ on `ops` still reaches the code that looks at it.
 import sys as _sys
 import types as _types
 
-from . import _base, prep, gemm, norm, ssm, scan, decode, moe, loss, attention
+from . import _base, prep, gemm, norm, ssm, scan, decode, moe, loss, attention, sample
 
-_MODULES = (_base, prep, gemm, norm, ssm, scan, decode, moe, loss, attention)
+_MODULES = (_base, prep, gemm, norm, ssm, scan, decode, moe, loss, attention, sample)
 # switches and counters that are REBOUND at run time (by tests, tools, parallel.py or the code itself): owner module per name
 _FORWARDED = {
     "SCAN_SINGLE_PASS": scan, "SCAN_LEAN": scan, "SCAN_LEAN_BWD": scan, "SCAN_LOOKBACK": scan, "SCAN_DT_FUSED": scan,
@@ -36,6 +37,7 @@ _FORWARDED = {
     "TRAIN_PREP": prep, "WEIGHT_EPOCH": prep, "_ACTIVE_TRAIN_PREP": prep, "_prep_scope_depth": prep,
     "_TIMER": _base,
     "ATTN_FUSED": attention,
+    "SAMPLE_FUSED": sample, "SAMPLE_UNIFORMS": sample,
 }
 for _m in _MODULES:
     for _k, _v in vars(_m).items():

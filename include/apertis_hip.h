@@ -49,11 +49,12 @@ extern "C" {
  * kernel; measured 15 % SLOWER at the bench shape (profiles/r6_probe_nt2i_vs_nt4r.log), so no caller sets it by default. */
 #define APERTIS_ACT_INTERLEAVED 0x400
 
-/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.8 - apertis_rope_qk_fwd / _bwd,
+/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.9 - apertis_token_counts,
+ * apertis_sample_next: generate()'s penalty / temperature / top-k / top-p / draw in one launch; 4.8 - apertis_rope_qk_fwd / _bwd,
  * apertis_attention_fwd / _bwd, apertis_attention_bwd_workspace_bytes: standard_mha; round 6: 4.7 - apertis_cross_entropy_fwd_bwd, apertis_layernorm_combine_bwd; round 5: 4.5 - apertis_scan_lookback_*, apertis_tiny_linear_bwd_pad; round 4: 4.4 - lean scan
  * entry points, apertis_scan_lean_fwd_dt, apertis_grouped_gemm_tn_dense_variant, apertis_weight_prep, apertis_ssm_decode_state_dt).  A host binding should
  * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does). */
-#define APERTIS_ABI_VERSION ((4 << 16) | 8)
+#define APERTIS_ABI_VERSION ((4 << 16) | 9)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
 const char *apertis_arch(void);
@@ -755,6 +756,47 @@ int apertis_attention_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_
                           const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
                           const int64_t *key_valid, float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B,
                           int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * generate()'s next-token selection (core.py:1605-1633), one launch per token step, one 1024-thread work-group per row.
+ *
+ * apertis_token_counts: counts[b, t] += 1 for every token t = tokens[b, i], i < L (int64, row stride tok_rs) - the occurrence
+ * table the repetition penalty reads.  The caller zeroes counts (int32 [B, V]) first.  Ids >= V are skipped (the reference
+ * skips them); ids in [-V, 0) count for id + V (Python indexing wraps them); an id below -V sets bit 4 of *err (the reference's
+ * indexing raises there).  V <= APERTIS_SAMPLE_MAX_VOCAB, B <= 65535, else APERTIS_ERR_UNSUPPORTED.
+ *
+ * apertis_sample_next, for every row b with alive_in[b] != 0, on x = logits[b, :V] (fp32 or bf16, row stride logits_rs),
+ * in fp32 and in this order:
+ *   1. counts != NULL and penalty != 1: x[v] / penalty, counts[b, v] times in sequence (true divisions)
+ *   2. do_sample and temperature != 1: x / temperature (true division; the caller passes max(temperature, 1e-6))
+ *   3. do_sample and 0 < top_k < V: keep x >= the k-th largest value (duplicates counted; ties at it stay)
+ *   4. do_sample and top_p < 1: sort the kept values descending (equal values: lowest index first), keep sorted positions up to
+ *      and including the first whose inclusive cumulative softmax probability exceeds top_p (the first is always kept)
+ *   5. do_sample: the first index, in vocabulary order, whose inclusive prefix of kept weights exp(x - max) exceeds u * Z (Z
+ *      their total; weights are summed as fixed-point integers, exp * 2^44 rounded, so every sum is exact and order-free);
+ *      u = uniforms[b * u_rs + step] when uniforms != NULL (fp64 in [0, 1); step outside [0, u_cols) sets bit 2 of *err and
+ *      reads u = 0), else the 32 bits of a counter hash of (seed, b, step) times 2^-32.  Greedy: the argmax, NaN above every
+ *      number, the lowest index among equal maxima (torch.argmax).
+ *   6. next[b] = that token; alive_out[b] = 0 when it is one of eos[0..n_eos), else alive_in[b]; counts[b, next] += 1 when
+ *      counts != NULL.
+ * Rows with alive_in[b] == 0: next[b] = pad, alive_out[b] = 0, nothing else.  alive_out may alias alive_in.
+ *   step       : int64 device scalar, read only (step = *step + step_off; NULL reads 0) - a replayed graph draws fresh numbers
+ *   probs_out  : fp32 [B, V] or NULL: with do_sample, the final distribution (zero where removed and for finished rows)
+ *   x_out      : fp32 [B, V] or NULL: the row after steps 1-2 (penalty, temperature), for rows with alive_in[b] != 0
+ *   u_out      : fp64 [B] or NULL: the u each row used
+ *   err        : int32 device word, OR-ed with 1 when a sampled row has a NaN or +inf value or no finite one (torch.multinomial
+ *                raises there; the row then gets token 0), 2 as above.  The caller reads it at a sync it already has.
+ * top_k > V or a null pointer: APERTIS_ERR_ARG before any launch; V > APERTIS_SAMPLE_MAX_VOCAB: APERTIS_ERR_UNSUPPORTED.
+ */
+#define APERTIS_SAMPLE_MAX_VOCAB 262144
+#define APERTIS_SAMPLE_MAX_ROWS 65535 /* apertis_token_counts' limit on B */
+int apertis_token_counts(const int64_t *tokens, int64_t tok_rs, int64_t B, int64_t L, int64_t V, int32_t *counts, int32_t *err,
+                         void *stream);
+int apertis_sample_next(const void *logits, int64_t logits_rs, int dtype, int64_t B, int64_t V, int32_t *counts, float penalty,
+                        int do_sample, float temperature, int64_t top_k, float top_p, uint64_t seed, const int64_t *step,
+                        int64_t step_off, const int64_t *alive_in, int64_t *alive_out, const int64_t *eos, int64_t n_eos,
+                        int64_t pad, int64_t *next, const double *uniforms, int64_t u_rs, int64_t u_cols, float *probs_out,
+                        float *x_out, double *u_out, int32_t *err, void *stream);
 
 #ifdef __cplusplus
 }

@@ -604,8 +604,170 @@ def gen_generate_long(core):
         raise SystemExit(f"{name}: no seed in 16 fits the eos rule with a clear greedy gap")
 
 
+def _penalised(raw, hist, pen, temp, top_k):
+    """The reference's steps 1-3 on one row (fp32 CPU torch, core.py:1605-1617): (logits after penalty, temperature and top-k,
+    the gap between the k-th and the (k+1)-th largest value)."""
+    x = raw.clone().float()
+    if pen != 1.0:
+        for t in hist:
+            if t < x.shape[-1]:
+                x[t] /= pen
+    if temp != 1.0:
+        x = x / temp
+    vals = torch.sort(x, descending=True).values
+    gap = float(vals[top_k - 1] - vals[top_k]) if 0 < top_k < x.numel() else math.inf
+    if top_k > 0:
+        x = x.masked_fill(x < vals[top_k - 1], float("-inf"))
+    return x, gap
+
+
+def _topp_margin(x, top_p):
+    """The smallest distance of an fp64 sorted cumulative probability from top_p (every cut clear of rounding)."""
+    v = x.double().numpy()
+    s = np.sort(v[np.isfinite(v)])[::-1]
+    p = np.exp(s - s[0])
+    cum = np.cumsum(p / p.sum())
+    return float(np.abs(cum - top_p).min()) if top_p < 1.0 else math.inf
+
+
+def _sampled_run(model, prompt, new, sp, eos, seed):
+    """The reference's generate() with torch.multinomial replaced, for this call only, by an fp64 inverse-CDF pick in vocabulary
+    order at a recorded uniform u[b, step]: one seeded numpy stream per row, a draw within 1e-3 of a CDF step is drawn again.
+    Returns (tokens, raw last-position logits [B, calls, V], probs handed to multinomial [B, steps, V], u [B, steps])."""
+    B = prompt.shape[0]
+    steps, probs_rec, us = [], [], []
+    rngs = [np.random.default_rng([seed, b]) for b in range(B)]
+
+    def pick(probs, num_samples=1, **kw):
+        P = probs.detach().double().numpy()
+        out, urow = [], []
+        for b in range(B):
+            c = np.cumsum(P[b])
+            c /= c[-1]
+            edges = np.concatenate([[0.0], c[P[b] > 0]])
+            while True:
+                u = float(rngs[b].random())
+                if np.abs(edges - u).min() >= 1e-3:
+                    break
+            out.append(min(int(np.searchsorted(c, u, side="right")), len(c) - 1))
+            urow.append(u)
+        probs_rec.append(probs.detach().clone().float())
+        us.append(urow)
+        return torch.tensor(out, dtype=torch.long).unsqueeze(1)
+    fwd = model.forward
+
+    def spy(*a, **k):
+        out = fwd(*a, **k)
+        steps.append(out[1][:, -1, :].detach().clone())
+        return out
+    orig = torch.multinomial
+    torch.multinomial = pick
+    model.forward = spy
+    try:
+        with torch.no_grad():
+            toks = model.generate(input_ids=prompt, max_new_tokens=new, use_cache=True, eos_token_id=eos, pad_token_id=0, **sp)
+    finally:
+        torch.multinomial = orig
+        model.forward = fwd
+    probs = torch.stack(probs_rec, dim=1) if probs_rec else None
+    uni = torch.tensor(us, dtype=torch.float64).T.contiguous() if us else None
+    return toks, torch.stack(steps, dim=1), probs, uni
+
+
+def _pick_eos(new):
+    """A token that sequence b emits for the first time at a step in [14, 40) and the other sequence never emits."""
+    for b in (0, 1):
+        mine, other = new[b].tolist(), set(new[1 - b].tolist())
+        for s_ in range(14, 40):
+            if mine[s_] not in mine[:s_] and mine[s_] not in other and mine[s_] != 0:
+                return mine[s_], (b, s_)
+    return None, None
+
+
+def gen_generate_sampled(core):
+    """N1 with sampling (issue: sampled generate() on a HIP kernel): the reference's generate() at the *_long shape (V 96,
+    B 2, 56 new tokens, one sequence reaching eos mid-way), sampled with temperature 0.7, top_k 20, top_p 0.9 and
+    repetition_penalty 1.3, multinomial replaced by an fp64 inverse-CDF pick at recorded uniforms; for the SSM models also
+    greedy with repetition_penalty 1.3 (keys pen_*).  Seeds are bumped until no live decision sits near a rounding boundary:
+    every u at least 1e-3 from a CDF step (by construction), every top-p cumulative probability at least 1e-3 from top_p,
+    every top-k gap (k-th minus (k+1)-th value) above 1e-4 (no 1e-5 change of the logits moves the threshold) and every
+    greedy top-2 gap above 1e-3; the margins are stored."""
+    specs = {"generate_sampled_ssm_dense": dict(attention_type="selective_ssm", use_expert_system=False),
+             "generate_sampled_ssm_moe": dict(attention_type="selective_ssm", use_expert_system=True, num_experts=4,
+                                              experts_per_token=2),
+             "generate_sampled_mha": dict(attention_type="standard_mha", use_expert_system=False)}
+    NEW, PEN = 56, 1.3
+    SP = dict(do_sample=True, temperature=0.7, top_k=20, top_p=0.9, repetition_penalty=PEN)
+    for name, extra in specs.items():
+        mha = extra["attention_type"] == "standard_mha"
+        H, heads = (64, 1) if mha else (32, 2)          # (standard_mha: head dim 64, the product's attention kernels take it)
+        for bump in range(200):
+            torch.manual_seed(zlib.crc32(name.encode()) % 1000 + bump)
+            cfg = core.ApertisConfig(vocab_size=96, hidden_size=H, num_hidden_layers=2, num_attention_heads=heads,
+                                     intermediate_size=2 * H, **extra)
+            model = core.ApertisForCausalLM(cfg).eval()
+            with torch.no_grad():
+                for n_, p in model.named_parameters():
+                    if p.dim() > 1 and "token_embeddings" not in n_:
+                        p.mul_(4.0)
+            prompt = torch.randint(4, 96, (2, 9))
+            seed = 1000 + bump
+            free = _sampled_run(model, prompt, NEW, SP, 10 ** 6, seed)[0]
+            eos, who = _pick_eos(free[:, 9:])
+            if eos is None:
+                continue
+            toks, logits, probs, uni = _sampled_run(model, prompt, NEW, SP, eos, seed)
+            newt = toks[:, 9:]
+            if newt.shape[1] != NEW or (newt[1 - who[0]] == eos).any() or int((newt[who[0]] == eos).nonzero()[0, 0]) != who[1]:
+                continue
+            live = torch.ones_like(newt, dtype=torch.bool)
+            live[who[0], who[1] + 1:] = False
+            kgap, pmar = math.inf, math.inf
+            for s_ in range(NEW):
+                for b in range(2):
+                    if live[b, s_]:
+                        x, g_ = _penalised(logits[b, s_], toks[b, :9 + s_].tolist(), PEN, SP["temperature"], SP["top_k"])
+                        kgap, pmar = min(kgap, g_), min(pmar, _topp_margin(x, SP["top_p"]))
+            if kgap <= 1e-4 or pmar < 1e-3:
+                continue
+            # the sampled decisions are not all the argmax (else the capture would not pin the draw)
+            arg = torch.tensor([[int(torch.argmax(probs[b, s_])) for s_ in range(NEW)] for b in range(2)])
+            n_nonmax = int(((arg != newt) & live).sum())
+            u_mar = min(float(np.abs(np.concatenate([[0.0], np.cumsum(probs[b, s_].double().numpy())]) - float(uni[b, s_])).min())
+                        for b in range(2) for s_ in range(NEW) if live[b, s_])
+            arrs = dict(prompt=prompt, tokens=toks, step_logits=logits, probs=probs, uniforms=uni, eos=eos, eos_seq=who[0],
+                        eos_step=who[1], live=live, temperature=SP["temperature"], top_k=SP["top_k"], top_p=SP["top_p"],
+                        repetition_penalty=PEN, margin_u=u_mar, margin_top_p=pmar, margin_top_k=kgap, seed_u=seed,
+                        config_json=json.dumps(cfg.to_dict()))
+            if not mha:
+                gfree = _sampled_run(model, prompt, NEW, dict(do_sample=False, repetition_penalty=PEN), 10 ** 6, seed)[0]
+                geos, gwho = _pick_eos(gfree[:, 9:])
+                if geos is None:
+                    continue
+                gtoks, glogits, _, _ = _sampled_run(model, prompt, NEW, dict(do_sample=False, repetition_penalty=PEN), geos, seed)
+                gnew = gtoks[:, 9:]
+                if (gnew[1 - gwho[0]] == geos).any() or int((gnew[gwho[0]] == geos).nonzero()[0, 0]) != gwho[1]:
+                    continue
+                glive = torch.ones_like(gnew, dtype=torch.bool)
+                glive[gwho[0], gwho[1] + 1:] = False
+                ggap = min(float(torch.topk(_penalised(glogits[b, s_], gtoks[b, :9 + s_].tolist(), PEN, 1.0, 0)[0], 2).values
+                                 .diff().abs()) for b in range(2) for s_ in range(NEW) if glive[b, s_])
+                if ggap <= 1e-3:
+                    continue
+                arrs.update(pen_tokens=gtoks, pen_step_logits=glogits, pen_eos=geos, pen_eos_seq=gwho[0], pen_eos_step=gwho[1],
+                            pen_live=glive, pen_min_gap=ggap)
+            print(f"  {name} (seed bump {bump}): eos {eos} ends sequence {who[0]} at step {who[1]}, {n_nonmax} live draws not the "
+                  f"argmax, margins u {u_mar:.2e} top-p {pmar:.2e} top-k {kgap:.2e}"
+                  + ("" if mha else f"; greedy + penalty: eos {arrs['pen_eos']} at step {arrs['pen_eos_step']}, gap {arrs['pen_min_gap']:.2e}"))
+            sd = {k: v.detach() for k, v in model.state_dict().items()}
+            npz(name, **arrs, **sd_arrays(sd))
+            break
+        else:
+            raise SystemExit(f"{name}: no seed in 200 fits the eos rule with clear margins")
+
+
 GENERATORS = ["scan", "ssm_layer", "moe", "vision", "models", "dims", "data_formats", "trainer_run", "config1", "generate",
-              "generate_long"]
+              "generate_long", "generate_sampled"]
 
 
 if __name__ == "__main__":
