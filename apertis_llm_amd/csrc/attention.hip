@@ -17,6 +17,7 @@
 // Every product is oriented so that the later product sums over the row index of the earlier one (S^T = K Q^T then
 // O^T += V^T P^T), so no accumulator ever changes lanes.  bf16: P and dS are rounded to bf16 for their products.
 #include "common.h"
+#include "rope_common.h"
 
 namespace {
 
@@ -436,29 +437,14 @@ __global__ __launch_bounds__(256) void rope_qk_k(const T *q, int64_t q_rs, const
   if (t >= total) return;
   const int64_t tok = t / half, j = t - tok * half;
   const int64_t b = tok / L, l = tok - b * L;
-  int64_t ps = pos ? pos[b * pos_bs + l] : l;
-  if (ps < 0) ps += max_pos;                                 // (torch indexing wraps negative positions)
-  float c = NAN, s = NAN;                                    // (the host checked the range: never read outside the table)
-  if (ps >= 0 && ps < max_pos) {
-    c = cs[ps * half + j];
-    s = sn[ps * half + j];
-  }
+  float c, s;                                                // (table lookup and pair arithmetic: rope_common.h)
+  rope_cos_sin(cs, sn, pos ? pos[b * pos_bs + l] : l, max_pos, half, j, c, s);
   const T *src[2] = {q + tok * q_rs, k + tok * k_rs};
   T *dst[2] = {qo + tok * 2 * half, ko + tok * 2 * half};
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const float x0 = to_f32(src[u][2 * j]), x1 = to_f32(src[u][2 * j + 1]);
     float y0, y1;
-    if constexpr (!BWD) {
-      // stock order: (a*cos) - (b*sin), (a*sin) + (b*cos), each product rounded (-ffp-contract=off)
-      const float p0 = x0 * c, p1 = x1 * s, p2 = x0 * s, p3 = x1 * c;
-      y0 = p0 - p1;
-      y1 = p2 + p3;
-    } else {
-      const float p0 = x0 * c, p1 = x1 * s, p2 = x0 * s, p3 = x1 * c;
-      y0 = p0 + p1;
-      y1 = p3 - p2;
-    }
+    rope_rotate_pair<BWD>(to_f32(src[u][2 * j]), to_f32(src[u][2 * j + 1]), c, s, y0, y1);
     dst[u][2 * j] = from_f32<T>(y0);
     dst[u][2 * j + 1] = from_f32<T>(y1);
   }

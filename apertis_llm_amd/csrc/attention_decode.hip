@@ -1,0 +1,280 @@
+// standard_mha single-token decode on gfx950: the KV-cache append (with the RoPE rotation of q and k, rope_common.h) and
+// softmax attention of ONE query row per (sequence, head) over the cached keys (reference core.py:639-700 with a past).
+//
+// Layout: q, out [B, H*D] rows; k_cache, v_cache [B, cap, H*D] token-major with a row and a batch stride, head h in columns
+// [h*D, (h+1)*D) - what the prefill's (k, v) already are: no head transposes.
+//
+// attn_decode_k: the byte-bound part (K and V are read once).  A head row of D elements is 16-byte pieces over LPR = D*es/16
+// lanes (8 for bf16 D 64 ... 32 for fp32 D 128), so a wave reads 64/LPR keys per load instruction, straight from global
+// memory into VGPRs, 4 keys in flight per lane.  Each group of LPR lanes runs its own online softmax (m, l, o[16/es]) in fp32
+// on the VALU: the dot product is a cross-lane sum inside the group, P is never rounded.  The groups of a wave are merged by
+// shuffles, the 4 waves of a work-group through 2 KiB of LDS.  The key range is split over work-groups (grid splits x H x B);
+// with splits > 1 every work-group leaves (m, l, o[D]) in a workspace and attn_decode_merge_k folds them in split order.  No
+// atomics, no waiting between work-groups: the same inputs and split count give the same bits.
+#include "common.h"
+#include "rope_common.h"
+
+namespace {
+
+constexpr int DEC_WAVES = 4;          // waves per work-group
+constexpr int DEC_UNROLL = 4;         // keys in flight per lane group
+constexpr int DEC_MIN_KEYS = 128;     // the heuristic gives a split at least this many keys
+constexpr int DEC_TARGET_WGS = 256;   // ... and stops splitting at one work-group per CU (measured: DESIGN.md section 3)
+
+template <typename T> __device__ __forceinline__ void unpack16(const uint4 &r, float (&f)[16 / sizeof(T)]) {
+  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = __uint_as_float(w[i]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[2 * i] = __uint_as_float(w[i] << 16);
+      f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+  }
+}
+
+// (m1, l1) <- merge with (m2, l2); returns the two rescale factors.  m in log2 units; m = -inf with l = 0 is "nothing yet".
+__device__ __forceinline__ void softmax_merge(float &m, float m2, float &a1, float &a2) {
+  const float mn = fmaxf(m, m2);
+  const float mu = mn == -INFINITY ? 0.f : mn;
+  a1 = exp2f(m - mu);
+  a2 = exp2f(m2 - mu);
+  m = mn;
+}
+
+struct DecArgs {
+  const void *q, *k, *v;
+  const int64_t *key_valid;
+  void *out;
+  float *ws_ml, *ws_o;
+  int64_t q_rs, k_rs, k_bs, v_rs, v_bs, kv_rs, out_rs, Lk;
+  int H, splits;
+  float sl2;                          // scale * log2(e)
+};
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_decode_k(DecArgs a) {
+  constexpr int E = 16 / (int)sizeof(T), LPR = D / E, KPW = APERTIS_WAVE / LPR, STEP = DEC_WAVES * KPW;
+  __shared__ float sm_m[DEC_WAVES], sm_l[DEC_WAVES], sm_o[DEC_WAVES][D];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane / LPR, c = (lane % LPR) * E;
+  const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int64_t j0 = (int64_t)s * a.Lk / a.splits, j1 = (int64_t)(s + 1) * a.Lk / a.splits;
+  float qf[E];
+  unpack16<T>(*reinterpret_cast<const uint4 *>(static_cast<const T *>(a.q) + (int64_t)b * a.q_rs + h * D + c), qf);
+  const T *kp = static_cast<const T *>(a.k) + (int64_t)b * a.k_bs + h * D + c;
+  const T *vp = static_cast<const T *>(a.v) + (int64_t)b * a.v_bs + h * D + c;
+  const int64_t *kv = a.key_valid ? a.key_valid + (int64_t)b * a.kv_rs : nullptr;
+  float m = -INFINITY, l = 0.f, o[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) o[e] = 0.f;
+  for (int64_t base = j0 + w * KPW; base < j1; base += STEP * DEC_UNROLL) {       // (wave-uniform trip count)
+    uint4 kr[DEC_UNROLL], vr[DEC_UNROLL];
+    bool ok[DEC_UNROLL];
+#pragma unroll
+    for (int u = 0; u < DEC_UNROLL; ++u) {
+      const int64_t j = base + g + u * STEP;
+      ok[u] = j < j1;
+      if (kv && ok[u]) ok[u] = kv[j] != 0;
+      kr[u] = vr[u] = make_uint4(0u, 0u, 0u, 0u);
+      if (ok[u]) {                                  // (a masked or out-of-range key row is never read)
+        kr[u] = *reinterpret_cast<const uint4 *>(kp + j * a.k_rs);
+        vr[u] = *reinterpret_cast<const uint4 *>(vp + j * a.v_rs);
+      }
+    }
+    float sc[DEC_UNROLL], tmax = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < DEC_UNROLL; ++u) {
+      float kf[E], d = 0.f;
+      unpack16<T>(kr[u], kf);
+#pragma unroll
+      for (int e = 0; e < E; ++e) d += qf[e] * kf[e];
+#pragma unroll
+      for (int off = LPR / 2; off >= 1; off >>= 1) d += __shfl_xor(d, off);
+      sc[u] = ok[u] ? d * a.sl2 : -INFINITY;
+      tmax = fmaxf(tmax, sc[u]);
+    }
+    float alpha, unused;
+    softmax_merge(m, tmax, alpha, unused);
+    const float mu = m == -INFINITY ? 0.f : m;
+    l *= alpha;
+#pragma unroll
+    for (int e = 0; e < E; ++e) o[e] *= alpha;
+#pragma unroll
+    for (int u = 0; u < DEC_UNROLL; ++u) {
+      const float p = exp2f(sc[u] - mu);            // (exp2(-inf) = 0 for a key that does not count)
+      float vf[E];
+      unpack16<T>(vr[u], vf);
+      l += p;
+#pragma unroll
+      for (int e = 0; e < E; ++e) o[e] += p * vf[e];
+    }
+  }
+  // the lane groups of the wave: a butterfly, after which every group holds the wave's result
+#pragma unroll
+  for (int off = LPR; off < APERTIS_WAVE; off <<= 1) {
+    float a1, a2;
+    softmax_merge(m, __shfl_xor(m, off), a1, a2);
+    l = l * a1 + __shfl_xor(l, off) * a2;
+#pragma unroll
+    for (int e = 0; e < E; ++e) o[e] = o[e] * a1 + __shfl_xor(o[e], off) * a2;
+  }
+  if (g == 0) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) sm_o[w][c + e] = o[e];
+    if (lane == 0) {
+      sm_m[w] = m;
+      sm_l[w] = l;
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t >= D) return;
+  float M = sm_m[0], L = sm_l[0], O = sm_o[0][t];
+#pragma unroll
+  for (int i = 1; i < DEC_WAVES; ++i) {             // wave order: fixed
+    float a1, a2;
+    softmax_merge(M, sm_m[i], a1, a2);
+    L = L * a1 + sm_l[i] * a2;
+    O = O * a1 + sm_o[i][t] * a2;
+  }
+  if (a.splits == 1) {
+    static_cast<T *>(a.out)[(int64_t)b * a.out_rs + h * D + t] = from_f32<T>(L > 0.f ? O / L : 0.f);
+  } else {
+    const int64_t idx = ((int64_t)b * a.H + h) * a.splits + s;
+    a.ws_o[idx * D + t] = O;
+    if (t == 0) {
+      a.ws_ml[2 * idx] = M;
+      a.ws_ml[2 * idx + 1] = L;
+    }
+  }
+}
+
+// out[b, h*D + t] from the splits' partials, in split order; D threads per (b, h)
+template <typename T, int D>
+__global__ __launch_bounds__(D) void attn_decode_merge_k(DecArgs a) {
+  const int t = threadIdx.x, h = blockIdx.x, b = blockIdx.y;
+  const int64_t idx0 = ((int64_t)b * a.H + h) * a.splits;
+  float M = a.ws_ml[2 * idx0], L = a.ws_ml[2 * idx0 + 1], O = a.ws_o[idx0 * D + t];
+  for (int s = 1; s < a.splits; ++s) {
+    float a1, a2;
+    softmax_merge(M, a.ws_ml[2 * (idx0 + s)], a1, a2);
+    L = L * a1 + a.ws_ml[2 * (idx0 + s) + 1] * a2;
+    O = O * a1 + a.ws_o[(idx0 + s) * D + t] * a2;
+  }
+  static_cast<T *>(a.out)[(int64_t)b * a.out_rs + h * D + t] = from_f32<T>(L > 0.f ? O / L : 0.f);
+}
+
+template <typename T, int D> int launch_decode(const DecArgs &a, int64_t B, hipStream_t st) {
+  hipLaunchKernelGGL((attn_decode_k<T, D>), dim3((unsigned)a.splits, (unsigned)a.H, (unsigned)B), dim3(64 * DEC_WAVES), 0, st, a);
+  if (a.splits > 1) hipLaunchKernelGGL((attn_decode_merge_k<T, D>), dim3((unsigned)a.H, (unsigned)B), dim3(D), 0, st, a);
+  return apertis_check_launch();
+}
+
+int64_t decode_splits(int64_t B, int64_t H, int64_t Lk) {
+  const int64_t want = DEC_TARGET_WGS / (B * H), by_len = Lk / DEC_MIN_KEYS;
+  int64_t s = want < by_len ? want : by_len;
+  if (s > APERTIS_ATTN_DECODE_MAX_SPLITS) s = APERTIS_ATTN_DECODE_MAX_SPLITS;
+  return s < 1 ? 1 : s;
+}
+
+// one thread per (sequence, pair j): rotated q pair to q_out, rotated k pair and the v pair into cache row t_cache
+template <typename T>
+__global__ __launch_bounds__(256) void rope_kv_append_k(const T *q, int64_t q_rs, const T *k, int64_t k_rs, const T *v,
+                                                        int64_t v_rs, const float *cs, const float *sn, int64_t max_pos, int64_t t,
+                                                        T *qo, int64_t qo_rs, T *kc, int64_t kc_rs, int64_t kc_bs, T *vc,
+                                                        int64_t vc_rs, int64_t vc_bs, int64_t t_cache, int64_t half, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int64_t b = i / half, j = i - b * half;
+  const T *qs = q + b * q_rs + 2 * j, *ks = k + b * k_rs + 2 * j, *vs = v + b * v_rs + 2 * j;
+  T *qd = qo + b * qo_rs + 2 * j, *kd = kc + b * kc_bs + t_cache * kc_rs + 2 * j, *vd = vc + b * vc_bs + t_cache * vc_rs + 2 * j;
+  if (cs) {
+    float c, s, y0, y1;
+    rope_cos_sin(cs, sn, t, max_pos, half, j, c, s);
+    rope_rotate_pair<false>(to_f32(qs[0]), to_f32(qs[1]), c, s, y0, y1);
+    qd[0] = from_f32<T>(y0);
+    qd[1] = from_f32<T>(y1);
+    rope_rotate_pair<false>(to_f32(ks[0]), to_f32(ks[1]), c, s, y0, y1);
+    kd[0] = from_f32<T>(y0);
+    kd[1] = from_f32<T>(y1);
+  } else {
+    qd[0] = qs[0];
+    qd[1] = qs[1];
+    kd[0] = ks[0];
+    kd[1] = ks[1];
+  }
+  vd[0] = vs[0];
+  vd[1] = vs[1];
+}
+
+}  // namespace
+
+extern "C" int apertis_rope_kv_append(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                      const float *cos_cached, const float *sin_cached, int64_t max_pos, int64_t t, void *q_out,
+                                      int64_t q_out_rs, void *k_cache, int64_t kc_rs, int64_t kc_bs, void *v_cache, int64_t vc_rs,
+                                      int64_t vc_bs, int64_t cap, int64_t t_cache, int64_t B, int64_t W, int dtype, void *stream) {
+  if (!q || !k || !v || !q_out || !k_cache || !v_cache || (cos_cached == nullptr) != (sin_cached == nullptr)) return APERTIS_ERR_ARG;
+  if (B < 0 || W <= 0 || (W & 1) || cap < 1 || (dtype != APERTIS_F32 && dtype != APERTIS_BF16)) return APERTIS_ERR_ARG;
+  if (q_rs < W || k_rs < W || v_rs < W || q_out_rs < W || kc_rs < W || vc_rs < W || kc_bs < cap * kc_rs || vc_bs < cap * vc_rs)
+    return APERTIS_ERR_ARG;
+  if (t_cache < 0 || t_cache >= cap) return APERTIS_ERR_ARG;
+  if (cos_cached && (max_pos <= 0 || t < -max_pos || t >= max_pos)) return APERTIS_ERR_ARG;
+  const int64_t half = W / 2, total = B * half;
+  if (total == 0) return APERTIS_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)ceil_div64(total, 256));
+  if (dtype == APERTIS_F32)
+    hipLaunchKernelGGL((rope_kv_append_k<float>), grid, dim3(256), 0, st, (const float *)q, q_rs, (const float *)k, k_rs,
+                       (const float *)v, v_rs, cos_cached, sin_cached, max_pos, t, (float *)q_out, q_out_rs, (float *)k_cache, kc_rs,
+                       kc_bs, (float *)v_cache, vc_rs, vc_bs, t_cache, half, total);
+  else
+    hipLaunchKernelGGL((rope_kv_append_k<bf16_t>), grid, dim3(256), 0, st, (const bf16_t *)q, q_rs, (const bf16_t *)k, k_rs,
+                       (const bf16_t *)v, v_rs, cos_cached, sin_cached, max_pos, t, (bf16_t *)q_out, q_out_rs, (bf16_t *)k_cache,
+                       kc_rs, kc_bs, (bf16_t *)v_cache, vc_rs, vc_bs, t_cache, half, total);
+  return apertis_check_launch();
+}
+
+extern "C" int64_t apertis_attention_decode_splits(int64_t B, int64_t H, int64_t Lk, int64_t D) {
+  if (B < 1 || H < 1 || Lk < 1 || D < 1) return -1;
+  return decode_splits(B, H, Lk);
+}
+
+extern "C" int64_t apertis_attention_decode_workspace_bytes(int64_t B, int64_t H, int64_t D, int64_t splits) {
+  if (B < 0 || H < 1 || D < 1 || splits < 1 || splits > APERTIS_ATTN_DECODE_MAX_SPLITS) return -1;
+  return splits == 1 ? 0 : B * H * splits * (D + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int apertis_attention_decode(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
+                                        const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid,
+                                        int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lk, int64_t H,
+                                        int64_t D, int64_t splits, int dtype, void *stream) {
+  if (!q || !k_cache || !v_cache || !out) return APERTIS_ERR_ARG;
+  if (B < 0 || H <= 0 || D <= 0 || cap < 1 || Lk < 1 || Lk > cap || (dtype != APERTIS_F32 && dtype != APERTIS_BF16))
+    return APERTIS_ERR_ARG;
+  if ((D != 64 && D != 128) || B > 65535 || H > 65535) return APERTIS_ERR_UNSUPPORTED;
+  const int64_t W = H * D, es = dtype == APERTIS_F32 ? 4 : 2;
+  if (q_rs < W || out_rs < W || k_rs < W || v_rs < W || k_bs < cap * k_rs || v_bs < cap * v_rs) return APERTIS_ERR_ARG;
+  if (key_valid && kv_rs < Lk) return APERTIS_ERR_ARG;
+  if (splits < 0 || splits > Lk || splits > APERTIS_ATTN_DECODE_MAX_SPLITS) return APERTIS_ERR_ARG;
+  // 16-byte pieces of a head row: every row start on a 16-byte boundary
+  const uint64_t bits = (uint64_t)(uintptr_t)q | (uint64_t)(uintptr_t)k_cache | (uint64_t)(uintptr_t)v_cache |
+                        (uint64_t)(q_rs * es) | (uint64_t)(k_rs * es) | (uint64_t)(k_bs * es) | (uint64_t)(v_rs * es) |
+                        (uint64_t)(v_bs * es);
+  if (bits & 15u) return APERTIS_ERR_UNSUPPORTED;
+  if (B == 0) return APERTIS_OK;
+  if (splits == 0) splits = decode_splits(B, H, Lk);
+  if (splits > 1 && !workspace) return APERTIS_ERR_ARG;
+  DecArgs a{};
+  a.q = q; a.k = k_cache; a.v = v_cache; a.key_valid = key_valid; a.out = out;
+  a.ws_ml = workspace;
+  a.ws_o = workspace ? workspace + 2 * B * H * splits : nullptr;
+  a.q_rs = q_rs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.kv_rs = kv_rs; a.out_rs = out_rs; a.Lk = Lk;
+  a.H = (int)H;
+  a.splits = (int)splits;
+  a.sl2 = (1.f / sqrtf((float)D)) * LOG2E_F;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == APERTIS_F32) return D == 64 ? launch_decode<float, 64>(a, B, st) : launch_decode<float, 128>(a, B, st);
+  return D == 64 ? launch_decode<bf16_t, 64>(a, B, st) : launch_decode<bf16_t, 128>(a, B, st);
+}

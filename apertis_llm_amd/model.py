@@ -804,6 +804,29 @@ class ApertisAttention(nn.Module):
         ctxv = ops.causal_attention(q, k, v, self.num_attention_heads, key_valid, self.attention_dropout.p, self.training)
         return self.out_proj(ctxv), cache
 
+    def _decode_ok(self, q, att_mask, past_kv, output_att, use_c):
+        """Whether this call is a single-token step the KV-cache decode kernels take: the past is a layer of an ops.KVCache
+        with room for one more row and the projections' dtype, one query position, inference (no grad, eval, use_cache, no
+        attention weights), on the GPU, D 64 or 128, both switches on, the position known on the host, and key 0 of every
+        sequence valid (the model's mask says so, _AttnMask: no row without a valid key).  Anything else with a KVCache in
+        flight runs the stock branch on the cache's views and returns plain tensors."""
+        if not (isinstance(past_kv, ops.KVLayer) and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and q.is_cuda
+                and q.shape[1] == 1 and use_c and not output_att and not self.training and not torch.is_grad_enabled()
+                and isinstance(att_mask, _AttnMask) and att_mask.decode_ok and att_mask.pos_host is not None
+                and ops.attention_decode_supported(q, self.num_attention_heads)):
+            return False
+        cache, kv = past_kv.cache, att_mask.key_valid
+        n = cache.lengths[past_kv.layer]
+        return (q.dtype == cache.dtype and n < cache.capacity and q.shape[0] == cache.k[0].shape[0]
+                and (kv is None or tuple(kv.shape) == (q.shape[0], n + 1)))
+
+    def _decode_attention(self, q, k, v, att_mask, past_kv):
+        cache, layer = past_kv.cache, past_kv.layer
+        cos, sin = (self.rope.cos_cached, self.rope.sin_cached) if self.rope is not None else (None, None)
+        q = ops.kv_append_rope(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
+        ctxv = ops.attention_decode(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
+        return self.out_proj(ctxv.unsqueeze(1)), cache
+
     def _heads(self, t):
         B, L, _ = t.shape
         return t.view(B, L, self.num_attention_heads, self.attention_head_size).transpose(1, 2)
@@ -822,11 +845,15 @@ class ApertisAttention(nn.Module):
             out, proxy, cache = self.attention_mechanism_impl(x, attention_mask=att_mask, position_ids=pos_ids,
                                                               past_key_value=past_kv, output_attentions=output_att,
                                                               use_cache=use_c)
-        elif self._fused_ok(q := self.q_proj(x), att_mask, past_kv, output_att):
+        elif self._decode_ok(q := self.q_proj(x), att_mask, past_kv, output_att, use_c):
+            out, cache = self._decode_attention(q, self.k_proj(x), self.v_proj(x), att_mask, past_kv)
+            proxy = None
+        elif self._fused_ok(q, att_mask, past_kv, output_att):
             out, cache = self._fused_attention(q, self.k_proj(x), self.v_proj(x), att_mask, pos_ids, use_c)
             proxy = None
         else:
-            # decode with a KV cache, output_attentions, other head dims, CPU, left padding: stock torch.
+            # decode with a plain-tensor KV cache (or what the decode kernels do not take of a KVCache: its views are the
+            # past), output_attentions, other head dims, CPU, left padding: stock torch.
             if isinstance(att_mask, _AttnMask):
                 att_mask = att_mask.additive()
             k, v = self.k_proj(x), self.v_proj(x)
@@ -972,12 +999,15 @@ ApertisFeedForward._small_entry = _ffn_small_entry
 class _AttnMask:
     """What a standard_mha layer receives as its mask from ApertisModel.forward: the raw key validity [B, L] (None: nothing
     padded) for the fused kernels, whether the fused path may run (no query row without a valid key), whether the positions
-    are the model's own 0..L-1, and the additive mask of the stock path, built only if that path asks for it."""
-    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive")
+    are the model's own 0..L-1, and the additive mask of the stock path, built only if that path asks for it.  For a
+    single-token step against a KVCache: whether the decode kernels may run (key 0 of every sequence valid, so every row has a
+    valid key) and the step's position as a HOST integer (None when the caller gave position_ids: only a tensor knows them)."""
+    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host")
 
-    def __init__(self, key_valid, fused_ok, default_pos, make_additive):
+    def __init__(self, key_valid, fused_ok, default_pos, make_additive, decode_ok=False, pos_host=None):
         self.key_valid, self.fused_ok, self.default_pos = key_valid, fused_ok, default_pos
         self._make, self._additive = make_additive, None
+        self.decode_ok, self.pos_host = decode_ok, pos_host
 
     def additive(self):
         if self._make is not None:
@@ -1090,24 +1120,30 @@ class ApertisModel(nn.Module):
             return None
         return (1.0 - allow.to(inputs_embeds.dtype)) * torch.finfo(inputs_embeds.dtype).min
 
-    def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos):
+    def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos, pos_host=None):
         """The standard_mha layers' mask (_AttnMask).  One host sync when a mask is given, as before: whether anything is
-        padded and whether key 0 of every sequence is valid (with no cache, then every query row has a valid key: right
-        padding, the trainer's form, stays on the fused path) come back together."""
+        padded and whether key 0 of every sequence is valid (then every query row has a valid key: right padding, the
+        trainer's form, stays on the fused path with no cache, and a step against a KVCache on the decode kernels - a
+        finished sequence of generate() keeps key 0) come back together."""
         default_pos = default_pos and past_len == 0
         if attention_mask is None:
-            return _AttnMask(None, True, default_pos, None)
+            return _AttnMask(None, True, default_pos, None, True, pos_host)
         valid = attention_mask.bool()
         all_valid, col0 = torch.stack((valid.all(), valid[:, 0].all())).tolist()
         if all_valid:
-            return _AttnMask(None, True, default_pos, None)
+            return _AttnMask(None, True, default_pos, None, True, pos_host)
         return _AttnMask(attention_mask, bool(col0) and past_len == 0, default_pos,
-                         lambda: self._prepare_decoder_attention_mask(attention_mask, input_shape, inputs_embeds, past_len))
+                         lambda: self._prepare_decoder_attention_mask(attention_mask, input_shape, inputs_embeds, past_len),
+                         bool(col0), pos_host)
 
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, pixel_values=None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None):
+        """past_key_values: a prefill's tuple of per-layer pairs (plain tensors in, plain tensors out), or for standard_mha an
+        ops.KVCache: a single-token step then appends to it IN PLACE on the decode kernels and hands the same object back
+        (position_ids = None: the step's position is the cache's length); a call the kernels do not take runs the stock
+        branch on the cache's views and hands back plain tensors."""
         cfg = self.config
         use_c = cfg.use_cache if use_cache is None else use_cache
         out_att = cfg.output_attentions if output_attentions is None else output_attentions
@@ -1121,7 +1157,10 @@ class ApertisModel(nn.Module):
         B, Lq = inputs_embeds.shape[:2]
         ssm = cfg.attention_type != "standard_mha"
         past_len = 0
-        if past_key_values is not None and past_key_values[0] is not None and not ssm:
+        kv_cache = past_key_values if isinstance(past_key_values, ops.KVCache) else None
+        if kv_cache is not None:
+            past_len = kv_cache.length
+        elif past_key_values is not None and past_key_values[0] is not None and not ssm:
             past_len = past_key_values[0][0].shape[1]
         pos = position_ids
         if pos is None:
@@ -1142,8 +1181,9 @@ class ApertisModel(nn.Module):
         elif cfg.multimodal and pixel_values is not None:
             logger.warning("pixel_values provided with past_key_values: image ignored for this step")
         x = self.embed_dropout(x)
-        mask = None if ssm else self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len,
-                                                     position_ids is None and pos_layers is pos)
+        own_pos = position_ids is None and pos_layers is pos
+        mask = None if ssm else self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len, own_pos,
+                                                     past_len if own_pos and kv_cache is not None and x.shape[1] == 1 else None)
 
         all_hs, all_att, all_cache = [], [], []
         lbs, rzs = [], []
@@ -1184,8 +1224,12 @@ class ApertisModel(nn.Module):
             # one reduction over the layers instead of two scalar adds per layer (core.py:1283-1287 sums as it goes)
             lb_tot = torch.stack(lbs).sum() if lbs else _zero_scalar(x.device, x.dtype)
             rz_tot = torch.stack(rzs).sum() if rzs else _zero_scalar(x.device, x.dtype)
+        if kv_cache is not None and all_cache and all(c is kv_cache for c in all_cache):
+            new_past = kv_cache                   # every layer appended in place (the decode kernels): the same object goes back
+        else:
+            new_past = tuple(all_cache) if use_c and all_cache else None
         return (x, tuple(all_hs) if out_hs and all_hs else None, tuple(all_att) if out_att and all_att else None,
-                tuple(all_cache) if use_c and all_cache else None,
+                new_past,
                 lb_tot if cfg.use_expert_system else None, rz_tot if cfg.use_expert_system else None)
 
     def _decode_prepass(self, st):
@@ -1408,10 +1452,17 @@ class ApertisForCausalLM(nn.Module):
                                                      position_ids_override=pos if past is None else None,
                                                      pixel_values=px, use_cache=use_cache)
             px = None
+            # (a step against a KVCache takes its position from the cache's length, a host integer - the value
+            #  prepare_inputs_for_generation puts into every row, mask.shape[1] - 1 - so the decode kernels need no read-back)
             out = self(input_ids=inp["input_ids"], attention_mask=inp["attention_mask"],
-                       position_ids=inp["position_ids"], past_key_values=inp["past_key_values"],
+                       position_ids=None if isinstance(past, ops.KVCache) else inp["position_ids"],
+                       past_key_values=inp["past_key_values"],
                        pixel_values=inp.get("pixel_values"), use_cache=inp["use_cache"])
+            prefill = past is None
             past = out[4] if use_cache else None
+            if prefill and past is not None and self._kv_cache_ok(past, tokens, max_new_tokens):
+                # standard_mha: the prefill's (k, v) move into preallocated buffers once; every later step appends in place
+                past = ops.KVCache.from_prefill(past, mask.shape[1] + max_new_tokens)
             if fused and sampler is None:
                 fused = ops.sample_supported(out[1][:, -1, :])
                 if fused:
@@ -1467,6 +1518,15 @@ class ApertisForCausalLM(nn.Module):
                 # the remaining single-token steps as ONE captured HIP graph replayed `left` times (same kernels, same tokens)
                 return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad)
         return tokens
+
+    def _kv_cache_ok(self, past, tokens, max_new_tokens):
+        """Whether generate() carries this prefill's cache as an ops.KVCache (the decode kernels then take every step that
+        qualifies, ApertisAttention._decode_ok): standard_mha on the GPU, both switches on, fp32 or bf16 with D 64 or 128."""
+        cfg = self.config
+        return (cfg.attention_type == "standard_mha" and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and tokens.is_cuda
+                and max_new_tokens > 1 and not self.training and not torch.is_grad_enabled()
+                and isinstance(past[0], tuple) and len(past[0]) == 2 and past[0][0].dim() == 3
+                and ops.attention_decode_supported(past[0][0], cfg.num_attention_heads))
 
     def _decode_graph_ok(self, tokens, do_sample, repetition_penalty, sampler=None):
         cfg = self.config

@@ -13,7 +13,7 @@ One module per subsystem (round 6: the 2 500-line ops.py split up):
     decode   single-token decode step
     moe      gate, plan, gather-LN, combine, small-batch entrance, expert MLP
     loss     cross-entropy, fused LM head + cross-entropy
-    attention  standard_mha: RoPE, causal flash attention
+    attention  standard_mha: RoPE, causal flash attention, KV-cache decode
     sample   generate()'s next-token selection (penalty, temperature, top-k, top-p, draw) in one launch
 `from apertis_llm_amd import ops; ops.<name>` reaches every name of every module, private helpers included (tests and tools use
 them).  The module-level SWITCHES (SCAN_LOOKBACK, TRAIN_PREP, GEMM_DYNAMIC_QUEUE, ...) live in the module whose code reads them;
@@ -36,7 +36,7 @@ _FORWARDED = {
     "GEMM_DYNAMIC_QUEUE": gemm, "TN_DYNAMIC_QUEUE": gemm, "DENSE_WGRAD_WIDE": gemm, "_splitk_depth": gemm,
     "TRAIN_PREP": prep, "WEIGHT_EPOCH": prep, "_ACTIVE_TRAIN_PREP": prep, "_prep_scope_depth": prep,
     "_TIMER": _base,
-    "ATTN_FUSED": attention,
+    "ATTN_FUSED": attention, "ATTN_DECODE_FUSED": attention,
     "SAMPLE_FUSED": sample, "SAMPLE_UNIFORMS": sample,
 }
 for _m in _MODULES:

@@ -1,7 +1,9 @@
-"""standard_mha: interleaved-pair RoPE over the full width and causal softmax attention (flash style).
+"""standard_mha: interleaved-pair RoPE over the full width, causal softmax attention (flash style), and single-token decode
+against a preallocated KV cache (KVCache, kv_append_rope, attention_decode).
 
 Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autograd bookkeeping only; every computation is a
-HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip).  Tensors must live on a ROCm device.
+HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip).  Tensors must live on a ROCm
+device.
 """
 import torch
 
@@ -155,3 +157,196 @@ def causal_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=Fal
         raise ApertisHipError(f"causal_attention: dropout_p {dropout_p} outside [0, 1)")
     seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0
     return _CausalAttention.apply(q, k, v, int(heads), key_valid, p, seed)
+
+
+# ---------------------------------------------------------------------------------------------------- KV-cache decode
+# single-token steps of a standard_mha model against a KVCache take the kernels of csrc/attention_decode.hip when this AND
+# ATTN_FUSED are on (ATTN_FUSED = False keeps meaning "stock torch attention everywhere"); off: torch.cat + stock SDPA
+ATTN_DECODE_FUSED = True
+
+ATTN_DECODE_MAX_SPLITS = 64          # = APERTIS_ATTN_DECODE_MAX_SPLITS
+
+
+class KVLayer:
+    """`cache[i]`: layer i of a KVCache, indexable like the (k, v) pair it replaces - [0] and [1] are VIEWS of the layer's
+    first `length` rows ([B, length, W]), built when asked for."""
+    __slots__ = ("cache", "layer")
+
+    def __init__(self, cache, layer):
+        self.cache, self.layer = cache, layer
+
+    def __len__(self):
+        return 2
+
+    def __getitem__(self, j):
+        if j not in (0, 1, -1, -2):
+            raise IndexError(j)
+        c = self.cache
+        return (c.k if j in (0, -2) else c.v)[self.layer][:, :c.lengths[self.layer]]
+
+    def __iter__(self):
+        return iter((self[0], self[1]))
+
+
+class KVCache:
+    """Preallocated KV cache of a standard_mha model: per layer one `k` and one `v` buffer [B, capacity, W] (W = heads * D,
+    token-major, the layout of a prefill's `past_key_values`) and one length per layer.  `cache[i]` is (k[:, :len], v[:, :len])
+    as views, `len(cache)` the number of layers, so it reads like the tuple of pairs it replaces.
+
+    It is an explicit, MUTABLE object: a decode step (kv_append_rope) writes row `len` of every layer IN PLACE and the layer's
+    length grows by one - there is no copy of the cache per token, and therefore ONE continuation per cache: a caller that wants
+    to branch a generation builds a second cache (from_prefill) for the second branch.  All layers of one step append at the
+    same row: each layer keeps its own length, so layer i's append does not move what layer i + 1 sees.  A step that raised
+    half-way leaves the layers at different lengths; such a cache is not used again."""
+
+    def __init__(self, k, v, length=0):
+        if len(k) != len(v) or not k:
+            raise ApertisHipError("KVCache: one k and one v buffer per layer")
+        for a, b in zip(k, v):
+            if (a.dim() != 3 or a.shape != b.shape or a.dtype != b.dtype or a.shape != k[0].shape or a.dtype != k[0].dtype
+                    or a.stride(2) != 1 or b.stride(2) != 1):
+                raise ApertisHipError("KVCache: buffers are [B, capacity, W] with unit inner stride, one shape and dtype")
+        self.k, self.v = list(k), list(v)
+        if not 0 <= length <= self.capacity:
+            raise ApertisHipError(f"KVCache: length {length} outside [0, {self.capacity}]")
+        self.lengths = [int(length)] * len(self.k)
+        self._ws = None
+
+    @classmethod
+    def empty(cls, layers, B, capacity, W, dtype=torch.float32, device=None):
+        if layers < 1 or B < 0 or capacity < 1 or W < 1:
+            raise ApertisHipError(f"KVCache.empty: layers {layers}, B {B}, capacity {capacity}, W {W}")
+        mk = lambda: [torch.empty(B, capacity, W, dtype=dtype, device=device) for _ in range(layers)]     # noqa: E731
+        return cls(mk(), mk(), 0)
+
+    @classmethod
+    def from_prefill(cls, past, capacity):
+        """From a prefill's `past_key_values` (per layer (k, v), [B, L, W]): one copy per layer into buffers of `capacity`
+        rows, in the prefill's dtype, once per generation."""
+        L = past[0][0].shape[1]
+        if capacity < L:
+            raise ApertisHipError(f"KVCache.from_prefill: capacity {capacity} below the prefill's {L} positions")
+        B, _, W = past[0][0].shape
+        c = cls.empty(len(past), B, capacity, W, past[0][0].dtype, past[0][0].device)
+        for i, (k, v) in enumerate(past):
+            c.k[i][:, :L].copy_(k)
+            c.v[i][:, :L].copy_(v)
+        c.lengths = [L] * len(past)
+        return c
+
+    capacity = property(lambda self: self.k[0].shape[1])
+    dtype = property(lambda self: self.k[0].dtype)
+    length = property(lambda self: self.lengths[0], doc="positions held (layer 0's: all layers agree between steps)")
+
+    def __len__(self):
+        return len(self.k)
+
+    def __getitem__(self, i):
+        if not -len(self.k) <= i < len(self.k):
+            raise IndexError(i)
+        return KVLayer(self, i % len(self.k))
+
+    def __iter__(self):
+        return (KVLayer(self, i) for i in range(len(self.k)))
+
+    def _workspace(self, nbytes):
+        if nbytes and (self._ws is None or self._ws.numel() * 4 < nbytes):
+            self._ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.k[0].device)
+        return self._ws if nbytes else None
+
+
+def _row2d(t, W, what):
+    """[B, W] or [B, 1, W] -> ([B, W] view with unit inner stride, row stride)."""
+    if t.dim() == 3 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 2 or t.shape[-1] != W:
+        raise ApertisHipError(f"{what}: expected [B, {W}] or [B, 1, {W}], got {tuple(t.shape)}")
+    if t.stride(-1) != 1 or (t.shape[0] > 1 and t.stride(0) < W):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else W)
+
+
+def kv_append_rope(q, k, v, cache, layer, t=None, cos=None, sin=None):
+    """One token of every sequence into layer `layer` of `cache`, in ONE launch: q and k ([B, W] or [B, 1, W]) are rotated at
+    rotary position `t` (a host integer; default: the row appended to) with the module's fp32 cos_cached / sin_cached - the
+    same bits as rope_qk - rotated k and v go into cache row `lengths[layer]`, IN PLACE, and that length grows by one.
+    cos = sin = None: no rotation, a plain append.  Returns the rotated q [B, W].  `t` outside [-max_pos, max_pos) raises
+    IndexError as the stock module's table lookup does; a full cache raises before anything is written."""
+    _require_gpu(q, k, v, cache.k[layer], cos, sin)
+    lib = _lib.load()
+    B, cap, W = cache.k[layer].shape
+    row = cache.lengths[layer]
+    if row >= cap:
+        raise ApertisHipError(f"kv_append_rope: the cache is full ({cap} rows)")
+    q, q_rs = _row2d(q, W, "kv_append_rope q")
+    k, k_rs = _row2d(k, W, "kv_append_rope k")
+    v, v_rs = _row2d(v, W, "kv_append_rope v")
+    if not (q.shape[0] == k.shape[0] == v.shape[0] == B and q.dtype == k.dtype == v.dtype == cache.dtype):
+        raise ApertisHipError(f"kv_append_rope: q/k/v {tuple(q.shape)} {q.dtype} against a cache of [{B}, {cap}, {W}] {cache.dtype}")
+    max_pos = 0
+    t = row if t is None else int(t)
+    if (cos is None) != (sin is None):
+        raise ApertisHipError("kv_append_rope: cos and sin come together")
+    if cos is not None:
+        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
+            raise ApertisHipError(f"kv_append_rope: cos/sin must be fp32 [max_pos, {W // 2}]")
+        cos, sin, max_pos = cos.contiguous(), sin.contiguous(), cos.shape[0]
+        if not -max_pos <= t < max_pos:
+            raise IndexError(f"position {t} outside the rotary table of {max_pos} positions")
+    qo = torch.empty(B, W, device=q.device, dtype=q.dtype)
+    kc, vc = cache.k[layer], cache.v[layer]
+    _launch("apertis_rope_kv_append", lib.apertis_rope_kv_append,
+            (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(cos), ptr(sin), max_pos, t, ptr(qo), W, ptr(kc), kc.stride(1),
+             kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, row, B, W, dtype_code(q), stream_ptr()),
+            work=5.0 * B * W * q.element_size())
+    cache.lengths[layer] = row + 1
+    return qo
+
+
+def attention_decode_supported(q, heads):
+    """Whether attention_decode takes one query row per sequence of this width and dtype (D 64 or 128, fp32 or bf16);
+    q: [B, W] or [B, L, W]."""
+    return (q.dim() in (2, 3) and q.shape[-1] % heads == 0 and q.shape[-1] // heads in (64, 128)
+            and q.dtype in (torch.float32, torch.bfloat16))
+
+
+def attention_decode_splits(B, heads, Lk, D):
+    """The number of pieces attention_decode cuts Lk keys into when splits = 0 (a pure function of the shape)."""
+    return int(_lib.load().apertis_attention_decode_splits(B, heads, Lk, D))
+
+
+def attention_decode(q, cache, layer, heads, key_valid=None, splits=0):
+    """softmax(q K^T / sqrt(D)) V for ONE query row per sequence and head over the rows layer `layer` of `cache` holds
+    (Lk = lengths[layer]: after kv_append_rope, the new token's own key included).  q: [B, W] or [B, 1, W] in the cache's dtype
+    (fp32 or bf16, D = W / heads in {64, 128}); returns O [B, W] where out_proj reads it.  key_valid: [B, >= Lk] (the raw
+    attention_mask, nonzero = attend; columns >= Lk are never read) or None.  splits: 0 = apertis_attention_decode_splits'
+    choice, else 1..min(Lk, ATTN_DECODE_MAX_SPLITS) pieces of the key range (tests reach every value); the same inputs and split count give
+    the same bits."""
+    _require_gpu(q, cache.k[layer], key_valid)
+    lib = _lib.load()
+    kc, vc = cache.k[layer], cache.v[layer]
+    B, cap, W = kc.shape
+    Lk = cache.lengths[layer]
+    q, q_rs = _row2d(q, W, "attention_decode q")
+    if not attention_decode_supported(q, heads) or q.shape[0] != B or q.dtype != cache.dtype:
+        raise ApertisHipError(f"attention_decode: q {tuple(q.shape)} {q.dtype} with {heads} heads against a cache of "
+                              f"[{B}, {cap}, {W}] {cache.dtype} (D 64 or 128, fp32 or bf16, one dtype)")
+    if q.data_ptr() % 16 or (q_rs * q.element_size()) % 16:
+        q, q_rs = q.clone(memory_format=torch.contiguous_format), W
+    D = W // heads
+    kv_rs = 0
+    if key_valid is not None:
+        if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < Lk:
+            raise ApertisHipError(f"attention_decode: key_valid {tuple(key_valid.shape)}, expected ({B}, >= {Lk})")
+        if key_valid.dtype != torch.int64 or key_valid.stride(1) != 1:
+            key_valid = key_valid.to(torch.int64).contiguous()
+        kv_rs = key_valid.stride(0) if B > 1 else key_valid.shape[1]
+    n = int(splits) if splits else int(lib.apertis_attention_decode_splits(B, heads, max(Lk, 1), D)) if B else 1
+    ws = cache._workspace(max(int(lib.apertis_attention_decode_workspace_bytes(B, heads, D, n)), 0)) if 1 <= n <= ATTN_DECODE_MAX_SPLITS else None
+    out = torch.empty(B, W, device=q.device, dtype=q.dtype)
+    nbytes = 2.0 * B * Lk * W * q.element_size()
+    _launch("apertis_attention_decode", lib.apertis_attention_decode,
+            (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
+             ptr(out), W, ptr(ws), B, Lk, heads, D, int(splits), dtype_code(q), stream_ptr()),
+            work=4.0 * B * Lk * W, detail=f"{B}x{heads}x{D}", nbytes=nbytes)
+    return out

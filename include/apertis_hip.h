@@ -49,12 +49,13 @@ extern "C" {
  * kernel; measured 15 % SLOWER at the bench shape (profiles/r6_probe_nt2i_vs_nt4r.log), so no caller sets it by default. */
 #define APERTIS_ACT_INTERLEAVED 0x400
 
-/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.9 - apertis_token_counts,
+/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.10 - apertis_rope_kv_append,
+ * apertis_attention_decode, apertis_attention_decode_splits / _workspace_bytes: standard_mha KV-cache decode; 4.9 - apertis_token_counts,
  * apertis_sample_next: generate()'s penalty / temperature / top-k / top-p / draw in one launch; 4.8 - apertis_rope_qk_fwd / _bwd,
  * apertis_attention_fwd / _bwd, apertis_attention_bwd_workspace_bytes: standard_mha; round 6: 4.7 - apertis_cross_entropy_fwd_bwd, apertis_layernorm_combine_bwd; round 5: 4.5 - apertis_scan_lookback_*, apertis_tiny_linear_bwd_pad; round 4: 4.4 - lean scan
  * entry points, apertis_scan_lean_fwd_dt, apertis_grouped_gemm_tn_dense_variant, apertis_weight_prep, apertis_ssm_decode_state_dt).  A host binding should
  * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does). */
-#define APERTIS_ABI_VERSION ((4 << 16) | 9)
+#define APERTIS_ABI_VERSION ((4 << 16) | 10)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
 const char *apertis_arch(void);
@@ -756,6 +757,47 @@ int apertis_attention_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_
                           const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
                           const int64_t *key_valid, float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B,
                           int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * standard_mha single-token decode against a preallocated KV cache (the attention of core.py:639-700 with a past):
+ * k_cache, v_cache [B, cap, W = H*D] token-major with a row stride (*_rs >= W) and a batch stride (*_bs >= cap * row stride),
+ * head h in columns [h*D, (h+1)*D) - the layout of the prefill's (k, v).
+ *
+ * apertis_rope_kv_append, one launch per layer and step: reads the new token's projections q, k, v ([B, W] rows, a row stride
+ * each), rotates q and k at position t exactly as apertis_rope_qk_fwd does (the same device code, the same bits, fp32 and
+ * bf16), writes rotated q to q_out [B, W] (row stride q_out_rs) and rotated k and unrotated v into row t_cache of the caches.
+ *   cos/sin_cached: fp32 [max_pos, W/2], or both NULL for no rotation (a plain append; q_out = q)
+ *   t             : rotary position, by value; in [-max_pos, max_pos) (negative wraps), else APERTIS_ERR_ARG
+ *   t_cache       : cache row, by value; in [0, cap), else APERTIS_ERR_ARG with nothing written
+ *
+ * apertis_attention_decode: O[b,h] = sum_j P[j] V[b,j,h], P = softmax over j < Lk with key_valid[b,j] != 0 of
+ * scale * q[b,h].K[b,j,h], scale = 1/sqrt(D) in fp32.  Scores, softmax and the P.V sums are fp32 (P is not rounded).
+ *   q, out        : [B, W] with row strides q_rs, out_rs
+ *   key_valid     : int64 [B, >= Lk] with row stride kv_rs (the raw attention_mask, nonzero = attend), or NULL.  A row with
+ *                   no valid key gets O = 0 (callers keep such rows off this path).  Cache rows >= Lk, mask columns >= Lk
+ *                   and the cache rows of masked keys are never read.
+ *   Lk            : 1 <= Lk <= cap, else APERTIS_ERR_ARG
+ *   D             : 64 or 128, B and H <= 65535, q / cache pointers and every cache stride on 16-byte boundaries, else
+ *                   APERTIS_ERR_UNSUPPORTED; dtype fp32 or bf16
+ *   splits        : the key range is cut into `splits` equal pieces, one work-group each (grid splits x H x B); 0 takes
+ *                   the heuristic min(256 / (B*H), Lk / 128, APERTIS_ATTN_DECODE_MAX_SPLITS) in integers, at least 1, which
+ *                   apertis_attention_decode_splits returns (a pure function of its arguments; -1 for a size < 1).
+ *                   Forced: 1 <= splits <= min(Lk, APERTIS_ATTN_DECODE_MAX_SPLITS), else APERTIS_ERR_ARG.
+ *   workspace     : with splits > 1, apertis_attention_decode_workspace_bytes bytes (fp32 (m, l) and o[D] per piece; 0 bytes
+ *                   for splits = 1, -1 for a bad argument): the pieces' partial results, folded in piece order by a second
+ *                   launch.  With splits = 1 the one launch writes out and workspace may be NULL.
+ * Two plain launches at most, no atomics: the same inputs and split count give the same bits on every run. */
+#define APERTIS_ATTN_DECODE_MAX_SPLITS 64
+int apertis_rope_kv_append(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                           const float *cos_cached, const float *sin_cached, int64_t max_pos, int64_t t, void *q_out,
+                           int64_t q_out_rs, void *k_cache, int64_t kc_rs, int64_t kc_bs, void *v_cache, int64_t vc_rs,
+                           int64_t vc_bs, int64_t cap, int64_t t_cache, int64_t B, int64_t W, int dtype, void *stream);
+int64_t apertis_attention_decode_splits(int64_t B, int64_t H, int64_t Lk, int64_t D);
+int64_t apertis_attention_decode_workspace_bytes(int64_t B, int64_t H, int64_t D, int64_t splits);
+int apertis_attention_decode(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs, const void *v_cache,
+                             int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid, int64_t kv_rs, void *out,
+                             int64_t out_rs, float *workspace, int64_t B, int64_t Lk, int64_t H, int64_t D, int64_t splits,
+                             int dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * generate()'s next-token selection (core.py:1605-1633), one launch per token step, one 1024-thread work-group per row.

@@ -1,0 +1,162 @@
+"""standard_mha KV-cache decode: the HIP kernels (ops.kv_append_rope + ops.attention_decode, csrc/attention_decode.hip) against
+the stock torch step they replace.
+
+    python tools/prof_mha_decode.py [--out FILE] [--no-e2e] [--no-layer]
+
+1. One layer-step alone: append + attention against the stock branch of ApertisAttention.forward (RotaryEmbedding twice,
+   torch.cat twice, head transposes, F.scaled_dot_product_attention) at create-model's 125M shape (14 heads x 64) and at
+   12 x 64 and 8 x 128, B in {1, 16}, Lk in {128, 512, 2047}, bf16 and fp32.  Device events around each call, warm-up of
+   every shape, then the median of A/B-alternated calls; a 512 MiB read runs before every timed call, so K / V come from HBM
+   as they do in a real step (the other layers' weights and caches pass through the caches in between; a read, not a fill:
+   a fill leaves dirty lines whose write-back would share the timed call's bandwidth).  `attn_us` times the
+   attention kernel(s) alone; `hbm_share` is its K / V bytes over that time as a share of 6.29 TB/s.
+2. End to end: generate() new tokens/s on create_apertis_model("125M") and ("350M"), standard_mha, bf16 autocast, B in
+   {1, 16}, 1 920-token prefill + 128 new tokens, per token step = (t(128) - t(1)) / 127 as bench.py --decode computes it,
+   greedy and chat's sampling parameters, ATTN_DECODE_FUSED on and off alternated in one process (off = the stock path).
+Prints one JSON line per measurement and writes them to --out.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK = 6.29e12
+
+
+def layer_step(dev, emit, iters=40):
+    import torch
+    import torch.nn.functional as F
+    import apertis_llm_amd as A
+    from apertis_llm_amd import ops
+    flush = torch.zeros(64 << 20, dtype=torch.int64, device=dev)
+
+    def timed(fn):
+        flush.sum()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e) * 1e3
+    for H, D in ((14, 64), (12, 64), (8, 128)):
+        W = H * D
+        rope = A.model.RotaryEmbedding(W, 2048).to(dev)
+        for dt in (torch.bfloat16, torch.float32):
+            for B in (1, 16):
+                for Lk in (128, 512, 2047):
+                    gen = torch.Generator(device=dev).manual_seed(Lk + B)
+                    q, k, v = (torch.randn(B, 1, W, device=dev, generator=gen).to(dt) for _ in range(3))
+                    past_k, past_v = (torch.randn(B, Lk - 1, W, device=dev, generator=gen).to(dt) for _ in range(2))
+                    cache = ops.KVCache.from_prefill(((past_k, past_v),), Lk + 1)
+                    pos = torch.full((B, 1), Lk - 1, dtype=torch.long, device=dev)
+                    hold = {}
+
+                    def fused():
+                        cache.lengths[0] = Lk - 1
+                        hold["q"] = ops.kv_append_rope(q, k, v, cache, 0, Lk - 1, rope.cos_cached, rope.sin_cached)
+                        return ops.attention_decode(hold["q"], cache, 0, H)
+
+                    def attn_only():
+                        return ops.attention_decode(hold["q"], cache, 0, H)
+
+                    def stock():
+                        qr, kr = rope(q, pos), rope(k, pos)
+                        kk, vv = torch.cat([past_k, kr], dim=1), torch.cat([past_v, v], dim=1)
+                        qh, kh, vh = (t.view(B, t.shape[1], H, D).transpose(1, 2) for t in (qr, kk, vv))
+                        return F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, 1, W)
+                    with torch.no_grad():
+                        ref, got = stock(), fused()
+                        err = float((got.float() - ref[:, 0].float()).abs().max())
+                        fns = (("fused", fused), ("attn", attn_only), ("stock", stock))
+                        times = {n: [] for n, _ in fns}
+                        for _ in range(5):
+                            for _, fn in fns:
+                                fn()
+                        torch.cuda.synchronize()
+                        for _ in range(iters):
+                            for n, fn in fns:
+                                times[n].append(timed(fn))
+                    med = {n: statistics.median(t) for n, t in times.items()}
+                    nbytes = 2.0 * B * Lk * W * q.element_size()
+                    emit({"what": "layer_step", "heads": H, "D": D, "B": B, "Lk": Lk, "dtype": str(dt).split(".")[-1],
+                          "splits": ops.attention_decode_splits(B, H, Lk, D), "fused_us": round(med["fused"], 2),
+                          "attn_us": round(med["attn"], 2), "stock_us": round(med["stock"], 2),
+                          "stock_over_fused": round(med["stock"] / med["fused"], 3), "kv_bytes": nbytes,
+                          "hbm_share": round(nbytes / (med["attn"] * 1e-6) / HBM_PEAK, 4), "max_abs_diff_vs_stock": err,
+                          "iters": iters})
+
+
+def e2e(dev, emit):
+    import torch
+    import apertis_llm_amd as A
+    from apertis_llm_amd import ops
+    modes = {"greedy": dict(do_sample=False), "chat": dict(do_sample=True, temperature=0.7, top_k=50, top_p=0.9)}
+    PREFILL, NEW = 1920, 128
+    for size in ("125M", "350M"):
+        torch.manual_seed(0)
+        model = A.create_apertis_model(size, vocab_size_override=32000, attention_type_override="standard_mha").to(dev).eval()
+        cfg = model.config
+        for B in (1, 16):
+            ids = torch.randint(4, 32000, (B, PREFILL), device=dev, generator=torch.Generator(device=dev).manual_seed(7))
+
+            def run(n_new, kw):
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = model.generate(ids, max_new_tokens=n_new, eos_token_id=[-1], use_cache=True, **kw)
+                    torch.cuda.synchronize()
+                    return time.perf_counter() - t0, out
+            for mode, kw in modes.items():
+                res = {}
+                for rep in range(3):
+                    for fused in (True, False):
+                        ops.ATTN_DECODE_FUSED = fused
+                        torch.manual_seed(rep)
+                        run(4, kw)
+                        t1, _ = run(1, kw)
+                        tn, out = run(NEW, kw)
+                        assert out.shape == (B, PREFILL + NEW)
+                        res.setdefault(fused, []).append((tn - t1) / (NEW - 1))
+                ops.ATTN_DECODE_FUSED = True
+                for fused, v in res.items():
+                    per_tok = min(v)
+                    emit({"what": "generate", "model": size, "layers": cfg.num_hidden_layers, "hidden": cfg.hidden_size,
+                          "heads": cfg.num_attention_heads, "mode": mode, "B": B, "decode_fused": fused,
+                          "ms_per_token_step": round(1e3 * per_tok, 4), "tokens_per_s": round(B / per_tok, 1),
+                          "runs_ms": [round(1e3 * x, 3) for x in v]})
+        del model
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--no-layer", action="store_true")
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("prof_mha_decode.py needs a ROCm GPU")
+    dev = torch.device("cuda:0")
+    lines = []
+
+    def emit(d):
+        print(json.dumps(d), flush=True)
+        lines.append(d)
+        if args.out:                                  # (written as it goes: an interrupted run keeps what it measured)
+            with open(args.out, "w") as f:
+                for x in lines:
+                    f.write(json.dumps(x) + "\n")
+    if not args.no_layer:
+        layer_step(dev, emit)
+    if not args.no_e2e:
+        e2e(dev, emit)
+
+
+if __name__ == "__main__":
+    main()
