@@ -11,6 +11,12 @@
 // shuffles, the 4 waves of a work-group through 2 KiB of LDS.  The key range is split over work-groups (grid splits x H x B);
 // with splits > 1 every work-group leaves (m, l, o[D]) in a workspace and attn_decode_merge_k folds them in split order.  No
 // atomics, no waiting between work-groups: the same inputs and split count give the same bits.
+//
+// The *_at forms (a captured graph replays them): the step's state is one int64 in device memory, `len` = rows the cache holds.
+// The append writes row *len at rotary position *len + pos_offset and refuses, with an error word, a row or a position out of
+// range; the attention reads Lk = min(*len + 1, cap) itself and cuts it into a split count fixed by the caller, so grid and
+// workspace depend on nothing read from the device.  Same kernels as the by-value forms, same bits for the same row, Lk and
+// split count.
 #include "common.h"
 #include "rope_common.h"
 
@@ -50,6 +56,7 @@ struct DecArgs {
   void *out;
   float *ws_ml, *ws_o;
   int64_t q_rs, k_rs, k_bs, v_rs, v_bs, kv_rs, out_rs, Lk;
+  const int64_t *len;                 // the *_at form: Lk = min(*len + 1, cap) is read here, a.Lk holds cap (null: a.Lk is Lk)
   int H, splits;
   float sl2;                          // scale * log2(e)
 };
@@ -60,7 +67,12 @@ __global__ __launch_bounds__(256) void attn_decode_k(DecArgs a) {
   __shared__ float sm_m[DEC_WAVES], sm_l[DEC_WAVES], sm_o[DEC_WAVES][D];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane / LPR, c = (lane % LPR) * E;
   const int s = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-  const int64_t j0 = (int64_t)s * a.Lk / a.splits, j1 = (int64_t)(s + 1) * a.Lk / a.splits;
+  int64_t Lk = a.Lk;
+  if (a.len) {                        // (uniform: one scalar load; a piece with j0 == j1 reads nothing and leaves (-inf, 0, 0))
+    const int64_t n = *a.len + 1;
+    Lk = n < 0 ? 0 : n < a.Lk ? n : a.Lk;
+  }
+  const int64_t j0 = (int64_t)s * Lk / a.splits, j1 = (int64_t)(s + 1) * Lk / a.splits;
   float qf[E];
   unpack16<T>(*reinterpret_cast<const uint4 *>(static_cast<const T *>(a.q) + (int64_t)b * a.q_rs + h * D + c), qf);
   const T *kp = static_cast<const T *>(a.k) + (int64_t)b * a.k_bs + h * D + c;
@@ -179,13 +191,30 @@ int64_t decode_splits(int64_t B, int64_t H, int64_t Lk) {
   return s < 1 ? 1 : s;
 }
 
+// the *_at form of the append: row and position come from *len; a row outside the cache or a position outside the rotary table
+// is not written through - the kernel writes nothing and thread 0 sets *err (the host cannot check a replayed step)
+struct AppendAt {
+  const int64_t *len;
+  int64_t pos_offset, cap;
+  int32_t *err;
+};
+
 // one thread per (sequence, pair j): rotated q pair to q_out, rotated k pair and the v pair into cache row t_cache
 template <typename T>
 __global__ __launch_bounds__(256) void rope_kv_append_k(const T *q, int64_t q_rs, const T *k, int64_t k_rs, const T *v,
                                                         int64_t v_rs, const float *cs, const float *sn, int64_t max_pos, int64_t t,
                                                         T *qo, int64_t qo_rs, T *kc, int64_t kc_rs, int64_t kc_bs, T *vc,
-                                                        int64_t vc_rs, int64_t vc_bs, int64_t t_cache, int64_t half, int64_t total) {
+                                                        int64_t vc_rs, int64_t vc_bs, int64_t t_cache, int64_t half, int64_t total,
+                                                        AppendAt at) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (at.len) {
+    t_cache = *at.len;
+    t = t_cache + at.pos_offset;      // (no overflow: t_cache in [0, cap) is checked first, |pos_offset| on the host)
+    if (t_cache < 0 || t_cache >= at.cap || (cs && (t < -max_pos || t >= max_pos))) {
+      if (i == 0) *at.err = 1;
+      return;
+    }
+  }
   if (i >= total) return;
   const int64_t b = i / half, j = i - b * half;
   const T *qs = q + b * q_rs + 2 * j, *ks = k + b * k_rs + 2 * j, *vs = v + b * v_rs + 2 * j;
@@ -211,16 +240,23 @@ __global__ __launch_bounds__(256) void rope_kv_append_k(const T *q, int64_t q_rs
 
 }  // namespace
 
-extern "C" int apertis_rope_kv_append(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
-                                      const float *cos_cached, const float *sin_cached, int64_t max_pos, int64_t t, void *q_out,
-                                      int64_t q_out_rs, void *k_cache, int64_t kc_rs, int64_t kc_bs, void *v_cache, int64_t vc_rs,
-                                      int64_t vc_bs, int64_t cap, int64_t t_cache, int64_t B, int64_t W, int dtype, void *stream) {
+// both appends: t and t_cache by value (at.len null), or the device-held length
+static int rope_kv_append_impl(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs, const float *cos_cached,
+                               const float *sin_cached, int64_t max_pos, int64_t t, void *q_out, int64_t q_out_rs, void *k_cache,
+                        int64_t kc_rs, int64_t kc_bs, void *v_cache, int64_t vc_rs, int64_t vc_bs, int64_t cap, int64_t t_cache,
+                        int64_t B, int64_t W, int dtype, void *stream, const AppendAt &at) {
   if (!q || !k || !v || !q_out || !k_cache || !v_cache || (cos_cached == nullptr) != (sin_cached == nullptr)) return APERTIS_ERR_ARG;
   if (B < 0 || W <= 0 || (W & 1) || cap < 1 || (dtype != APERTIS_F32 && dtype != APERTIS_BF16)) return APERTIS_ERR_ARG;
   if (q_rs < W || k_rs < W || v_rs < W || q_out_rs < W || kc_rs < W || vc_rs < W || kc_bs < cap * kc_rs || vc_bs < cap * vc_rs)
     return APERTIS_ERR_ARG;
-  if (t_cache < 0 || t_cache >= cap) return APERTIS_ERR_ARG;
-  if (cos_cached && (max_pos <= 0 || t < -max_pos || t >= max_pos)) return APERTIS_ERR_ARG;
+  if (cos_cached && max_pos <= 0) return APERTIS_ERR_ARG;
+  if (at.len) {
+    // (an offset with which no row of the cache can land in the table is an argument error, and the kernel's sum cannot overflow)
+    if (!at.err || (cos_cached && (at.pos_offset <= -max_pos - cap || at.pos_offset >= max_pos))) return APERTIS_ERR_ARG;
+  } else {
+    if (t_cache < 0 || t_cache >= cap) return APERTIS_ERR_ARG;
+    if (cos_cached && (t < -max_pos || t >= max_pos)) return APERTIS_ERR_ARG;
+  }
   const int64_t half = W / 2, total = B * half;
   if (total == 0) return APERTIS_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -228,12 +264,30 @@ extern "C" int apertis_rope_kv_append(const void *q, int64_t q_rs, const void *k
   if (dtype == APERTIS_F32)
     hipLaunchKernelGGL((rope_kv_append_k<float>), grid, dim3(256), 0, st, (const float *)q, q_rs, (const float *)k, k_rs,
                        (const float *)v, v_rs, cos_cached, sin_cached, max_pos, t, (float *)q_out, q_out_rs, (float *)k_cache, kc_rs,
-                       kc_bs, (float *)v_cache, vc_rs, vc_bs, t_cache, half, total);
+                       kc_bs, (float *)v_cache, vc_rs, vc_bs, t_cache, half, total, at);
   else
     hipLaunchKernelGGL((rope_kv_append_k<bf16_t>), grid, dim3(256), 0, st, (const bf16_t *)q, q_rs, (const bf16_t *)k, k_rs,
                        (const bf16_t *)v, v_rs, cos_cached, sin_cached, max_pos, t, (bf16_t *)q_out, q_out_rs, (bf16_t *)k_cache,
-                       kc_rs, kc_bs, (bf16_t *)v_cache, vc_rs, vc_bs, t_cache, half, total);
+                       kc_rs, kc_bs, (bf16_t *)v_cache, vc_rs, vc_bs, t_cache, half, total, at);
   return apertis_check_launch();
+}
+
+extern "C" int apertis_rope_kv_append(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                      const float *cos_cached, const float *sin_cached, int64_t max_pos, int64_t t, void *q_out,
+                                      int64_t q_out_rs, void *k_cache, int64_t kc_rs, int64_t kc_bs, void *v_cache, int64_t vc_rs,
+                                      int64_t vc_bs, int64_t cap, int64_t t_cache, int64_t B, int64_t W, int dtype, void *stream) {
+  return rope_kv_append_impl(q, q_rs, k, k_rs, v, v_rs, cos_cached, sin_cached, max_pos, t, q_out, q_out_rs, k_cache, kc_rs, kc_bs,
+                             v_cache, vc_rs, vc_bs, cap, t_cache, B, W, dtype, stream, AppendAt{nullptr, 0, 0, nullptr});
+}
+
+extern "C" int apertis_rope_kv_append_at(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                         const float *cos_cached, const float *sin_cached, int64_t max_pos, const int64_t *len,
+                                         int64_t pos_offset, int32_t *err, void *q_out, int64_t q_out_rs, void *k_cache,
+                                         int64_t kc_rs, int64_t kc_bs, void *v_cache, int64_t vc_rs, int64_t vc_bs, int64_t cap,
+                                         int64_t B, int64_t W, int dtype, void *stream) {
+  if (!len) return APERTIS_ERR_ARG;
+  return rope_kv_append_impl(q, q_rs, k, k_rs, v, v_rs, cos_cached, sin_cached, max_pos, 0, q_out, q_out_rs, k_cache, kc_rs, kc_bs,
+                             v_cache, vc_rs, vc_bs, cap, 0, B, W, dtype, stream, AppendAt{len, pos_offset, cap, err});
 }
 
 extern "C" int64_t apertis_attention_decode_splits(int64_t B, int64_t H, int64_t Lk, int64_t D) {
@@ -246,10 +300,11 @@ extern "C" int64_t apertis_attention_decode_workspace_bytes(int64_t B, int64_t H
   return splits == 1 ? 0 : B * H * splits * (D + 2) * (int64_t)sizeof(float);
 }
 
-extern "C" int apertis_attention_decode(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
-                                        const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid,
-                                        int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lk, int64_t H,
-                                        int64_t D, int64_t splits, int dtype, void *stream) {
+// both attentions: Lk by value (len null), or min(*len + 1, cap) read by the kernel with a split count the caller fixes
+static int attention_decode_impl(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs, const void *v_cache,
+                          int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *len, const int64_t *key_valid, int64_t kv_rs,
+                          void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lk, int64_t H, int64_t D, int64_t splits,
+                          int dtype, void *stream) {
   if (!q || !k_cache || !v_cache || !out) return APERTIS_ERR_ARG;
   if (B < 0 || H <= 0 || D <= 0 || cap < 1 || Lk < 1 || Lk > cap || (dtype != APERTIS_F32 && dtype != APERTIS_BF16))
     return APERTIS_ERR_ARG;
@@ -257,7 +312,7 @@ extern "C" int apertis_attention_decode(const void *q, int64_t q_rs, const void 
   const int64_t W = H * D, es = dtype == APERTIS_F32 ? 4 : 2;
   if (q_rs < W || out_rs < W || k_rs < W || v_rs < W || k_bs < cap * k_rs || v_bs < cap * v_rs) return APERTIS_ERR_ARG;
   if (key_valid && kv_rs < Lk) return APERTIS_ERR_ARG;
-  if (splits < 0 || splits > Lk || splits > APERTIS_ATTN_DECODE_MAX_SPLITS) return APERTIS_ERR_ARG;
+  if (splits < (len ? 1 : 0) || (!len && splits > Lk) || splits > APERTIS_ATTN_DECODE_MAX_SPLITS) return APERTIS_ERR_ARG;
   // 16-byte pieces of a head row: every row start on a 16-byte boundary
   const uint64_t bits = (uint64_t)(uintptr_t)q | (uint64_t)(uintptr_t)k_cache | (uint64_t)(uintptr_t)v_cache |
                         (uint64_t)(q_rs * es) | (uint64_t)(k_rs * es) | (uint64_t)(k_bs * es) | (uint64_t)(v_rs * es) |
@@ -271,10 +326,29 @@ extern "C" int apertis_attention_decode(const void *q, int64_t q_rs, const void 
   a.ws_ml = workspace;
   a.ws_o = workspace ? workspace + 2 * B * H * splits : nullptr;
   a.q_rs = q_rs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.kv_rs = kv_rs; a.out_rs = out_rs; a.Lk = Lk;
+  a.len = len;
   a.H = (int)H;
   a.splits = (int)splits;
   a.sl2 = (1.f / sqrtf((float)D)) * LOG2E_F;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == APERTIS_F32) return D == 64 ? launch_decode<float, 64>(a, B, st) : launch_decode<float, 128>(a, B, st);
   return D == 64 ? launch_decode<bf16_t, 64>(a, B, st) : launch_decode<bf16_t, 128>(a, B, st);
+}
+
+extern "C" int apertis_attention_decode(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
+                                        const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid,
+                                        int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lk, int64_t H,
+                                        int64_t D, int64_t splits, int dtype, void *stream) {
+  return attention_decode_impl(q, q_rs, k_cache, k_rs, k_bs, v_cache, v_rs, v_bs, cap, nullptr, key_valid, kv_rs, out, out_rs,
+                               workspace, B, Lk, H, D, splits, dtype, stream);
+}
+
+extern "C" int apertis_attention_decode_at(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
+                                           const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *len,
+                                           const int64_t *key_valid, int64_t kv_rs, void *out, int64_t out_rs, float *workspace,
+                                           int64_t B, int64_t H, int64_t D, int64_t splits, int dtype, void *stream) {
+  if (!len) return APERTIS_ERR_ARG;
+  // (Lk = cap for the shared checks: key_valid must cover every column the kernel can reach, and the kernel clamps to it)
+  return attention_decode_impl(q, q_rs, k_cache, k_rs, k_bs, v_cache, v_rs, v_bs, cap, len, key_valid, kv_rs, out, out_rs, workspace,
+                               B, cap, H, D, splits, dtype, stream);
 }

@@ -809,11 +809,24 @@ class ApertisAttention(nn.Module):
         with room for one more row and the projections' dtype, one query position, inference (no grad, eval, use_cache, no
         attention weights), on the GPU, D 64 or 128, both switches on, the position known on the host, and key 0 of every
         sequence valid (the model's mask says so, _AttnMask: no row without a valid key).  Anything else with a KVCache in
-        flight runs the stock branch on the cache's views and returns plain tensors."""
-        if not (isinstance(past_kv, ops.KVLayer) and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and q.is_cuda
-                and q.shape[1] == 1 and use_c and not output_att and not self.training and not torch.is_grad_enabled()
-                and isinstance(att_mask, _AttnMask) and att_mask.decode_ok and att_mask.pos_host is not None
-                and ops.attention_decode_supported(q, self.num_attention_heads)):
+        flight runs the stock branch on the cache's views and returns plain tensors.
+        A cache whose DEVICE step state is active (att_mask.step_cache; a captured graph replays such a step) brings length,
+        position and key validity in device buffers: no host position, no host length, and the room in the cache and in the
+        rotary table is the kernel's check (ops.kv_append_rope_at).  Its host lengths are stale, so a call the kernels do not
+        take cannot fall back on the views: it raises."""
+        step = isinstance(past_kv, ops.KVLayer) and past_kv.cache.step_active
+        ok = (isinstance(past_kv, ops.KVLayer) and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and q.is_cuda
+              and q.shape[1] == 1 and use_c and not output_att and not self.training and not torch.is_grad_enabled()
+              and isinstance(att_mask, _AttnMask) and att_mask.decode_ok
+              and (att_mask.step_cache is past_kv.cache if step else att_mask.pos_host is not None)
+              and ops.attention_decode_supported(q, self.num_attention_heads))
+        if step:
+            cache = past_kv.cache
+            if not (ok and q.dtype == cache.dtype and q.shape[0] == cache.k[0].shape[0]):
+                raise ops.ApertisHipError("a KVCache whose device step state is active takes single-token inference steps on the "
+                                          "decode kernels only (its host lengths are stale): KVCache.step_state_end() first")
+            return True
+        if not ok:
             return False
         cache, kv = past_kv.cache, att_mask.key_valid
         n = cache.lengths[past_kv.layer]
@@ -823,6 +836,10 @@ class ApertisAttention(nn.Module):
     def _decode_attention(self, q, k, v, att_mask, past_kv):
         cache, layer = past_kv.cache, past_kv.layer
         cos, sin = (self.rope.cos_cached, self.rope.sin_cached) if self.rope is not None else (None, None)
+        if cache.step_active:
+            q = ops.kv_append_rope_at(q, k, v, cache, layer, cos, sin)
+            ctxv = ops.attention_decode_at(q, cache, layer, self.num_attention_heads)
+            return self.out_proj(ctxv.unsqueeze(1)), cache
         q = ops.kv_append_rope(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
         ctxv = ops.attention_decode(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
         return self.out_proj(ctxv.unsqueeze(1)), cache
@@ -1001,13 +1018,15 @@ class _AttnMask:
     padded) for the fused kernels, whether the fused path may run (no query row without a valid key), whether the positions
     are the model's own 0..L-1, and the additive mask of the stock path, built only if that path asks for it.  For a
     single-token step against a KVCache: whether the decode kernels may run (key 0 of every sequence valid, so every row has a
-    valid key) and the step's position as a HOST integer (None when the caller gave position_ids: only a tensor knows them)."""
-    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host")
+    valid key) and the step's position as a HOST integer (None when the caller gave position_ids: only a tensor knows them).
+    `step_cache`: the KVCache whose device step state carries length, position and key validity of this step instead (no
+    host integer, no mask tensor here)."""
+    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host", "step_cache")
 
-    def __init__(self, key_valid, fused_ok, default_pos, make_additive, decode_ok=False, pos_host=None):
+    def __init__(self, key_valid, fused_ok, default_pos, make_additive, decode_ok=False, pos_host=None, step_cache=None):
         self.key_valid, self.fused_ok, self.default_pos = key_valid, fused_ok, default_pos
         self._make, self._additive = make_additive, None
-        self.decode_ok, self.pos_host = decode_ok, pos_host
+        self.decode_ok, self.pos_host, self.step_cache = decode_ok, pos_host, step_cache
 
     def additive(self):
         if self._make is not None:
@@ -1120,11 +1139,15 @@ class ApertisModel(nn.Module):
             return None
         return (1.0 - allow.to(inputs_embeds.dtype)) * torch.finfo(inputs_embeds.dtype).min
 
-    def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos, pos_host=None):
+    def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos, pos_host=None, step_cache=None):
         """The standard_mha layers' mask (_AttnMask).  One host sync when a mask is given, as before: whether anything is
         padded and whether key 0 of every sequence is valid (then every query row has a valid key: right padding, the
         trainer's form, stays on the fused path with no cache, and a step against a KVCache on the decode kernels - a
-        finished sequence of generate() keeps key 0) come back together."""
+        finished sequence of generate() keeps key 0) come back together.  A step on a cache's device step state
+        (`step_cache`) has no mask tensor and NO host sync: the validity is the cache's buffer, and key 0 of every sequence
+        was valid when the state was activated (column 0 does not change afterwards)."""
+        if step_cache is not None:
+            return _AttnMask(None, False, False, None, True, None, step_cache)
         default_pos = default_pos and past_len == 0
         if attention_mask is None:
             return _AttnMask(None, True, default_pos, None, True, pos_host)
@@ -1158,14 +1181,22 @@ class ApertisModel(nn.Module):
         ssm = cfg.attention_type != "standard_mha"
         past_len = 0
         kv_cache = past_key_values if isinstance(past_key_values, ops.KVCache) else None
+        dev_step = kv_cache is not None and kv_cache.step_active
+        if dev_step and (Lq != 1 or position_ids is not None or attention_mask is not None):
+            raise ops.ApertisHipError("a KVCache whose device step state is active takes one token per step, with its own "
+                                      "positions and key validity (no position_ids, no attention_mask)")
         if kv_cache is not None:
-            past_len = kv_cache.length
+            past_len = kv_cache.length            # (stale under a device step state: nothing below may depend on it then)
         elif past_key_values is not None and past_key_values[0] is not None and not ssm:
             past_len = past_key_values[0][0].shape[1]
         pos = position_ids
-        if pos is None:
+        if dev_step:
+            if cfg.position_embedding_type == "absolute" and self.abs_pos_embeddings is not None:
+                raise ops.ApertisHipError("absolute position embeddings need the step's position on the host: not with a "
+                                          "KVCache device step state")
+        elif pos is None:
             pos = torch.arange(past_len, past_len + Lq, device=inputs_embeds.device).unsqueeze(0).expand(B, -1)
-        if cfg.position_embedding_type == "absolute" and self.abs_pos_embeddings is not None:
+        if not dev_step and cfg.position_embedding_type == "absolute" and self.abs_pos_embeddings is not None:
             inputs_embeds = inputs_embeds + self.abs_pos_embeddings(pos)
         x, pos_layers = inputs_embeds, pos
         if cfg.multimodal and pixel_values is not None and past_len == 0:              # core.py:1207-1227
@@ -1183,7 +1214,8 @@ class ApertisModel(nn.Module):
         x = self.embed_dropout(x)
         own_pos = position_ids is None and pos_layers is pos
         mask = None if ssm else self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len, own_pos,
-                                                     past_len if own_pos and kv_cache is not None and x.shape[1] == 1 else None)
+                                                     past_len if own_pos and kv_cache is not None and x.shape[1] == 1 else None,
+                                                     kv_cache if dev_step else None)
 
         all_hs, all_att, all_cache = [], [], []
         lbs, rzs = [], []
@@ -1479,9 +1511,9 @@ class ApertisForCausalLM(nn.Module):
                     break
                 left = max_new_tokens - (tokens.shape[1] - prompt_len)
                 if (past is not None and left >= DECODE_GRAPH_MIN_STEPS
-                        and self._decode_graph_ok(tokens, do_sample, repetition_penalty, sampler)):
+                        and self._decode_graph_ok(tokens, do_sample, repetition_penalty, sampler, past, left, mask)):
                     return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad,
-                                                     sampler=sampler)
+                                                     sampler=sampler, mask=mask)
                 continue
             nxt_logits = out[1][:, -1, :].float()
             if repetition_penalty != 1.0:
@@ -1514,9 +1546,10 @@ class ApertisForCausalLM(nn.Module):
             if alive.max() == 0 and tokens.shape[1] - prompt_len >= min_new_tokens:
                 break
             left = max_new_tokens - (tokens.shape[1] - prompt_len)
-            if past is not None and left >= DECODE_GRAPH_MIN_STEPS and self._decode_graph_ok(tokens, do_sample, repetition_penalty):
+            if (past is not None and left >= DECODE_GRAPH_MIN_STEPS
+                    and self._decode_graph_ok(tokens, do_sample, repetition_penalty, None, past, left, mask)):
                 # the remaining single-token steps as ONE captured HIP graph replayed `left` times (same kernels, same tokens)
-                return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad)
+                return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, mask=mask)
         return tokens
 
     def _kv_cache_ok(self, past, tokens, max_new_tokens):
@@ -1528,23 +1561,50 @@ class ApertisForCausalLM(nn.Module):
                 and isinstance(past[0], tuple) and len(past[0]) == 2 and past[0][0].dim() == 3
                 and ops.attention_decode_supported(past[0][0], cfg.num_attention_heads))
 
-    def _decode_graph_ok(self, tokens, do_sample, repetition_penalty, sampler=None):
+    def _decode_graph_ok(self, tokens, do_sample, repetition_penalty, sampler=None, past=None, left=0, mask=None):
         cfg = self.config
         # (sampling and the penalty replay too when the fused sampler selects the tokens: its kernel reads the step counter
         #  and the occurrence table from device buffers)
-        return (DECODE_GRAPH and tokens.is_cuda and (sampler is not None or (not do_sample and repetition_penalty == 1.0))
-                and not torch.is_grad_enabled() and cfg.attention_type != "standard_mha"
-                and cfg.position_embedding_type != "absolute" and not self.training)
+        ok = (DECODE_GRAPH and tokens.is_cuda and (sampler is not None or (not do_sample and repetition_penalty == 1.0))
+              and not torch.is_grad_enabled() and cfg.position_embedding_type != "absolute" and not self.training)
+        if cfg.attention_type != "standard_mha":
+            return ok
+        return ok and self._mha_graph_ok(tokens, past, left, mask)
 
-    def _generate_graph_tail(self, tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, sampler=None):
+    def _mha_graph_ok(self, tokens, past, left, mask):
+        """Whether the remaining `left` token steps of a standard_mha model replay as a graph (opt-in: ops.ATTN_DECODE_GRAPH):
+        every precondition of ApertisAttention._decode_ok that does not change from step to step, checked ONCE - the past is
+        an ops.KVCache in the dtype the projections produce, with room for every remaining row; the rotary table reaches the
+        last position; key 0 of every sequence is valid (one host read here; column 0 does not change afterwards).  Anything
+        else stays on the eager loop, which raises where it always did when a position runs off the table."""
+        if not (ops.ATTN_DECODE_GRAPH and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and isinstance(past, ops.KVCache)
+                and not past.step_active and len(set(past.lengths)) == 1 and not self.config.output_attentions):
+            return False
+        attn = self.model.layers[0].attention
+        n, (B, cap, _) = past.length, past.k[0].shape
+        want = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else attn.q_proj.weight.dtype
+        if not (n == tokens.shape[1] - 1 and B == tokens.shape[0] and n + left <= cap and past.dtype == want
+                and len(past) == len(self.model.layers) and ops.attention_decode_supported(past.k[0], attn.num_attention_heads)
+                and (attn.rope is None or n + left <= attn.rope.cos_cached.shape[0])):
+            return False
+        return mask is None or (tuple(mask.shape) == (B, n + 1) and bool(mask[:, 0].all()))
+
+    def _generate_graph_tail(self, tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, sampler=None, mask=None):
         """Greedy decoding of `left` more tokens through a captured HIP graph of the single-token step (reference
         core.py:1578-1644: the same forward through the cache, argmax, eos / pad bookkeeping - attention mask and position ids
         do not enter an SSM model's step).  An eager token step is ~2 600 small launches, 18 ms of mostly host time at 44
         layers; the replay is 10 ms (tools/decode_graph_try.py).  Token, cache, alive flags, the step counter and the outputs
         live in static buffers that the graph updates in place; the host looks at the alive flags every 16 steps only.
         With a `sampler` (ops.Sampler: sampling or a repetition penalty) its kernel replaces the argmax and the pad / eos
-        updates; its occurrence table and error word are static buffers too, and its draw counter is the step index."""
+        updates; its occurrence table and error word are static buffers too, and its draw counter is the step index.
+        standard_mha (`past` an ops.KVCache, `mask` the key validity so far): the cache itself is the static state.  Its device
+        step state (length, key validity, error word) is activated here; the step's kernels read row, position and key count
+        from it, on a grid fixed for the whole tail, and the body ends with the validity column of the token just selected
+        (the alive flags it was selected under - the column the eager loop appends) and `dev_len += 1`.  No KV buffer is
+        cloned: the rows the warm-up writes are at or beyond the starting length, and the replay rewrites them."""
         B, dev = tokens.shape[0], tokens.device
+        if isinstance(past, ops.KVCache):
+            return self._generate_graph_tail_kv(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, sampler, mask)
         s_tok = tokens[:, -1:].clone()
         # (contiguous copies: the prefill hands the conv window over as a transposed view, and a cache that is not contiguous
         #  is copied in and out of every token step instead of being updated in place - two launches per layer)
@@ -1607,8 +1667,55 @@ class ApertisForCausalLM(nn.Module):
             for m in ssm_blocks:
                 m._inplace_cache = False
 
+    def _generate_graph_tail_kv(self, tokens, cache, alive, left, prompt_len, min_new_tokens, eos, pad, sampler, mask):
+        B, dev = tokens.shape[0], tokens.device
+        start, cap = cache.length, cache.capacity
+        s_tok = tokens[:, -1:].clone()
+        s_alive = alive.clone()
+        s_idx = torch.zeros(1, dtype=torch.long, device=dev)
+        s_out = torch.full((B, left), pad, dtype=tokens.dtype, device=dev)
+        s_any = torch.ones(left, dtype=alive.dtype, device=dev)
+        # one split count for the whole tail, from the length it ends at (which end to size for)
+        cache.step_state_begin(self.config.num_attention_heads, mask, L_end=start + left)
+        off = tokens.shape[1] - prompt_len
+        s_nxt = torch.empty(B, dtype=torch.long, device=dev)
+
+        def body():
+            out = self(input_ids=s_tok, past_key_values=cache, use_cache=True)
+            # the new token's validity column (row dev_len + 1: the step above filled row dev_len), once per step, with the flags
+            # the token is selected under; the clamp keeps a length that ran away (the error word says so) inside the buffer
+            cache.dev_valid.scatter_(1, (cache.dev_len + 1).clamp_(max=cap - 1).expand(B, 1), s_alive.unsqueeze(1))
+            if sampler is None:
+                nxt = torch.argmax(out[1][:, -1, :].float(), dim=-1)
+                nxt = nxt * s_alive + pad * (1 - s_alive)
+                al = s_alive
+                for e_ in eos:
+                    if e_ is not None:
+                        al = al.masked_fill((nxt == e_) & (al == 1), 0)
+                s_alive.copy_(al)
+            else:
+                sampler.step(out[1][:, -1, :], s_alive, off, step=s_idx, alive_out=s_alive, out=s_nxt)
+                nxt = s_nxt
+            s_out.scatter_(1, s_idx.expand(B, 1), nxt.unsqueeze(1).to(s_out.dtype))
+            s_any.scatter_(0, s_idx, s_alive.max().reshape(1))
+            s_idx.add_(1)
+            s_tok.copy_(nxt.unsqueeze(1))
+            cache.dev_len.add_(1)
+
+        extra = (cache.dev_len, cache.dev_valid, cache.dev_err)
+        if sampler is not None:
+            extra += tuple(t for t in (sampler.counts, sampler.err) if t is not None)
+        kept = 0
+        try:
+            out = self._generate_graph_run(body, tokens, s_tok, [], s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens,
+                                           pad, extra=extra, sampler=sampler, err_word=cache.dev_err)
+            kept = out.shape[1] - tokens.shape[1]
+            return out
+        finally:
+            cache.step_state_end(start + kept)           # (the replay may have run up to 15 steps past the last token kept)
+
     def _generate_graph_run(self, body, tokens, s_tok, s_past, s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens, pad,
-                            extra=(), sampler=None):
+                            extra=(), sampler=None, err_word=None):
         dev = tokens.device
         # warm-up on a side stream (lazy bindings, prepared-weight cache, allocator), then restore the state it advanced
         # (`extra`: further buffers the body updates in place - the sampler's occurrence table and error word)
@@ -1642,7 +1749,13 @@ class ApertisForCausalLM(nn.Module):
         for i in range(left):
             graph.replay()
             if (i + 1) % 16 == 0 or i + 1 == left:
-                flags = s_any[:i + 1].tolist()                         # the only host sync: every 16 steps
+                if err_word is None:
+                    flags = s_any[:i + 1].tolist()                     # the only host sync: every 16 steps
+                else:                                                  # (the KV cache's error word rides in the same read)
+                    *flags, code = torch.cat((s_any[:i + 1], err_word.to(s_any.dtype))).tolist()
+                    if code:
+                        raise ops.ApertisHipError("generate(): a replayed KV-cache step ran past the cache or the rotary table "
+                                                  f"(error word {code}); nothing was written by that step")
                 if sampler is not None:
                     sampler.check()
                 stop = next((j for j, a in enumerate(flags)

@@ -36,7 +36,7 @@ _FORWARDED = {
     "GEMM_DYNAMIC_QUEUE": gemm, "TN_DYNAMIC_QUEUE": gemm, "DENSE_WGRAD_WIDE": gemm, "_splitk_depth": gemm,
     "TRAIN_PREP": prep, "WEIGHT_EPOCH": prep, "_ACTIVE_TRAIN_PREP": prep, "_prep_scope_depth": prep,
     "_TIMER": _base,
-    "ATTN_FUSED": attention, "ATTN_DECODE_FUSED": attention,
+    "ATTN_FUSED": attention, "ATTN_DECODE_FUSED": attention, "ATTN_DECODE_GRAPH": attention,
     "SAMPLE_FUSED": sample, "SAMPLE_UNIFORMS": sample,
 }
 for _m in _MODULES:

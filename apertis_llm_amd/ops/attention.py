@@ -5,6 +5,8 @@ Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autog
 HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip).  Tensors must live on a ROCm
 device.
 """
+import os
+
 import torch
 
 from .. import _lib
@@ -163,6 +165,10 @@ def causal_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=Fal
 # single-token steps of a standard_mha model against a KVCache take the kernels of csrc/attention_decode.hip when this AND
 # ATTN_FUSED are on (ATTN_FUSED = False keeps meaning "stock torch attention everywhere"); off: torch.cat + stock SDPA
 ATTN_DECODE_FUSED = True
+# generate() replays the KV-cache token step of a standard_mha model as one captured HIP graph (model.py:
+# _generate_graph_tail; kv_append_rope_at / attention_decode_at below).  OFF by default (APERTIS_MHA_DECODE_GRAPH=1 turns it
+# on): the eager loop's launch counts are pinned by tests, and flipping the default is a change of its own
+ATTN_DECODE_GRAPH = os.environ.get("APERTIS_MHA_DECODE_GRAPH", "0") == "1"
 
 ATTN_DECODE_MAX_SPLITS = 64          # = APERTIS_ATTN_DECODE_MAX_SPLITS
 
@@ -197,7 +203,16 @@ class KVCache:
     length grows by one - there is no copy of the cache per token, and therefore ONE continuation per cache: a caller that wants
     to branch a generation builds a second cache (from_prefill) for the second branch.  All layers of one step append at the
     same row: each layer keeps its own length, so layer i's append does not move what layer i + 1 sees.  A step that raised
-    half-way leaves the layers at different lengths; such a cache is not used again."""
+    half-way leaves the layers at different lengths; such a cache is not used again.
+
+    DEVICE STEP STATE (opt-in, for a captured graph of the step: a graph freezes host values).  step_state_begin() copies the
+    host state to the device: `dev_len` int64[1] (the rows held; ONE for all layers), `dev_valid` int64 [B, capacity] (the key
+    validity, nonzero = attend; columns the caller's mask does not reach are 1) and `dev_err` int32[1] (set by a step that
+    would have left the cache or the rotary table; such a step writes nothing).  kv_append_rope_at / attention_decode_at
+    read the step from there and never touch `lengths`; whoever drives the steps adds one to `dev_len` after the last layer
+    and writes the validity column of the new token.  WHILE THE DEVICE STATE DRIVES THE STEPS THE HOST `lengths` ARE STALE
+    (and with them the views `cache[i]` hands out); step_state_end() makes them current again - from `dev_len` with one
+    host read, or from the length its caller knows - and the by-value steps may go on.  Still one continuation per cache."""
 
     def __init__(self, k, v, length=0):
         if len(k) != len(v) or not k:
@@ -211,6 +226,8 @@ class KVCache:
             raise ApertisHipError(f"KVCache: length {length} outside [0, {self.capacity}]")
         self.lengths = [int(length)] * len(self.k)
         self._ws = None
+        self.dev_len = self.dev_valid = self.dev_err = None
+        self.step_active, self.step_splits = False, 1
 
     @classmethod
     def empty(cls, layers, B, capacity, W, dtype=torch.float32, device=None):
@@ -248,6 +265,48 @@ class KVCache:
 
     def __iter__(self):
         return (KVLayer(self, i) for i in range(len(self.k)))
+
+    def step_state_begin(self, heads, key_valid=None, L_end=None, splits=None):
+        """Device step state from the host state (class docstring).  key_valid: the mask so far, [B, <= capacity], or None
+        (every key valid).  The split count of attention_decode_at is fixed here, once - apertis_attention_decode_splits at
+        `L_end` keys (the length the steps can reach; default: the capacity) unless `splits` gives it - and the workspace is
+        sized for it, so nothing is allocated by a step."""
+        if len(set(self.lengths)) != 1:
+            raise ApertisHipError(f"KVCache.step_state_begin: the layers disagree on the length ({self.lengths})")
+        B, cap, W = self.k[0].shape
+        dev = self.k[0].device
+        if W % heads:
+            raise ApertisHipError(f"KVCache.step_state_begin: width {W} with {heads} heads")
+        lib = _lib.load()
+        n = int(splits) if splits is not None else int(lib.apertis_attention_decode_splits(
+            max(B, 1), heads, min(max(int(L_end if L_end is not None else cap), 1), cap), W // heads))
+        nbytes = int(lib.apertis_attention_decode_workspace_bytes(B, heads, W // heads, n))
+        if nbytes < 0:
+            raise ApertisHipError(f"KVCache.step_state_begin: {n} splits outside [1, {ATTN_DECODE_MAX_SPLITS}]")
+        self._workspace(nbytes)
+        valid = torch.ones(B, cap, dtype=torch.int64, device=dev)
+        if key_valid is not None:
+            if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] > cap:
+                raise ApertisHipError(f"KVCache.step_state_begin: key_valid {tuple(key_valid.shape)}, expected ({B}, <= {cap})")
+            valid[:, :key_valid.shape[1]] = key_valid.to(torch.int64)
+        self.dev_valid = valid
+        self.dev_len = torch.full((1,), self.lengths[0], dtype=torch.int64, device=dev)
+        self.dev_err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.step_active, self.step_splits = True, n
+
+    def step_state_end(self, length=None):
+        """The host lengths (every layer) from the device state: `length` if the caller knows it (no host read; `dev_len` is
+        set to it too), else one read of `dev_len`.  The by-value steps go on from there; the device buffers stay readable."""
+        if self.dev_len is None:
+            raise ApertisHipError("KVCache.step_state_end: no device step state")
+        if length is None:
+            length = int(self.dev_len.item())
+        else:
+            self.dev_len.fill_(int(length))
+        if not 0 <= length <= self.capacity:
+            raise ApertisHipError(f"KVCache.step_state_end: length {length} outside [0, {self.capacity}]")
+        self.lengths = [int(length)] * len(self.k)
+        self.step_active = False
 
     def _workspace(self, nbytes):
         if nbytes and (self._ws is None or self._ws.numel() * 4 < nbytes):
@@ -349,4 +408,68 @@ def attention_decode(q, cache, layer, heads, key_valid=None, splits=0):
             (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
              ptr(out), W, ptr(ws), B, Lk, heads, D, int(splits), dtype_code(q), stream_ptr()),
             work=4.0 * B * Lk * W, detail=f"{B}x{heads}x{D}", nbytes=nbytes)
+    return out
+
+
+def _step_state(cache, what):
+    if cache.dev_len is None:
+        raise ApertisHipError(f"{what}: the cache has no device step state (KVCache.step_state_begin)")
+
+
+def kv_append_rope_at(q, k, v, cache, layer, cos=None, sin=None, pos_offset=0):
+    """kv_append_rope at the cache's DEVICE length: row `dev_len[0]` of layer `layer`, rotary position `dev_len[0] +
+    pos_offset`, both read by the kernel - no host length, nothing a captured graph would freeze.  The same bits as
+    kv_append_rope for the same row and position.  It moves neither `dev_len` (one step of all layers shares it; the caller
+    adds one after the last) nor the host `lengths`.  A row outside the cache or a position outside the rotary table writes
+    NOTHING and sets `cache.dev_err` - the host cannot check a replayed step, so the kernel does.  Returns the rotated q."""
+    _step_state(cache, "kv_append_rope_at")
+    _require_gpu(q, k, v, cache.k[layer], cos, sin)
+    lib = _lib.load()
+    B, cap, W = cache.k[layer].shape
+    q, q_rs = _row2d(q, W, "kv_append_rope_at q")
+    k, k_rs = _row2d(k, W, "kv_append_rope_at k")
+    v, v_rs = _row2d(v, W, "kv_append_rope_at v")
+    if not (q.shape[0] == k.shape[0] == v.shape[0] == B and q.dtype == k.dtype == v.dtype == cache.dtype):
+        raise ApertisHipError(f"kv_append_rope_at: q/k/v {tuple(q.shape)} {q.dtype} against a cache of [{B}, {cap}, {W}] {cache.dtype}")
+    max_pos = 0
+    if (cos is None) != (sin is None):
+        raise ApertisHipError("kv_append_rope_at: cos and sin come together")
+    if cos is not None:
+        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
+            raise ApertisHipError(f"kv_append_rope_at: cos/sin must be fp32 [max_pos, {W // 2}]")
+        cos, sin, max_pos = cos.contiguous(), sin.contiguous(), cos.shape[0]
+    qo = torch.empty(B, W, device=q.device, dtype=q.dtype)
+    kc, vc = cache.k[layer], cache.v[layer]
+    _launch("apertis_rope_kv_append_at", lib.apertis_rope_kv_append_at,
+            (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(cos), ptr(sin), max_pos, ptr(cache.dev_len), int(pos_offset),
+             ptr(cache.dev_err), ptr(qo), W, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, B, W,
+             dtype_code(q), stream_ptr()), work=5.0 * B * W * q.element_size())
+    return qo
+
+
+def attention_decode_at(q, cache, layer, heads, splits=None):
+    """attention_decode over Lk = min(dev_len[0] + 1, capacity) keys, read by the kernel (after kv_append_rope_at and BEFORE
+    `dev_len` moves: the new token's own key included), under the cache's `dev_valid`.  splits: the FIXED number of pieces,
+    1..ATTN_DECODE_MAX_SPLITS, not bounded by Lk (default: what step_state_begin chose) - grid and workspace depend on it
+    alone, an empty piece contributes nothing.  The same bits as attention_decode(..., splits=n) for the same Lk."""
+    _step_state(cache, "attention_decode_at")
+    _require_gpu(q, cache.k[layer])
+    lib = _lib.load()
+    kc, vc = cache.k[layer], cache.v[layer]
+    B, cap, W = kc.shape
+    q, q_rs = _row2d(q, W, "attention_decode_at q")
+    if not attention_decode_supported(q, heads) or q.shape[0] != B or q.dtype != cache.dtype:
+        raise ApertisHipError(f"attention_decode_at: q {tuple(q.shape)} {q.dtype} with {heads} heads against a cache of "
+                              f"[{B}, {cap}, {W}] {cache.dtype} (D 64 or 128, fp32 or bf16, one dtype)")
+    if q.data_ptr() % 16 or (q_rs * q.element_size()) % 16:
+        q, q_rs = q.clone(memory_format=torch.contiguous_format), W
+    D = W // heads
+    n = cache.step_splits if splits is None else int(splits)
+    ws = cache._workspace(max(int(lib.apertis_attention_decode_workspace_bytes(B, heads, D, n)), 0)) if 1 <= n <= ATTN_DECODE_MAX_SPLITS else None
+    kv = cache.dev_valid
+    out = torch.empty(B, W, device=q.device, dtype=q.dtype)
+    _launch("apertis_attention_decode_at", lib.apertis_attention_decode_at,
+            (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(cache.dev_len),
+             ptr(kv), kv.stride(0), ptr(out), W, ptr(ws), B, heads, D, n, dtype_code(q), stream_ptr()),
+            work=4.0 * B * cap * W, detail=f"{B}x{heads}x{D}", nbytes=2.0 * B * cap * W * q.element_size())
     return out

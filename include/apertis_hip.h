@@ -49,13 +49,14 @@ extern "C" {
  * kernel; measured 15 % SLOWER at the bench shape (profiles/r6_probe_nt2i_vs_nt4r.log), so no caller sets it by default. */
 #define APERTIS_ACT_INTERLEAVED 0x400
 
-/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.10 - apertis_rope_kv_append,
+/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.11 - apertis_rope_kv_append_at,
+ * apertis_attention_decode_at: the KV-cache decode step at a device-held length, for graph replay; 4.10 - apertis_rope_kv_append,
  * apertis_attention_decode, apertis_attention_decode_splits / _workspace_bytes: standard_mha KV-cache decode; 4.9 - apertis_token_counts,
  * apertis_sample_next: generate()'s penalty / temperature / top-k / top-p / draw in one launch; 4.8 - apertis_rope_qk_fwd / _bwd,
  * apertis_attention_fwd / _bwd, apertis_attention_bwd_workspace_bytes: standard_mha; round 6: 4.7 - apertis_cross_entropy_fwd_bwd, apertis_layernorm_combine_bwd; round 5: 4.5 - apertis_scan_lookback_*, apertis_tiny_linear_bwd_pad; round 4: 4.4 - lean scan
  * entry points, apertis_scan_lean_fwd_dt, apertis_grouped_gemm_tn_dense_variant, apertis_weight_prep, apertis_ssm_decode_state_dt).  A host binding should
  * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does). */
-#define APERTIS_ABI_VERSION ((4 << 16) | 10)
+#define APERTIS_ABI_VERSION ((4 << 16) | 11)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
 const char *apertis_arch(void);
@@ -786,7 +787,24 @@ int apertis_attention_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_
  *   workspace     : with splits > 1, apertis_attention_decode_workspace_bytes bytes (fp32 (m, l) and o[D] per piece; 0 bytes
  *                   for splits = 1, -1 for a bad argument): the pieces' partial results, folded in piece order by a second
  *                   launch.  With splits = 1 the one launch writes out and workspace may be NULL.
- * Two plain launches at most, no atomics: the same inputs and split count give the same bits on every run. */
+ * Two plain launches at most, no atomics: the same inputs and split count give the same bits on every run.
+ *
+ * The *_at forms take the step's state from device memory, so that a captured graph of the step can be replayed: `len` points
+ * at ONE int64, the rows the cache holds before the step (shared by all layers of a step; the caller adds one after the last).
+ * They run the same kernels: for the same row, position, Lk and split count the results are the same bits as above.
+ *
+ * apertis_rope_kv_append_at: cache row = *len, rotary position = *len + pos_offset.  The kernel checks both: with *len outside
+ * [0, cap), or (with tables) a position outside [-max_pos, max_pos), it writes NOTHING (q_out, k_cache, v_cache untouched) and
+ * one thread stores 1 to *err (int32, caller-owned and caller-cleared; never written otherwise).  No fault, no HIP error.
+ *   pos_offset    : with tables in (-max_pos - cap, max_pos) - outside it no row of the cache has a position in the table -
+ *                   else APERTIS_ERR_ARG; ignored without tables.  len or err NULL: APERTIS_ERR_ARG.
+ *
+ * apertis_attention_decode_at: Lk = min(*len + 1, cap) (0 for *len < 0), read by the kernel.
+ *   splits        : REQUIRED, 1..APERTIS_ATTN_DECODE_MAX_SPLITS, not bounded by Lk: grid (splits x H x B) and workspace depend on
+ *                   it alone.  Piece s is keys [s*Lk/splits, (s+1)*Lk/splits) as above; an empty piece reads nothing and leaves
+ *                   (m = -inf, l = 0, o = 0), which the fold passes over.
+ *   key_valid     : int64 [B, >= cap] (kv_rs >= cap, else APERTIS_ERR_ARG) or NULL; columns >= Lk are never read.
+ *   Every other argument, check and error code as apertis_attention_decode. */
 #define APERTIS_ATTN_DECODE_MAX_SPLITS 64
 int apertis_rope_kv_append(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
                            const float *cos_cached, const float *sin_cached, int64_t max_pos, int64_t t, void *q_out,
@@ -798,6 +816,15 @@ int apertis_attention_decode(const void *q, int64_t q_rs, const void *k_cache, i
                              int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid, int64_t kv_rs, void *out,
                              int64_t out_rs, float *workspace, int64_t B, int64_t Lk, int64_t H, int64_t D, int64_t splits,
                              int dtype, void *stream);
+int apertis_rope_kv_append_at(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                              const float *cos_cached, const float *sin_cached, int64_t max_pos, const int64_t *len,
+                              int64_t pos_offset, int32_t *err, void *q_out, int64_t q_out_rs, void *k_cache, int64_t kc_rs,
+                              int64_t kc_bs, void *v_cache, int64_t vc_rs, int64_t vc_bs, int64_t cap, int64_t B, int64_t W,
+                              int dtype, void *stream);
+int apertis_attention_decode_at(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs, const void *v_cache,
+                                int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *len, const int64_t *key_valid,
+                                int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t H, int64_t D,
+                                int64_t splits, int dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * generate()'s next-token selection (core.py:1605-1633), one launch per token step, one 1024-thread work-group per row.
