@@ -839,9 +839,9 @@ class ApertisAttention(nn.Module):
         if cache.step_active:
             q = ops.kv_append_rope_at(q, k, v, cache, layer, cos, sin)
             ctxv = ops.attention_decode_at(q, cache, layer, self.num_attention_heads)
-            return self.out_proj(ctxv.unsqueeze(1)), cache
-        q = ops.kv_append_rope(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
-        ctxv = ops.attention_decode(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
+        else:
+            q = ops.kv_append_rope(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
+            ctxv = ops.attention_decode(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
         return self.out_proj(ctxv.unsqueeze(1)), cache
 
     def _heads(self, t):
@@ -1315,6 +1315,18 @@ class ApertisModel(nn.Module):
                                compute_dtype=_compute_dtype(feats))
 
 
+def _select_tokens(logits, alive, eos, pad, drawn=None):
+    """One decode step's selection: the argmax of the fp32 `logits` - or `drawn`, the tokens the stock sampling block drew
+    from them - with `pad` for a finished sequence (alive 0), and the alive flags after the step: a sequence that emits one
+    of the `eos` ids is finished.  Returns (tokens, new alive flags); `alive` itself is not written."""
+    nxt = torch.argmax(logits, dim=-1) if drawn is None else drawn
+    nxt = nxt * alive + pad * (1 - alive)
+    for e_ in eos:
+        if e_ is not None:
+            alive = alive.masked_fill((nxt == e_) & (alive == 1), 0)
+    return nxt, alive
+
+
 class ApertisForCausalLM(nn.Module):
     def __init__(self, config: ApertisConfig):
         super().__init__()
@@ -1365,20 +1377,6 @@ class ApertisForCausalLM(nn.Module):
             self.lm_head.weight.data[:n] = old.weight.data[:n]
         self.config.vocab_size = self.lm_head.out_features
         return self.lm_head
-
-    def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos):
-        """The standard_mha layers' mask (_AttnMask).  One host sync when a mask is given, as before: whether anything is
-        padded and whether key 0 of every sequence is valid (with no cache, then every query row has a valid key: right
-        padding, the trainer's form, stays on the fused path) come back together."""
-        default_pos = default_pos and past_len == 0
-        if attention_mask is None:
-            return _AttnMask(None, True, default_pos, None)
-        valid = attention_mask.bool()
-        all_valid, col0 = torch.stack((valid.all(), valid[:, 0].all())).tolist()
-        if all_valid:
-            return _AttnMask(None, True, default_pos, None)
-        return _AttnMask(attention_mask, bool(col0) and past_len == 0, default_pos,
-                         lambda: self._prepare_decoder_attention_mask(attention_mask, input_shape, inputs_embeds, past_len))
 
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
@@ -1502,54 +1500,45 @@ class ApertisForCausalLM(nn.Module):
                                           top_p=top_p, repetition_penalty=repetition_penalty, eos=eos, pad=pad)
             if sampler is not None:
                 nxt, new_alive = sampler.step(out[1][:, -1, :], alive, tokens.shape[1] - prompt_len)
-                tokens = torch.cat([tokens, nxt.unsqueeze(-1)], dim=-1)
-                mask = torch.cat([mask, alive.unsqueeze(-1).to(mask.dtype)], dim=1)
-                alive = new_alive
+            else:
+                nxt_logits, drawn = out[1][:, -1, :].float(), None
+                if repetition_penalty != 1.0:
+                    for b in range(B):
+                        if alive[b]:
+                            seen = tokens[b][tokens[b] < nxt_logits.shape[-1]]
+                            for t_ in seen.tolist():                    # divides once per occurrence, like the reference
+                                nxt_logits[b, t_] /= repetition_penalty
+                if do_sample:
+                    if temp != 1.0:
+                        nxt_logits = nxt_logits / temp
+                    if top_k > 0:
+                        kth = torch.topk(nxt_logits, top_k).values[:, -1:]
+                        nxt_logits = nxt_logits.masked_fill(nxt_logits < kth, float("-inf"))
+                    if top_p < 1.0:
+                        srt, order = torch.sort(nxt_logits, descending=True)
+                        drop = torch.cumsum(F.softmax(srt, dim=-1), dim=-1) > top_p
+                        drop[..., 1:] = drop[..., :-1].clone()
+                        drop[..., 0] = False
+                        nxt_logits = nxt_logits.masked_fill(torch.zeros_like(drop).scatter_(-1, order, drop), float("-inf"))
+                    drawn = torch.multinomial(F.softmax(nxt_logits, dim=-1), 1).squeeze(1)
+                nxt, new_alive = _select_tokens(nxt_logits, alive, eos, pad, drawn)
+            tokens = torch.cat([tokens, nxt.unsqueeze(-1)], dim=-1)
+            mask = torch.cat([mask, alive.unsqueeze(-1).to(mask.dtype)], dim=1)     # (the flags the token was selected under)
+            alive = new_alive
+            if sampler is None:
+                stop = bool(alive.max() == 0)
+            else:                                                       # (the sampler's error word rides in the step's one read)
                 any_alive, code = torch.cat((alive.max().reshape(1), sampler.err.to(alive.dtype))).tolist()
                 sampler.check(code)
-                if any_alive == 0 and tokens.shape[1] - prompt_len >= min_new_tokens:
-                    break
-                left = max_new_tokens - (tokens.shape[1] - prompt_len)
-                if (past is not None and left >= DECODE_GRAPH_MIN_STEPS
-                        and self._decode_graph_ok(tokens, do_sample, repetition_penalty, sampler, past, left, mask)):
-                    return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad,
-                                                     sampler=sampler, mask=mask)
-                continue
-            nxt_logits = out[1][:, -1, :].float()
-            if repetition_penalty != 1.0:
-                for b in range(B):
-                    if alive[b]:
-                        seen = tokens[b][tokens[b] < nxt_logits.shape[-1]]
-                        for t_ in seen.tolist():                    # divides once per occurrence, like the reference
-                            nxt_logits[b, t_] /= repetition_penalty
-            if do_sample:
-                if temp != 1.0:
-                    nxt_logits = nxt_logits / temp
-                if top_k > 0:
-                    kth = torch.topk(nxt_logits, top_k).values[:, -1:]
-                    nxt_logits = nxt_logits.masked_fill(nxt_logits < kth, float("-inf"))
-                if top_p < 1.0:
-                    srt, order = torch.sort(nxt_logits, descending=True)
-                    drop = torch.cumsum(F.softmax(srt, dim=-1), dim=-1) > top_p
-                    drop[..., 1:] = drop[..., :-1].clone()
-                    drop[..., 0] = False
-                    nxt_logits = nxt_logits.masked_fill(torch.zeros_like(drop).scatter_(-1, order, drop), float("-inf"))
-                nxt = torch.multinomial(F.softmax(nxt_logits, dim=-1), 1).squeeze(1)
-            else:
-                nxt = torch.argmax(nxt_logits, dim=-1)
-            nxt = nxt * alive + pad * (1 - alive)
-            tokens = torch.cat([tokens, nxt.unsqueeze(-1)], dim=-1)
-            mask = torch.cat([mask, alive.unsqueeze(-1).to(mask.dtype)], dim=1)
-            for e_ in eos:
-                if e_ is not None:
-                    alive = alive.masked_fill((nxt == e_) & (alive == 1), 0)
-            if alive.max() == 0 and tokens.shape[1] - prompt_len >= min_new_tokens:
+                stop = any_alive == 0
+            if stop and tokens.shape[1] - prompt_len >= min_new_tokens:
                 break
             left = max_new_tokens - (tokens.shape[1] - prompt_len)
             if (past is not None and left >= DECODE_GRAPH_MIN_STEPS
-                    and self._decode_graph_ok(tokens, do_sample, repetition_penalty, None, past, left, mask)):
+                    and self._decode_graph_ok(tokens, do_sample, repetition_penalty, sampler, past, left, mask)):
                 # the remaining single-token steps as ONE captured HIP graph replayed `left` times (same kernels, same tokens)
-                return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, mask=mask)
+                return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad,
+                                                 sampler=sampler, mask=mask)
         return tokens
 
     def _kv_cache_ok(self, past, tokens, max_new_tokens):
@@ -1590,8 +1579,8 @@ class ApertisForCausalLM(nn.Module):
         return mask is None or (tuple(mask.shape) == (B, n + 1) and bool(mask[:, 0].all()))
 
     def _generate_graph_tail(self, tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, sampler=None, mask=None):
-        """Greedy decoding of `left` more tokens through a captured HIP graph of the single-token step (reference
-        core.py:1578-1644: the same forward through the cache, argmax, eos / pad bookkeeping - attention mask and position ids
+        """Decoding of `left` more tokens through a captured HIP graph of the single-token step (reference core.py:1578-1644:
+        the same forward through the cache, then the eager loop's selection, _select_tokens - attention mask and position ids
         do not enter an SSM model's step).  An eager token step is ~2 600 small launches, 18 ms of mostly host time at 44
         layers; the replay is 10 ms (tools/decode_graph_try.py).  Token, cache, alive flags, the step counter and the outputs
         live in static buffers that the graph updates in place; the host looks at the alive flags every 16 steps only.
@@ -1599,99 +1588,54 @@ class ApertisForCausalLM(nn.Module):
         updates; its occurrence table and error word are static buffers too, and its draw counter is the step index.
         standard_mha (`past` an ops.KVCache, `mask` the key validity so far): the cache itself is the static state.  Its device
         step state (length, key validity, error word) is activated here; the step's kernels read row, position and key count
-        from it, on a grid fixed for the whole tail, and the body ends with the validity column of the token just selected
-        (the alive flags it was selected under - the column the eager loop appends) and `dev_len += 1`.  No KV buffer is
-        cloned: the rows the warm-up writes are at or beyond the starting length, and the replay rewrites them."""
+        from it, on a grid fixed for the whole tail; after the forward the body writes the validity column of the token about
+        to be selected (the alive flags it is selected under - the column the eager loop appends) and ends with
+        `dev_len += 1`.  No KV buffer is cloned: the rows the warm-up writes are at or beyond the starting length, and the
+        replay rewrites them."""
         B, dev = tokens.shape[0], tokens.device
-        if isinstance(past, ops.KVCache):
-            return self._generate_graph_tail_kv(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, sampler, mask)
+        cache = past if isinstance(past, ops.KVCache) else None
         s_tok = tokens[:, -1:].clone()
-        # (contiguous copies: the prefill hands the conv window over as a transposed view, and a cache that is not contiguous
-        #  is copied in and out of every token step instead of being updated in place - two launches per layer)
-        s_past = [(c.clone(memory_format=torch.contiguous_format), st.clone(memory_format=torch.contiguous_format)) for (c, st) in past]
-        if (DECODE_PREPASS and len(s_past) > 0 and all(c.dim() == 3 and st.dim() == 3 and st.dtype == torch.float32 and
-                                                       c.shape == s_past[0][0].shape and st.shape == s_past[0][1].shape
-                                                       and c.dtype == s_past[0][0].dtype for c, st in s_past)):
-            # one tensor per kind, the per-layer caches as views: the cache-only half of every layer's step runs at once
-            conv_all = torch.stack([c for c, _ in s_past]).contiguous()
-            state_all = torch.stack([st.reshape(st.shape[0], -1) for _, st in s_past]).contiguous()
-            s_past = _StackedPast(conv_all, state_all, s_past[0][1].shape[1], s_past[0][1].shape[2])
         s_alive = alive.clone()
         s_idx = torch.zeros(1, dtype=torch.long, device=dev)
         s_out = torch.full((B, left), pad, dtype=tokens.dtype, device=dev)
         s_any = torch.ones(left, dtype=alive.dtype, device=dev)          # max over the batch of `alive` after each step
-
-        def copy_back(out):
-            for (sc, ss), (nc, ns) in zip(s_past, out[4]):
-                if nc.data_ptr() != sc.data_ptr():     # (both updated in place by the step: _inplace_cache)
-                    sc.copy_(nc)
-                if ns.data_ptr() != ss.data_ptr():
-                    ss.copy_(ns)
-
-        if sampler is None:
-            def body():
-                out = self(input_ids=s_tok, past_key_values=s_past, use_cache=True)
-                nxt = torch.argmax(out[1][:, -1, :].float(), dim=-1)
-                nxt = nxt * s_alive + pad * (1 - s_alive)
-                s_out.scatter_(1, s_idx.expand(B, 1), nxt.unsqueeze(1).to(s_out.dtype))
-                al = s_alive
-                for e_ in eos:
-                    if e_ is not None:
-                        al = al.masked_fill((nxt == e_) & (al == 1), 0)
-                s_alive.copy_(al)
-                s_any.scatter_(0, s_idx, al.max().reshape(1))
-                s_idx.add_(1)
-                s_tok.copy_(nxt.unsqueeze(1))
-                copy_back(out)
-            extra = ()
-        else:
-            s_nxt = torch.empty(B, dtype=torch.long, device=dev)
-            off = tokens.shape[1] - prompt_len                  # (steps already decoded: the draw counter goes on from there)
-
-            def body():
-                out = self(input_ids=s_tok, past_key_values=s_past, use_cache=True)
-                sampler.step(out[1][:, -1, :], s_alive, off, step=s_idx, alive_out=s_alive, out=s_nxt)
-                s_out.scatter_(1, s_idx.expand(B, 1), s_nxt.unsqueeze(1).to(s_out.dtype))
-                s_any.scatter_(0, s_idx, s_alive.max().reshape(1))
-                s_idx.add_(1)
-                s_tok.copy_(s_nxt.unsqueeze(1))
-                copy_back(out)
-            extra = tuple(t for t in (sampler.counts, sampler.err) if t is not None)
-        ssm_blocks = [m for m in self.modules() if isinstance(m, SelectiveLinearAttention)]
-        for m in ssm_blocks:
-            m._inplace_cache = True
-        try:
-            return self._generate_graph_run(body, tokens, s_tok, s_past, s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens, pad,
-                                            extra=extra, sampler=sampler)
-        finally:
+        # what the body updates in place: saved before the warm-up, restored after it and after the capture
+        state = [s_tok, s_alive]
+        s_nxt = torch.empty(B, dtype=torch.long, device=dev)            # (the sampler's tokens)
+        off = tokens.shape[1] - prompt_len                      # (steps already decoded: the draw counter goes on from there)
+        if sampler is not None:
+            state += [t for t in (sampler.counts, sampler.err) if t is not None]
+        ssm_blocks, start, cap, err_word = [], 0, 0, None
+        if cache is None:
+            # (contiguous copies: the prefill hands the conv window over as a transposed view, and a cache that is not contiguous
+            #  is copied in and out of every token step instead of being updated in place - two launches per layer)
+            s_past = [(c.clone(memory_format=torch.contiguous_format), st.clone(memory_format=torch.contiguous_format)) for (c, st) in past]
+            if (DECODE_PREPASS and len(s_past) > 0 and all(c.dim() == 3 and st.dim() == 3 and st.dtype == torch.float32 and
+                                                           c.shape == s_past[0][0].shape and st.shape == s_past[0][1].shape
+                                                           and c.dtype == s_past[0][0].dtype for c, st in s_past)):
+                # one tensor per kind, the per-layer caches as views: the cache-only half of every layer's step runs at once
+                conv_all = torch.stack([c for c, _ in s_past]).contiguous()
+                state_all = torch.stack([st.reshape(st.shape[0], -1) for _, st in s_past]).contiguous()
+                s_past = _StackedPast(conv_all, state_all, s_past[0][1].shape[1], s_past[0][1].shape[2])
+            state += [t for pair in s_past for t in pair]
+            ssm_blocks = [m for m in self.modules() if isinstance(m, SelectiveLinearAttention)]
             for m in ssm_blocks:
-                m._inplace_cache = False
-
-    def _generate_graph_tail_kv(self, tokens, cache, alive, left, prompt_len, min_new_tokens, eos, pad, sampler, mask):
-        B, dev = tokens.shape[0], tokens.device
-        start, cap = cache.length, cache.capacity
-        s_tok = tokens[:, -1:].clone()
-        s_alive = alive.clone()
-        s_idx = torch.zeros(1, dtype=torch.long, device=dev)
-        s_out = torch.full((B, left), pad, dtype=tokens.dtype, device=dev)
-        s_any = torch.ones(left, dtype=alive.dtype, device=dev)
-        # one split count for the whole tail, from the length it ends at (DESIGN.md section 3: which end to size for)
-        cache.step_state_begin(self.config.num_attention_heads, mask, L_end=start + left)
-        off = tokens.shape[1] - prompt_len
-        s_nxt = torch.empty(B, dtype=torch.long, device=dev)
+                m._inplace_cache = True
+        else:
+            s_past, start, cap = cache, cache.length, cache.capacity
+            # one split count for the whole tail, from the length it ends at (DESIGN.md section 3: which end to size for)
+            cache.step_state_begin(self.config.num_attention_heads, mask, L_end=start + left)
+            state += [cache.dev_len, cache.dev_valid, cache.dev_err]
+            err_word = cache.dev_err
 
         def body():
-            out = self(input_ids=s_tok, past_key_values=cache, use_cache=True)
-            # the new token's validity column (row dev_len + 1: the step above filled row dev_len), once per step, with the flags
-            # the token is selected under; the clamp keeps a length that ran away (the error word says so) inside the buffer
-            cache.dev_valid.scatter_(1, (cache.dev_len + 1).clamp_(max=cap - 1).expand(B, 1), s_alive.unsqueeze(1))
+            out = self(input_ids=s_tok, past_key_values=s_past, use_cache=True)
+            if cache is not None:
+                # the new token's validity column (row dev_len + 1: the step above filled row dev_len), once per step, with the
+                # flags the token is selected under; the clamp keeps a length that ran away (the error word says so) inside the buffer
+                cache.dev_valid.scatter_(1, (cache.dev_len + 1).clamp_(max=cap - 1).expand(B, 1), s_alive.unsqueeze(1))
             if sampler is None:
-                nxt = torch.argmax(out[1][:, -1, :].float(), dim=-1)
-                nxt = nxt * s_alive + pad * (1 - s_alive)
-                al = s_alive
-                for e_ in eos:
-                    if e_ is not None:
-                        al = al.masked_fill((nxt == e_) & (al == 1), 0)
+                nxt, al = _select_tokens(out[1][:, -1, :].float(), s_alive, eos, pad)
                 s_alive.copy_(al)
             else:
                 sampler.step(out[1][:, -1, :], s_alive, off, step=s_idx, alive_out=s_alive, out=s_nxt)
@@ -1700,27 +1644,35 @@ class ApertisForCausalLM(nn.Module):
             s_any.scatter_(0, s_idx, s_alive.max().reshape(1))
             s_idx.add_(1)
             s_tok.copy_(nxt.unsqueeze(1))
-            cache.dev_len.add_(1)
+            if cache is not None:
+                cache.dev_len.add_(1)
+            else:
+                for (sc, ss), (nc, ns) in zip(s_past, out[4]):
+                    if nc.data_ptr() != sc.data_ptr():     # (both updated in place by the step: _inplace_cache)
+                        sc.copy_(nc)
+                    if ns.data_ptr() != ss.data_ptr():
+                        ss.copy_(ns)
 
-        extra = (cache.dev_len, cache.dev_valid, cache.dev_err)
-        if sampler is not None:
-            extra += tuple(t for t in (sampler.counts, sampler.err) if t is not None)
         kept = 0
         try:
-            out = self._generate_graph_run(body, tokens, s_tok, [], s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens,
-                                           pad, extra=extra, sampler=sampler, err_word=cache.dev_err)
+            out = self._generate_graph_run(body, state, (s_idx, s_out, s_any), tokens, left, prompt_len, min_new_tokens, pad,
+                                           sampler=sampler, err_word=err_word)
             kept = out.shape[1] - tokens.shape[1]
             return out
         finally:
-            cache.step_state_end(start + kept)           # (the replay may have run up to 15 steps past the last token kept)
+            for m in ssm_blocks:
+                m._inplace_cache = False
+            if cache is not None:
+                cache.step_state_end(start + kept)       # (the replay may have run up to 15 steps past the last token kept)
 
-    def _generate_graph_run(self, body, tokens, s_tok, s_past, s_alive, s_idx, s_out, s_any, left, prompt_len, min_new_tokens, pad,
-                            extra=(), sampler=None, err_word=None):
+    def _generate_graph_run(self, body, state, outputs, tokens, left, prompt_len, min_new_tokens, pad, sampler=None, err_word=None):
+        """Warm-up, capture and replay of `body` for `left` steps.  `state`: the tensors the body updates in place (token, alive
+        flags, caches, the sampler's occurrence table and error word, a KVCache's step state); `outputs`: the step counter,
+        the tokens and the per-step alive maximum, which start from zero / pad / one."""
         dev = tokens.device
+        s_idx, s_out, s_any = outputs
         # warm-up on a side stream (lazy bindings, prepared-weight cache, allocator), then restore the state it advanced
-        # (`extra`: further buffers the body updates in place - the sampler's occurrence table and error word)
-        keep = (s_tok.clone(), [(c.clone(), st.clone()) for (c, st) in s_past], s_alive.clone())
-        keep_extra = [t.clone() for t in extra]
+        keep = [t.clone() for t in state]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -1729,12 +1681,7 @@ class ApertisForCausalLM(nn.Module):
         torch.cuda.current_stream(dev).wait_stream(side)
 
         def restore():
-            s_tok.copy_(keep[0])
-            for (sc, ss), (c, st) in zip(s_past, keep[1]):
-                sc.copy_(c)
-                ss.copy_(st)
-            s_alive.copy_(keep[2])
-            for t, k in zip(extra, keep_extra):
+            for t, k in zip(state, keep):
                 t.copy_(k)
             s_idx.zero_()
             s_out.fill_(pad)

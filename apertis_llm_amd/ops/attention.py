@@ -325,6 +325,44 @@ def _row2d(t, W, what):
     return t, (t.stride(0) if t.shape[0] > 1 else W)
 
 
+def _append_operands(what, q, k, v, cache, layer, cos, sin):
+    """What both appends hand to the library: q, k, v as rows with their strides, the rotary table and its length (0: no
+    rotation) and the output for the rotated q."""
+    B, cap, W = cache.k[layer].shape
+    q, q_rs = _row2d(q, W, f"{what} q")
+    k, k_rs = _row2d(k, W, f"{what} k")
+    v, v_rs = _row2d(v, W, f"{what} v")
+    if not (q.shape[0] == k.shape[0] == v.shape[0] == B and q.dtype == k.dtype == v.dtype == cache.dtype):
+        raise ApertisHipError(f"{what}: q/k/v {tuple(q.shape)} {q.dtype} against a cache of [{B}, {cap}, {W}] {cache.dtype}")
+    max_pos = 0
+    if (cos is None) != (sin is None):
+        raise ApertisHipError(f"{what}: cos and sin come together")
+    if cos is not None:
+        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
+            raise ApertisHipError(f"{what}: cos/sin must be fp32 [max_pos, {W // 2}]")
+        cos, sin, max_pos = cos.contiguous(), sin.contiguous(), cos.shape[0]
+    qo = torch.empty(B, W, device=q.device, dtype=q.dtype)
+    return (q, q_rs), (k, k_rs), (v, v_rs), cos, sin, max_pos, qo
+
+
+def _decode_operands(what, lib, q, cache, layer, heads, splits):
+    """What both attentions hand to the library: the query rows, 16-byte aligned, with their stride, D, the cache's
+    workspace for `splits` pieces (a count, or a function of D asked once q has passed its check; None where the library
+    refuses the count) and the output."""
+    B, cap, W = cache.k[layer].shape
+    q, q_rs = _row2d(q, W, f"{what} q")
+    if not attention_decode_supported(q, heads) or q.shape[0] != B or q.dtype != cache.dtype:
+        raise ApertisHipError(f"{what}: q {tuple(q.shape)} {q.dtype} with {heads} heads against a cache of "
+                              f"[{B}, {cap}, {W}] {cache.dtype} (D 64 or 128, fp32 or bf16, one dtype)")
+    if q.data_ptr() % 16 or (q_rs * q.element_size()) % 16:
+        q, q_rs = q.clone(memory_format=torch.contiguous_format), W
+    D, ws = W // heads, None
+    n = splits(D) if callable(splits) else splits
+    if 1 <= n <= ATTN_DECODE_MAX_SPLITS:
+        ws = cache._workspace(max(int(lib.apertis_attention_decode_workspace_bytes(B, heads, D, n)), 0))
+    return q, q_rs, D, ws, torch.empty(B, W, device=q.device, dtype=q.dtype)
+
+
 def kv_append_rope(q, k, v, cache, layer, t=None, cos=None, sin=None):
     """One token of every sequence into layer `layer` of `cache`, in ONE launch: q and k ([B, W] or [B, 1, W]) are rotated at
     rotary position `t` (a host integer; default: the row appended to) with the module's fp32 cos_cached / sin_cached - the
@@ -337,22 +375,10 @@ def kv_append_rope(q, k, v, cache, layer, t=None, cos=None, sin=None):
     row = cache.lengths[layer]
     if row >= cap:
         raise ApertisHipError(f"kv_append_rope: the cache is full ({cap} rows)")
-    q, q_rs = _row2d(q, W, "kv_append_rope q")
-    k, k_rs = _row2d(k, W, "kv_append_rope k")
-    v, v_rs = _row2d(v, W, "kv_append_rope v")
-    if not (q.shape[0] == k.shape[0] == v.shape[0] == B and q.dtype == k.dtype == v.dtype == cache.dtype):
-        raise ApertisHipError(f"kv_append_rope: q/k/v {tuple(q.shape)} {q.dtype} against a cache of [{B}, {cap}, {W}] {cache.dtype}")
-    max_pos = 0
+    (q, q_rs), (k, k_rs), (v, v_rs), cos, sin, max_pos, qo = _append_operands("kv_append_rope", q, k, v, cache, layer, cos, sin)
     t = row if t is None else int(t)
-    if (cos is None) != (sin is None):
-        raise ApertisHipError("kv_append_rope: cos and sin come together")
-    if cos is not None:
-        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
-            raise ApertisHipError(f"kv_append_rope: cos/sin must be fp32 [max_pos, {W // 2}]")
-        cos, sin, max_pos = cos.contiguous(), sin.contiguous(), cos.shape[0]
-        if not -max_pos <= t < max_pos:
-            raise IndexError(f"position {t} outside the rotary table of {max_pos} positions")
-    qo = torch.empty(B, W, device=q.device, dtype=q.dtype)
+    if cos is not None and not -max_pos <= t < max_pos:
+        raise IndexError(f"position {t} outside the rotary table of {max_pos} positions")
     kc, vc = cache.k[layer], cache.v[layer]
     _launch("apertis_rope_kv_append", lib.apertis_rope_kv_append,
             (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(cos), ptr(sin), max_pos, t, ptr(qo), W, ptr(kc), kc.stride(1),
@@ -386,13 +412,8 @@ def attention_decode(q, cache, layer, heads, key_valid=None, splits=0):
     kc, vc = cache.k[layer], cache.v[layer]
     B, cap, W = kc.shape
     Lk = cache.lengths[layer]
-    q, q_rs = _row2d(q, W, "attention_decode q")
-    if not attention_decode_supported(q, heads) or q.shape[0] != B or q.dtype != cache.dtype:
-        raise ApertisHipError(f"attention_decode: q {tuple(q.shape)} {q.dtype} with {heads} heads against a cache of "
-                              f"[{B}, {cap}, {W}] {cache.dtype} (D 64 or 128, fp32 or bf16, one dtype)")
-    if q.data_ptr() % 16 or (q_rs * q.element_size()) % 16:
-        q, q_rs = q.clone(memory_format=torch.contiguous_format), W
-    D = W // heads
+    n = int(splits) if splits else lambda D: int(lib.apertis_attention_decode_splits(B, heads, max(Lk, 1), D)) if B else 1
+    q, q_rs, D, ws, out = _decode_operands("attention_decode", lib, q, cache, layer, heads, n)
     kv_rs = 0
     if key_valid is not None:
         if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < Lk:
@@ -400,9 +421,6 @@ def attention_decode(q, cache, layer, heads, key_valid=None, splits=0):
         if key_valid.dtype != torch.int64 or key_valid.stride(1) != 1:
             key_valid = key_valid.to(torch.int64).contiguous()
         kv_rs = key_valid.stride(0) if B > 1 else key_valid.shape[1]
-    n = int(splits) if splits else int(lib.apertis_attention_decode_splits(B, heads, max(Lk, 1), D)) if B else 1
-    ws = cache._workspace(max(int(lib.apertis_attention_decode_workspace_bytes(B, heads, D, n)), 0)) if 1 <= n <= ATTN_DECODE_MAX_SPLITS else None
-    out = torch.empty(B, W, device=q.device, dtype=q.dtype)
     nbytes = 2.0 * B * Lk * W * q.element_size()
     _launch("apertis_attention_decode", lib.apertis_attention_decode,
             (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
@@ -426,19 +444,7 @@ def kv_append_rope_at(q, k, v, cache, layer, cos=None, sin=None, pos_offset=0):
     _require_gpu(q, k, v, cache.k[layer], cos, sin)
     lib = _lib.load()
     B, cap, W = cache.k[layer].shape
-    q, q_rs = _row2d(q, W, "kv_append_rope_at q")
-    k, k_rs = _row2d(k, W, "kv_append_rope_at k")
-    v, v_rs = _row2d(v, W, "kv_append_rope_at v")
-    if not (q.shape[0] == k.shape[0] == v.shape[0] == B and q.dtype == k.dtype == v.dtype == cache.dtype):
-        raise ApertisHipError(f"kv_append_rope_at: q/k/v {tuple(q.shape)} {q.dtype} against a cache of [{B}, {cap}, {W}] {cache.dtype}")
-    max_pos = 0
-    if (cos is None) != (sin is None):
-        raise ApertisHipError("kv_append_rope_at: cos and sin come together")
-    if cos is not None:
-        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
-            raise ApertisHipError(f"kv_append_rope_at: cos/sin must be fp32 [max_pos, {W // 2}]")
-        cos, sin, max_pos = cos.contiguous(), sin.contiguous(), cos.shape[0]
-    qo = torch.empty(B, W, device=q.device, dtype=q.dtype)
+    (q, q_rs), (k, k_rs), (v, v_rs), cos, sin, max_pos, qo = _append_operands("kv_append_rope_at", q, k, v, cache, layer, cos, sin)
     kc, vc = cache.k[layer], cache.v[layer]
     _launch("apertis_rope_kv_append_at", lib.apertis_rope_kv_append_at,
             (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(cos), ptr(sin), max_pos, ptr(cache.dev_len), int(pos_offset),
@@ -457,17 +463,9 @@ def attention_decode_at(q, cache, layer, heads, splits=None):
     lib = _lib.load()
     kc, vc = cache.k[layer], cache.v[layer]
     B, cap, W = kc.shape
-    q, q_rs = _row2d(q, W, "attention_decode_at q")
-    if not attention_decode_supported(q, heads) or q.shape[0] != B or q.dtype != cache.dtype:
-        raise ApertisHipError(f"attention_decode_at: q {tuple(q.shape)} {q.dtype} with {heads} heads against a cache of "
-                              f"[{B}, {cap}, {W}] {cache.dtype} (D 64 or 128, fp32 or bf16, one dtype)")
-    if q.data_ptr() % 16 or (q_rs * q.element_size()) % 16:
-        q, q_rs = q.clone(memory_format=torch.contiguous_format), W
-    D = W // heads
     n = cache.step_splits if splits is None else int(splits)
-    ws = cache._workspace(max(int(lib.apertis_attention_decode_workspace_bytes(B, heads, D, n)), 0)) if 1 <= n <= ATTN_DECODE_MAX_SPLITS else None
+    q, q_rs, D, ws, out = _decode_operands("attention_decode_at", lib, q, cache, layer, heads, n)
     kv = cache.dev_valid
-    out = torch.empty(B, W, device=q.device, dtype=q.dtype)
     _launch("apertis_attention_decode_at", lib.apertis_attention_decode_at,
             (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(cache.dev_len),
              ptr(kv), kv.stride(0), ptr(out), W, ptr(ws), B, heads, D, n, dtype_code(q), stream_ptr()),

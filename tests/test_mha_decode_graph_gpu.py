@@ -506,6 +506,47 @@ def test_generate_bf16_autocast_through_the_graph_tail(dev, ops, monkeypatch):
     assert torch.equal(res[0], res[1])
 
 
+def test_an_exception_in_the_graph_tail_ends_the_step_state(dev, ops, monkeypatch):
+    """A Python exception out of the graph tail's first warm-up step (the second forward of the generate(): the prefill is the
+    first) propagates, and the tail's clean-up has run: the cache's device step state is ended at the length the tail
+    started from, with a clean error word, and the next generate() on the model gives the switch-off tokens."""
+    import apertis_llm_amd as A
+    NEW, P = 40, 12
+    torch.manual_seed(0)
+    model = _model(A, dev)
+    ids = torch.randint(4, 512, (2, P), device=dev)
+    kw = dict(input_ids=ids, max_new_tokens=NEW, do_sample=False, eos_token_id=-1, pad_token_id=0)
+    ops.ATTN_DECODE_GRAPH = False
+    off = model.generate(**kw)
+    spies = _Spies(monkeypatch, ops)
+    ops.ATTN_DECODE_GRAPH = True
+    fwd, n_fwd, tails = model.forward, [], []
+    tail = A.model.ApertisForCausalLM._generate_graph_tail
+
+    def tail_spy(self, *a, **k):
+        tails.append(1)
+        return tail(self, *a, **k)
+    monkeypatch.setattr(A.model.ApertisForCausalLM, "_generate_graph_tail", tail_spy)
+
+    def second_call_raises(*a, **k):
+        n_fwd.append(1)
+        if len(n_fwd) == 2:
+            raise RuntimeError("stop")
+        return fwd(*a, **k)
+    model.forward = second_call_raises
+    try:
+        with pytest.raises(RuntimeError, match="^stop$"):
+            model.generate(**kw)
+    finally:
+        del model.forward
+    assert len(n_fwd) == 2 and len(tails) == 1 and spies.replays == 0
+    cache, = spies.caches
+    assert cache.dev_len is not None and cache.step_active is False       # (the tail began the step state, and ended it)
+    assert cache.lengths == [P] * 2 and int(cache.dev_err) == 0
+    spies.reset()
+    assert torch.equal(model.generate(**kw), off) and spies.replays >= 32
+
+
 def test_active_step_state_refuses_what_the_kernels_do_not_take(dev, ops):
     """While the device state drives the steps the host lengths are stale: a forward the decode kernels do not take cannot
     fall back on the cache's views, so it raises instead of computing on them."""

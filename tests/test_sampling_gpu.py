@@ -343,6 +343,43 @@ def test_sampled_tokens_lie_in_their_kept_sets(dev, monkeypatch):
                 assert bool(keep[b, int(toks[b, prompt.shape[1] + s])]), (graph, s, b)
 
 
+def test_an_exception_in_the_graph_tail_leaves_the_model_as_it_was(dev, monkeypatch):
+    """A Python exception out of the graph tail's first warm-up step (the second forward of the generate(): the prefill is the
+    first) propagates, and the tail's clean-up has run: no SSM block is left updating its cache in place, and the next
+    generate() gives the eager loop's tokens."""
+    from apertis_llm_amd import model as M
+    model = _model(dev)
+    prompt = torch.randint(4, 97, (2, 8), device=dev)
+    kw = dict(input_ids=prompt, max_new_tokens=40, do_sample=False, use_cache=True, eos_token_id=-1)
+    monkeypatch.setattr(M, "DECODE_GRAPH", False)
+    eager = model.generate(**kw)
+    monkeypatch.setattr(M, "DECODE_GRAPH", True)
+    seen = {"tail": 0, "fwd": 0}
+    tail = M.ApertisForCausalLM._generate_graph_tail
+
+    def tail_spy(self, *a, **k):
+        seen["tail"] += 1
+        return tail(self, *a, **k)
+    monkeypatch.setattr(M.ApertisForCausalLM, "_generate_graph_tail", tail_spy)
+    fwd = model.forward
+
+    def second_call_raises(*a, **k):
+        seen["fwd"] += 1
+        if seen["fwd"] == 2:
+            raise RuntimeError("stop")
+        return fwd(*a, **k)
+    model.forward = second_call_raises
+    try:
+        with pytest.raises(RuntimeError, match="^stop$"):
+            model.generate(**kw)
+    finally:
+        del model.forward
+    assert seen == {"tail": 1, "fwd": 2}
+    blocks = [m for m in model.modules() if isinstance(m, M.SelectiveLinearAttention)]
+    assert len(blocks) == 2 and all(m._inplace_cache is False for m in blocks)
+    assert torch.equal(model.generate(**kw), eager) and seen["tail"] == 2
+
+
 @pytest.mark.parametrize("name", ["generate_ssm_dense_long", "generate_ssm_moe_long"])
 def test_top_k_one_through_the_graph_reproduces_the_greedy_reference(dev, name, monkeypatch):
     """do_sample=True with top_k = 1 keeps only the maximum: through the graph tail it must give the reference's greedy tokens
