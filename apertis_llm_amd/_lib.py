@@ -29,7 +29,7 @@ _vp, _i64, _i32, _f32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, cty
 _f64 = ctypes.c_double
 
 # name -> (restype, argtypes).  Order and meaning mirror include/apertis_hip.h exactly.
-ABI_VERSION = (4 << 16) | 11     # = APERTIS_ABI_VERSION of include/apertis_hip.h (tests/test_host_cpu.py compares them)
+ABI_VERSION = (4 << 16) | 12     # = APERTIS_ABI_VERSION of include/apertis_hip.h (tests/test_host_cpu.py compares them)
 SIGNATURES = {
     "apertis_abi_version": (ctypes.c_int, []),
     "apertis_arch": (ctypes.c_char_p, []),
@@ -170,6 +170,12 @@ SIGNATURES = {
                                          _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
     "apertis_attention_decode_at": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
                                            _i64, _i64, _i64, _i32, _vp]),
+    "apertis_rope_kv_append_chunk": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
+                                            _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
+    "apertis_attention_chunk_splits": (_i64, [_i64, _i64, _i64, _i64, _i64]),
+    "apertis_attention_chunk_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
+    "apertis_attention_chunk": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
+                                       _i64, _i64, _i64, _i64, _i32, _vp]),
     "apertis_token_counts": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "apertis_sample_next": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _f32, _i32, _f32, _i64, _f32, _u64, _vp, _i64, _vp, _vp, _vp,
                                    _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),

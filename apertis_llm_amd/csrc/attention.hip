@@ -16,132 +16,11 @@
 //               R[16s + 4g + r][l&15]); k-slot t of lane group g is row 16(t>>2) + 4g + (t&3), Z is read at that row.
 // Every product is oriented so that the later product sums over the row index of the earlier one (S^T = K Q^T then
 // O^T += V^T P^T), so no accumulator ever changes lanes.  bf16: P and dS are rounded to bf16 for their products.
-#include "common.h"
+// The tiles and the forward's per-tile step live in attn_tile.h: the chunk kernel of attention_decode.hip runs the same step.
+#include "attn_tile.h"
 #include "rope_common.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) bf16_t bf16x8;
-
-constexpr int ROWS = 16;       // rows per wave
-constexpr int TILE = 32;       // columns per step of a wave's loop
-constexpr int WAVES = 4;       // waves per work-group
-constexpr int WG_ROWS = ROWS * WAVES;
-
-// the lane's quarter of one head row: D/4 contiguous elements starting at column (lane>>4)*D/4
-template <typename T, int D> struct Quarter {
-  static constexpr int N = D / 4;
-  static constexpr int V = N * (int)sizeof(T) / 16;     // 16-byte loads
-  uint4 raw[V];
-};
-
-template <typename T, int D>
-__device__ __forceinline__ void load_quarter(Quarter<T, D> &f, const T *row, bool ok) {
-  if (ok) {
-    const uint4 *p = reinterpret_cast<const uint4 *>(row);
-#pragma unroll
-    for (int i = 0; i < Quarter<T, D>::V; ++i) f.raw[i] = p[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < Quarter<T, D>::V; ++i) f.raw[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
-
-// rows form
-template <int D>
-__device__ __forceinline__ void dot_rows(f32x4 &acc, const Quarter<bf16_t, D> &a, const Quarter<bf16_t, D> &b) {
-#pragma unroll
-  for (int i = 0; i < Quarter<bf16_t, D>::V; ++i)
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a.raw[i]), __builtin_bit_cast(bf16x8, b.raw[i]),
-                                                  acc, 0, 0, 0);
-}
-template <int D>
-__device__ __forceinline__ void dot_rows(f32x4 &acc, const Quarter<float, D> &a, const Quarter<float, D> &b) {
-#pragma unroll
-  for (int i = 0; i < Quarter<float, D>::V; ++i) {
-    const f32x4 av = __builtin_bit_cast(f32x4, a.raw[i]), bv = __builtin_bit_cast(f32x4, b.raw[i]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[e], acc, 0, 0, 0);
-  }
-}
-
-__device__ __forceinline__ int tile_row(int g, int t) { return 16 * (t >> 2) + 4 * g + (t & 3); }
-
-// column form: acc[dt] holds C[d = 16dt + 4g + r][l&15]; z points at row 0 / column 0 of this tile's head slice,
-// rows >= nrows read as zero (never dereferenced)
-template <int D>
-__device__ __forceinline__ void acc_cols(f32x4 (&acc)[D / 16], const bf16_t *z, int64_t z_rs, int nrows, const f32x4 (&R)[2],
-                                         int lane) {
-  const int g = lane >> 4, c = lane & 15;
-  bf16x8 b;
-#pragma unroll
-  for (int t = 0; t < 8; ++t) b[t] = (bf16_t)R[t >> 2][t & 3];
-  int64_t off[8];
-  bool ok[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int kr = tile_row(g, t);
-    ok[t] = kr < nrows;
-    off[t] = (int64_t)kr * z_rs + c;
-  }
-#pragma unroll
-  for (int dt = 0; dt < D / 16; ++dt) {
-    bf16x8 a;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) a[t] = ok[t] ? z[off[t] + 16 * dt] : (bf16_t)0.f;
-    acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[dt], 0, 0, 0);
-  }
-}
-template <int D>
-__device__ __forceinline__ void acc_cols(f32x4 (&acc)[D / 16], const float *z, int64_t z_rs, int nrows, const f32x4 (&R)[2],
-                                         int lane) {
-  const int g = lane >> 4, c = lane & 15;
-  int64_t off[8];
-  bool ok[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int kr = tile_row(g, t);
-    ok[t] = kr < nrows;
-    off[t] = (int64_t)kr * z_rs + c;
-  }
-#pragma unroll
-  for (int dt = 0; dt < D / 16; ++dt) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const float a = ok[t] ? z[off[t] + 16 * dt] : 0.f;
-      acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, R[t >> 2][t & 3], acc[dt], 0, 0, 0);
-    }
-  }
-}
-
-// row d = 16dt + 4g + r of a column-form accumulator, stored as 4 consecutive elements of output row `row`
-template <typename T, int D>
-__device__ __forceinline__ void store_cols(T *row, const f32x4 (&acc)[D / 16], float s, int lane) {
-  const int g = lane >> 4;
-#pragma unroll
-  for (int dt = 0; dt < D / 16; ++dt) {
-    T *p = row + 16 * dt + 4 * g;
-    if constexpr (sizeof(T) == 4) {
-      *reinterpret_cast<f32x4 *>(p) = acc[dt] * s;
-    } else {
-      typedef __attribute__((ext_vector_type(4))) bf16_t bf16x4;
-      bf16x4 v;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = (bf16_t)(acc[dt][r] * s);
-      *reinterpret_cast<bf16x4 *>(p) = v;
-    }
-  }
-}
-
-__device__ __forceinline__ float xor_max(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16));
-  return fmaxf(v, __shfl_xor(v, 32));
-}
-__device__ __forceinline__ float xor_sum(float v) {
-  v += __shfl_xor(v, 16);
-  return v + __shfl_xor(v, 32);
-}
 
 struct AttnArgs {
   const void *q, *k, *v, *o, *dout;
@@ -180,50 +59,20 @@ __global__ __launch_bounds__(256) void attn_fwd_k(AttnArgs a) {
   const int64_t last = min(q0 + ROWS - 1, L - 1);
   const uint64_t drow = (uint64_t)bh * (uint64_t)L + (uint64_t)qi;
   for (int64_t kb = 0; kb <= last; kb += TILE) {
-    f32x4 st[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      Quarter<T, D> kf;
-      const int64_t kr = kb + 16 * s + c;
-      load_quarter(kf, kp + kr * a.k_rs + g * (D / 4), kr < L);
-      st[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dot_rows<D>(st[s], kf, qf);                          // S^T[key 16s+4g+r][query c]
-    }
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t key = kb + 16 * s + 4 * g + r;
-        bool ok = key <= qi && key < L;
-        if (kv && ok) ok = kv[key] != 0;
-        st[s][r] = ok ? st[s][r] * sl2 : -INFINITY;
-        tmax = fmaxf(tmax, st[s][r]);
-      }
-    tmax = xor_max(tmax);
-    const float mn = fmaxf(m, tmax);
-    const float mu = mn == -INFINITY ? 0.f : mn;          // (a row with nothing valid yet: p = 0, no -inf - -inf)
-    const float alpha = exp2f(m - mu);
-    m = mn;
-    float ps = 0.f;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = exp2f(st[s][r] - mu);
-        ps += p;
-        float pd = p;
-        if constexpr (DROP) {
-          const int64_t key = kb + 16 * s + 4 * g + r;
-          pd = drop_keep(a.seed, (int64_t)drow, key, L, a.thresh16) ? p * a.inv_keep : 0.f;
-        }
-        st[s][r] = pd;
-      }
-    lsum = lsum * alpha + ps;
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt) acc[dt] *= alpha;
     const int64_t nrows = L - kb;
-    acc_cols<D>(acc, vp + kb * a.v_rs, a.v_rs, nrows < TILE ? (int)nrows : TILE, st, lane);
+    attn_fwd_tile<T, D>(
+        qf, kp, a.k_rs, vp, a.v_rs, kb, sl2, m, lsum, acc, lane, [=](int64_t kr) { return kr < L; },
+        [=](int t) {
+          const int64_t key = kb + tile_row(g, t);
+          bool ok = key <= qi && key < L;
+          if (kv && ok) ok = kv[key] != 0;
+          return ok;
+        },
+        RowsBelow{g, nrows < TILE ? (int)nrows : TILE},
+        [=](float p, int t) {
+          if constexpr (DROP) return drop_keep(a.seed, (int64_t)drow, kb + tile_row(g, t), L, a.thresh16) ? p * a.inv_keep : 0.f;
+          else return p;
+        });
   }
   const float l = xor_sum(lsum);
   if (qi >= L) return;
@@ -300,9 +149,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(AttnArgs a) {
       }
     }
     const int64_t nrows = L - qb;
-    const int nr = nrows < TILE ? (int)nrows : TILE;
-    acc_cols<D>(dv, dop + qb * a.do_rs, a.do_rs, nr, pd, lane);
-    acc_cols<D>(dk, qp + qb * a.q_rs, a.q_rs, nr, ds, lane);
+    const RowsBelow rows{g, nrows < TILE ? (int)nrows : TILE};
+    acc_cols<D>(dv, dop + qb * a.do_rs, a.do_rs, rows, pd, lane);
+    acc_cols<D>(dk, qp + qb * a.q_rs, a.q_rs, rows, ds, lane);
   }
   if (kj >= L) return;
   store_cols<T, D>(static_cast<T *>(a.dk) + (bo + kj) * a.d_rs + h * D, dk, a.scale, lane);
@@ -360,7 +209,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
       }
     }
     const int64_t nrows = L - kb;
-    acc_cols<D>(dq, kp + kb * a.k_rs, a.k_rs, nrows < TILE ? (int)nrows : TILE, ds, lane);
+    acc_cols<D>(dq, kp + kb * a.k_rs, a.k_rs, RowsBelow{g, nrows < TILE ? (int)nrows : TILE}, ds, lane);
   }
   if (!qok) return;
   store_cols<T, D>(static_cast<T *>(a.dq) + (bo + qi) * a.d_rs + h * D, dq, a.scale, lane);

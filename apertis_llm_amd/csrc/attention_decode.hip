@@ -17,7 +17,14 @@
 // range; the attention reads Lk = min(*len + 1, cap) itself and cuts it into a split count fixed by the caller, so grid and
 // workspace depend on nothing read from the device.  Same kernels as the by-value forms, same bits for the same row, Lk and
 // split count.
-#include "common.h"
+//
+// Multi-token steps (a chunk of Lq > 1 positions: a chat turn, a piece of a long prompt) - rope_kv_append_chunk_k appends Lq rows
+// per sequence and attn_chunk_k attends them causally over cache rows [0, n + Lq).  attn_chunk_k is the forward's algorithm
+// with the forward's own per-tile step (attn_tile.h: 16 query rows per wave, 32-key tiles from key 0, online softmax in fp32, no
+// LDS), so at one split a query gets the bits attn_fwd_k gives it in the whole sequence.  A short chunk against a long past is
+// few work-groups walking many keys: with splits > 1 each wave cuts ITS key tiles into `splits` runs (grid.z), leaves fp32
+// (m, l, o[D]) per (row, head, run) in the workspace, and attn_decode_merge_k - unchanged, over B * Lq rows - folds them in order.
+#include "attn_tile.h"
 #include "rope_common.h"
 
 namespace {
@@ -238,6 +245,147 @@ __global__ __launch_bounds__(256) void rope_kv_append_k(const T *q, int64_t q_rs
   vd[1] = vs[1];
 }
 
+// -------------------------------------------------------------------------------------------------- multi-token steps
+// one thread per (sequence, chunk row l, pair j): rotated q pair to q_out [B, Lq, W], rotated k pair and the v pair into cache
+// row t_cache0 + l; the rotary position is t0 + l
+template <typename T>
+__global__ __launch_bounds__(256) void rope_kv_append_chunk_k(const T *q, int64_t q_rs, int64_t q_bs, const T *k, int64_t k_rs,
+                                                              int64_t k_bs, const T *v, int64_t v_rs, int64_t v_bs,
+                                                              const float *cs, const float *sn, int64_t max_pos, int64_t t0,
+                                                              T *qo, T *kc, int64_t kc_rs, int64_t kc_bs, T *vc, int64_t vc_rs,
+                                                              int64_t vc_bs, int64_t t_cache0, int64_t Lq, int64_t half,
+                                                              int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int64_t tok = i / half, j = i - tok * half;
+  const int64_t b = tok / Lq, l = tok - b * Lq;
+  const T *qs = q + b * q_bs + l * q_rs + 2 * j, *ks = k + b * k_bs + l * k_rs + 2 * j, *vs = v + b * v_bs + l * v_rs + 2 * j;
+  T *qd = qo + tok * 2 * half + 2 * j, *kd = kc + b * kc_bs + (t_cache0 + l) * kc_rs + 2 * j;
+  T *vd = vc + b * vc_bs + (t_cache0 + l) * vc_rs + 2 * j;
+  if (cs) {
+    float c, s, y0, y1;
+    rope_cos_sin(cs, sn, t0 + l, max_pos, half, j, c, s);
+    rope_rotate_pair<false>(to_f32(qs[0]), to_f32(qs[1]), c, s, y0, y1);
+    qd[0] = from_f32<T>(y0);
+    qd[1] = from_f32<T>(y1);
+    rope_rotate_pair<false>(to_f32(ks[0]), to_f32(ks[1]), c, s, y0, y1);
+    kd[0] = from_f32<T>(y0);
+    kd[1] = from_f32<T>(y1);
+  } else {
+    qd[0] = qs[0];
+    qd[1] = qs[1];
+    kd[0] = ks[0];
+    kd[1] = ks[1];
+  }
+  vd[0] = vs[0];
+  vd[1] = vs[1];
+}
+
+struct ChunkArgs {
+  const void *q, *k, *v;
+  const int64_t *key_valid;
+  void *out;
+  float *ws_ml, *ws_o;
+  int64_t q_rs, k_rs, k_bs, v_rs, v_bs, kv_rs, out_rs, Lq, n;
+  int H, splits;
+  float scale;
+};
+
+// Query row i of the chunk sits at key position n + i and attends keys j <= n + i with key_valid[b, j] != 0.  Grid: 64-row
+// blocks of the chunk (the last, longest-walking block first, as attn_fwd_k) x (B * H) x splits.  A key row at or past n + Lq,
+// the row of a masked key and a mask column at or past n + Lq are never read: such a row enters the tile as zeros, and its score
+// is replaced by -inf before anything reads it.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_chunk_k(ChunkArgs a) {
+  const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+  const int64_t Lq = a.Lq, Lk = a.n + a.Lq;
+  const int bh = blockIdx.y, H = a.H, b = bh / H, h = bh - b * H, sp = blockIdx.z;
+  const int64_t nblk = (Lq + WG_ROWS - 1) / WG_ROWS;
+  const int64_t q0 = (nblk - 1 - blockIdx.x) * WG_ROWS + (threadIdx.x >> 6) * ROWS;
+  if (q0 >= Lq) return;
+  const T *qp = static_cast<const T *>(a.q) + (int64_t)b * Lq * a.q_rs + h * D;
+  const T *kp = static_cast<const T *>(a.k) + (int64_t)b * a.k_bs + h * D;
+  const T *vp = static_cast<const T *>(a.v) + (int64_t)b * a.v_bs + h * D;
+  const int64_t *kv = a.key_valid ? a.key_valid + (int64_t)b * a.kv_rs : nullptr;
+  const int64_t qi = q0 + c, pi = a.n + qi;                // this lane's chunk row and its position among the keys
+  Quarter<T, D> qf;
+  load_quarter(qf, qp + qi * a.q_rs + g * (D / 4), qi < Lq);
+  const float sl2 = a.scale * LOG2E_F;
+  float m = -INFINITY, lsum = 0.f;
+  f32x4 acc[D / 16];
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // the wave's tiles: up to the one that holds its last row's own key; run `sp` of `splits` (wave-uniform, possibly empty)
+  const int64_t ntile = (a.n + min(q0 + ROWS - 1, Lq - 1)) / TILE + 1;
+  const int64_t t0 = sp * ntile / a.splits, t1 = (sp + 1) * ntile / a.splits;
+  for (int64_t kb = t0 * TILE; kb < t1 * TILE; kb += TILE) {
+    bool valid[8];                                         // k-slot t of this lane group: may the row be read at all
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int64_t key = kb + tile_row(g, t);
+      valid[t] = key < Lk;
+      if (kv && valid[t]) valid[t] = kv[key] != 0;
+    }
+    attn_fwd_tile<T, D>(
+        qf, kp, a.k_rs, vp, a.v_rs, kb, sl2, m, lsum, acc, lane,
+        [=](int64_t kr) {
+          bool ok = kr < Lk;
+          if (kv && ok) ok = kv[kr] != 0;
+          return ok;
+        },
+        [&](int t) { return valid[t] && kb + tile_row(g, t) <= pi; }, [&](int t) { return valid[t]; },
+        [](float p, int) { return p; });
+  }
+  const float l = xor_sum(lsum);
+  if (qi >= Lq) return;
+  const int64_t row = (int64_t)b * Lq + qi;
+  if (a.splits == 1) {
+    store_cols<T, D>(static_cast<T *>(a.out) + row * a.out_rs + h * D, acc, l > 0.f ? 1.f / l : 0.f, lane);
+  } else {
+    const int64_t idx = (row * H + h) * a.splits + sp;     // (attn_decode_merge_k's layout with B * Lq rows)
+    store_cols<float, D>(a.ws_o + idx * D, acc, 1.f, lane);
+    if (g == 0) {
+      a.ws_ml[2 * idx] = m;
+      a.ws_ml[2 * idx + 1] = l;
+    }
+  }
+}
+
+constexpr int64_t MERGE_MAX_ROWS = 65535;                  // grid.y of attn_decode_merge_k
+
+template <typename T, int D> int launch_chunk(const ChunkArgs &a, int64_t B, hipStream_t st) {
+  const dim3 grid((unsigned)ceil_div64(a.Lq, WG_ROWS), (unsigned)(B * a.H), (unsigned)a.splits);
+  hipLaunchKernelGGL((attn_chunk_k<T, D>), grid, dim3(256), 0, st, a);
+  if (a.splits > 1) {
+    const int64_t rows = B * a.Lq;
+    for (int64_t r0 = 0; r0 < rows; r0 += MERGE_MAX_ROWS) {
+      const int64_t nr = rows - r0 < MERGE_MAX_ROWS ? rows - r0 : MERGE_MAX_ROWS;
+      DecArgs d{};
+      d.out = static_cast<T *>(a.out) + r0 * a.out_rs;
+      d.ws_ml = a.ws_ml + 2 * r0 * a.H * a.splits;
+      d.ws_o = a.ws_o + r0 * a.H * a.splits * D;
+      d.out_rs = a.out_rs;
+      d.H = a.H;
+      d.splits = a.splits;
+      hipLaunchKernelGGL((attn_decode_merge_k<T, D>), dim3((unsigned)a.H, (unsigned)nr), dim3(D), 0, st, d);
+    }
+  }
+  return apertis_check_launch();
+}
+
+// The decode rule's form, placed by a sweep of forced counts: the time follows the number of WAVES in
+// flight (a 16-row chunk costs what a 64-row one costs at the same count), it stops falling at about 2 048 of them - two per
+// SIMD - and a run wants at least two 32-key tiles.
+constexpr int CHUNK_TARGET_WAVES = 2048;
+constexpr int CHUNK_MIN_KEYS = 2 * TILE;
+
+int64_t chunk_splits(int64_t B, int64_t H, int64_t Lq, int64_t Lk) {
+  const int64_t want = CHUNK_TARGET_WAVES / (B * H * ceil_div64(Lq, ROWS)), by_len = Lk / CHUNK_MIN_KEYS;
+  int64_t s = want < by_len ? want : by_len;
+  if (s > APERTIS_ATTN_DECODE_MAX_SPLITS) s = APERTIS_ATTN_DECODE_MAX_SPLITS;
+  return s < 1 ? 1 : s;
+}
+
 }  // namespace
 
 // both appends: t and t_cache by value (at.len null), or the device-held length
@@ -351,4 +499,76 @@ extern "C" int apertis_attention_decode_at(const void *q, int64_t q_rs, const vo
   // (Lk = cap for the shared checks: key_valid must cover every column the kernel can reach, and the kernel clamps to it)
   return attention_decode_impl(q, q_rs, k_cache, k_rs, k_bs, v_cache, v_rs, v_bs, cap, len, key_valid, kv_rs, out, out_rs, workspace,
                                B, cap, H, D, splits, dtype, stream);
+}
+
+extern "C" int apertis_rope_kv_append_chunk(const void *q, int64_t q_rs, int64_t q_bs, const void *k, int64_t k_rs, int64_t k_bs,
+                                            const void *v, int64_t v_rs, int64_t v_bs, const float *cos_cached,
+                                            const float *sin_cached, int64_t max_pos, int64_t t0, void *q_out, void *k_cache,
+                                            int64_t kc_rs, int64_t kc_bs, void *v_cache, int64_t vc_rs, int64_t vc_bs, int64_t cap,
+                                            int64_t t_cache0, int64_t B, int64_t Lq, int64_t W, int dtype, void *stream) {
+  if (!q || !k || !v || !q_out || !k_cache || !v_cache || (cos_cached == nullptr) != (sin_cached == nullptr)) return APERTIS_ERR_ARG;
+  if (B < 0 || Lq < 0 || W <= 0 || (W & 1) || cap < 1 || (dtype != APERTIS_F32 && dtype != APERTIS_BF16)) return APERTIS_ERR_ARG;
+  if (q_rs < W || k_rs < W || v_rs < W || kc_rs < W || vc_rs < W || kc_bs < cap * kc_rs || vc_bs < cap * vc_rs) return APERTIS_ERR_ARG;
+  if (Lq > 0 && (q_bs < Lq * q_rs || k_bs < Lq * k_rs || v_bs < Lq * v_rs)) return APERTIS_ERR_ARG;
+  if (cos_cached && max_pos <= 0) return APERTIS_ERR_ARG;
+  if (t_cache0 < 0 || t_cache0 > cap || Lq > cap - t_cache0) return APERTIS_ERR_ARG;
+  if (cos_cached && Lq > 0 && (t0 < -max_pos || t0 >= max_pos || Lq > max_pos - t0)) return APERTIS_ERR_ARG;
+  const int64_t half = W / 2, total = B * Lq * half;
+  if (total == 0) return APERTIS_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)ceil_div64(total, 256));
+  if (dtype == APERTIS_F32)
+    hipLaunchKernelGGL((rope_kv_append_chunk_k<float>), grid, dim3(256), 0, st, (const float *)q, q_rs, q_bs, (const float *)k, k_rs,
+                       k_bs, (const float *)v, v_rs, v_bs, cos_cached, sin_cached, max_pos, t0, (float *)q_out, (float *)k_cache,
+                       kc_rs, kc_bs, (float *)v_cache, vc_rs, vc_bs, t_cache0, Lq, half, total);
+  else
+    hipLaunchKernelGGL((rope_kv_append_chunk_k<bf16_t>), grid, dim3(256), 0, st, (const bf16_t *)q, q_rs, q_bs, (const bf16_t *)k,
+                       k_rs, k_bs, (const bf16_t *)v, v_rs, v_bs, cos_cached, sin_cached, max_pos, t0, (bf16_t *)q_out,
+                       (bf16_t *)k_cache, kc_rs, kc_bs, (bf16_t *)v_cache, vc_rs, vc_bs, t_cache0, Lq, half, total);
+  return apertis_check_launch();
+}
+
+extern "C" int64_t apertis_attention_chunk_splits(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D) {
+  if (B < 1 || H < 1 || Lq < 1 || Lk < Lq || D < 1) return -1;
+  return chunk_splits(B, H, Lq, Lk);
+}
+
+extern "C" int64_t apertis_attention_chunk_workspace_bytes(int64_t B, int64_t H, int64_t Lq, int64_t D, int64_t splits) {
+  if (B < 0 || H < 1 || Lq < 0 || D < 1 || splits < 1 || splits > APERTIS_ATTN_DECODE_MAX_SPLITS) return -1;
+  return splits == 1 ? 0 : B * Lq * H * splits * (D + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int apertis_attention_chunk(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
+                                       const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid,
+                                       int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lq, int64_t n,
+                                       int64_t H, int64_t D, int64_t splits, int dtype, void *stream) {
+  if (!q || !k_cache || !v_cache || !out) return APERTIS_ERR_ARG;
+  if (B < 0 || H <= 0 || D <= 0 || cap < 1 || Lq < 1 || n < 0 || n > cap || Lq > cap - n ||
+      (dtype != APERTIS_F32 && dtype != APERTIS_BF16))
+    return APERTIS_ERR_ARG;
+  if ((D != 64 && D != 128) || B * H > 65535) return APERTIS_ERR_UNSUPPORTED;
+  const int64_t W = H * D, es = dtype == APERTIS_F32 ? 4 : 2;
+  if (q_rs < W || out_rs < W || k_rs < W || v_rs < W || k_bs < cap * k_rs || v_bs < cap * v_rs) return APERTIS_ERR_ARG;
+  if (key_valid && kv_rs < n + Lq) return APERTIS_ERR_ARG;
+  if (splits < 0 || splits > APERTIS_ATTN_DECODE_MAX_SPLITS) return APERTIS_ERR_ARG;
+  // 16-byte row quarters and 16-byte stores of the output: every row start on a 16-byte boundary
+  const uint64_t bits = (uint64_t)(uintptr_t)q | (uint64_t)(uintptr_t)k_cache | (uint64_t)(uintptr_t)v_cache |
+                        (uint64_t)(uintptr_t)out | (uint64_t)(q_rs * es) | (uint64_t)(out_rs * es) | (uint64_t)(k_rs * es) |
+                        (uint64_t)(k_bs * es) | (uint64_t)(v_rs * es) | (uint64_t)(v_bs * es);
+  if (bits & 15u) return APERTIS_ERR_UNSUPPORTED;
+  if (B == 0) return APERTIS_OK;
+  if (splits == 0) splits = chunk_splits(B, H, Lq, n + Lq);
+  if (splits > 1 && (!workspace || ((uintptr_t)workspace & 15u))) return APERTIS_ERR_ARG;
+  ChunkArgs a{};
+  a.q = q; a.k = k_cache; a.v = v_cache; a.key_valid = key_valid; a.out = out;
+  a.ws_ml = workspace;
+  a.ws_o = workspace ? workspace + 2 * B * Lq * H * splits : nullptr;
+  a.q_rs = q_rs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.kv_rs = kv_rs; a.out_rs = out_rs;
+  a.Lq = Lq; a.n = n;
+  a.H = (int)H;
+  a.splits = (int)splits;
+  a.scale = 1.f / sqrtf((float)D);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == APERTIS_F32) return D == 64 ? launch_chunk<float, 64>(a, B, st) : launch_chunk<float, 128>(a, B, st);
+  return D == 64 ? launch_chunk<bf16_t, 64>(a, B, st) : launch_chunk<bf16_t, 128>(a, B, st);
 }

@@ -844,6 +844,31 @@ class ApertisAttention(nn.Module):
             ctxv = ops.attention_decode(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
         return self.out_proj(ctxv.unsqueeze(1)), cache
 
+    def _chunk_ok(self, q, att_mask, past_kv, output_att, use_c):
+        """Whether this call is a multi-token step the chunk kernels take (ops.kv_append_rope_chunk, ops.attention_chunk):
+        the past is a layer of an ops.KVCache that opted in (`multi_token`) with no device step state active, in the
+        projections' dtype and with room for the Lq > 1 new rows; inference (no grad, eval, use_cache, no attention weights),
+        on the GPU, D 64 or 128, both switches on; the model's own positions, known on the host (n .. n + Lq - 1); key 0 of
+        every sequence valid, so that every row has a valid key; the mask None or [B, n + Lq].  Anything else runs the stock
+        branch on the cache's views, as every multi-token forward against a cache without the flag does."""
+        if not (isinstance(past_kv, ops.KVLayer) and past_kv.cache.multi_token and not past_kv.cache.step_active
+                and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and q.is_cuda and q.shape[1] > 1 and use_c and not output_att
+                and not self.training and not torch.is_grad_enabled()
+                and isinstance(att_mask, _AttnMask) and att_mask.decode_ok and att_mask.pos_host is not None
+                and ops.attention_decode_supported(q, self.num_attention_heads)):
+            return False
+        cache, kv = past_kv.cache, att_mask.key_valid
+        n = cache.lengths[past_kv.layer]
+        return (q.dtype == cache.dtype and n + q.shape[1] <= cache.capacity and q.shape[0] == cache.k[0].shape[0]
+                and att_mask.pos_host == n and (kv is None or tuple(kv.shape) == (q.shape[0], n + q.shape[1])))
+
+    def _chunk_attention(self, q, k, v, att_mask, past_kv):
+        cache, layer = past_kv.cache, past_kv.layer
+        cos, sin = (self.rope.cos_cached, self.rope.sin_cached) if self.rope is not None else (None, None)
+        q = ops.kv_append_rope_chunk(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
+        ctxv = ops.attention_chunk(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
+        return self.out_proj(ctxv), cache
+
     def _heads(self, t):
         B, L, _ = t.shape
         return t.view(B, L, self.num_attention_heads, self.attention_head_size).transpose(1, 2)
@@ -864,6 +889,9 @@ class ApertisAttention(nn.Module):
                                                               use_cache=use_c)
         elif self._decode_ok(q := self.q_proj(x), att_mask, past_kv, output_att, use_c):
             out, cache = self._decode_attention(q, self.k_proj(x), self.v_proj(x), att_mask, past_kv)
+            proxy = None
+        elif self._chunk_ok(q, att_mask, past_kv, output_att, use_c):
+            out, cache = self._chunk_attention(q, self.k_proj(x), self.v_proj(x), att_mask, past_kv)
             proxy = None
         elif self._fused_ok(q, att_mask, past_kv, output_att):
             out, cache = self._fused_attention(q, self.k_proj(x), self.v_proj(x), att_mask, pos_ids, use_c)
@@ -1019,6 +1047,7 @@ class _AttnMask:
     are the model's own 0..L-1, and the additive mask of the stock path, built only if that path asks for it.  For a
     single-token step against a KVCache: whether the decode kernels may run (key 0 of every sequence valid, so every row has a
     valid key) and the step's position as a HOST integer (None when the caller gave position_ids: only a tensor knows them).
+    A multi-token step against a `multi_token` KVCache reads the same two: `pos_host` is then the position of its first token.
     `step_cache`: the KVCache whose device step state carries length, position and key validity of this step instead (no
     host integer, no mask tensor here)."""
     __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host", "step_cache")
@@ -1165,8 +1194,9 @@ class ApertisModel(nn.Module):
                 output_hidden_states=None, return_dict=None):
         """past_key_values: a prefill's tuple of per-layer pairs (plain tensors in, plain tensors out), or for standard_mha an
         ops.KVCache: a single-token step then appends to it IN PLACE on the decode kernels and hands the same object back
-        (position_ids = None: the step's position is the cache's length); a call the kernels do not take runs the stock
-        branch on the cache's views and hands back plain tensors."""
+        (position_ids = None: the step's position is the cache's length); a cache with `multi_token` set takes a forward of
+        several tokens the same way, on the chunk kernels; a call the kernels do not take runs the stock branch on the
+        cache's views and hands back plain tensors."""
         cfg = self.config
         use_c = cfg.use_cache if use_cache is None else use_cache
         out_att = cfg.output_attentions if output_attentions is None else output_attentions
@@ -1214,7 +1244,8 @@ class ApertisModel(nn.Module):
         x = self.embed_dropout(x)
         own_pos = position_ids is None and pos_layers is pos
         mask = None if ssm else self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len, own_pos,
-                                                     past_len if own_pos and kv_cache is not None and x.shape[1] == 1 else None,
+                                                     past_len if own_pos and kv_cache is not None
+                                                     and (x.shape[1] == 1 or kv_cache.multi_token) else None,
                                                      kv_cache if dev_step else None)
 
         all_hs, all_att, all_cache = [], [], []
@@ -1443,18 +1474,84 @@ class ApertisForCausalLM(nn.Module):
                  max_new_tokens: Optional[int] = 20, min_new_tokens: Optional[int] = 0, do_sample: Optional[bool] = False,
                  temperature: Optional[float] = 1.0, top_k: Optional[int] = 50, top_p: Optional[float] = 1.0,
                  repetition_penalty: Optional[float] = 1.0, eos_token_id=None, pad_token_id=None,
-                 use_cache: bool = True, **kwargs):
+                 use_cache: bool = True, past_key_values=None, prefill_chunk: Optional[int] = None, **kwargs):
         """Greedy / top-k / top-p / repetition-penalty decoding loop (reference core.py:1520-1644).  The prepared copies of
-        the weights (stacked / padded / cast) are reused from token to token inside the call (ops.prep_cache_scope)."""
+        the weights (stacked / padded / cast) are reused from token to token inside the call (ops.prep_cache_scope).
+
+        past_key_values (standard_mha on the GPU): a `multi_token` ops.KVCache (new_kv_cache) the caller keeps between calls.
+        It holds n = cache.length <= P - 1 rows, and the caller promises that they are the keys and values of
+        input_ids[:, :n] under attention_mask[:, :n].  Only positions >= n are forwarded: the rest of the prompt goes into
+        the cache on the chunk kernels in steps of at most `prefill_chunk` tokens (None: one step), then the usual loop runs
+        on the same cache.  On return cache.length == output.shape[1] - 1: the next turn passes the output plus its new
+        tokens and the same cache.  A cache that cannot be continued raises (_generate_cache_check); nothing is prefilled
+        again silently."""
         if input_ids is None:
             raise ValueError("input_ids must be provided.")
+        if past_key_values is not None:
+            self._generate_cache_check(past_key_values, input_ids, position_ids, pixel_values, max_new_tokens, use_cache,
+                                       prefill_chunk)
+        elif prefill_chunk is not None:
+            raise ValueError("generate(): prefill_chunk pieces a prompt into a KVCache passed as past_key_values")
         with ops.prep_cache_scope():
             return self._generate(input_ids, attention_mask, position_ids, pixel_values, max_new_tokens, min_new_tokens,
                                   do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id, pad_token_id,
-                                  use_cache)
+                                  use_cache, past_key_values, prefill_chunk)
+
+    def new_kv_cache(self, batch_size, capacity, dtype=None, device=None):
+        """An empty `multi_token` ops.KVCache for this model (standard_mha): one [batch_size, capacity, hidden_size] k and v
+        buffer per layer.  dtype: the autocast dtype if autocast is enabled, else the projection weights' (what the
+        projections will produce: _mha_graph_ok's rule); device: the weights'."""
+        cfg = self.config
+        if cfg.attention_type != "standard_mha":
+            raise ops.ApertisHipError(f"new_kv_cache: a KVCache serves standard_mha, not attention_type {cfg.attention_type!r}")
+        w = self.model.layers[0].attention.q_proj.weight
+        if dtype is None:
+            dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else w.dtype
+        return ops.KVCache.empty(cfg.num_hidden_layers, batch_size, capacity, cfg.hidden_size, dtype,
+                                 w.device if device is None else device, multi_token=True)
+
+    def _generate_cache_check(self, cache, input_ids, position_ids, pixel_values, max_new_tokens, use_cache, prefill_chunk):
+        """Everything generate(past_key_values=cache) needs of the cache and the call, checked before the first forward: a
+        call that cannot continue the cache in place raises here rather than prefill again or leave the kernels."""
+        cfg, err = self.config, ops.ApertisHipError
+        if not isinstance(cache, ops.KVCache):
+            raise err(f"generate(): past_key_values takes an ops.KVCache (new_kv_cache), not {type(cache).__name__}")
+        if cfg.attention_type != "standard_mha":
+            raise err(f"generate(): a KVCache serves standard_mha, not attention_type {cfg.attention_type!r}")
+        if not cache.multi_token:
+            raise err("generate(): the KVCache must be multi_token (new_kv_cache, or KVCache.empty(..., multi_token=True))")
+        if not use_cache:
+            raise err("generate(): past_key_values with use_cache=False")
+        if pixel_values is not None:
+            raise err("generate(): pixel_values together with a KVCache (the image rows are not part of input_ids)")
+        if position_ids is not None:
+            raise err("generate(): a KVCache takes the model's own positions (position_ids=None)")
+        if not (ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED) or self.training or cfg.output_attentions:
+            raise err("generate(): a KVCache needs ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED, eval mode and no output_attentions")
+        if cache.step_active or len(set(cache.lengths)) != 1 or len(cache) != len(self.model.layers):
+            raise err(f"generate(): the KVCache is mid-step or not this model's ({len(cache)} layers, lengths {cache.lengths})")
+        attn = self.model.layers[0].attention
+        want = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else attn.q_proj.weight.dtype
+        B, P = input_ids.shape
+        if tuple(cache.k[0].shape) != (B, cache.capacity, cfg.hidden_size) or cache.dtype != want:
+            raise err(f"generate(): a KVCache of {tuple(cache.k[0].shape)} {cache.dtype} for {B} sequences of width "
+                      f"{cfg.hidden_size} in {want}")
+        if not ops.attention_decode_supported(cache.k[0], attn.num_attention_heads):
+            raise err("generate(): the KV-cache kernels take head dims 64 and 128 in fp32 or bf16")
+        n = cache.length
+        if n > P - 1:
+            raise err(f"generate(): the KVCache holds {n} rows but the prompt has {P} tokens (at most {P - 1} may be cached)")
+        if P + max_new_tokens - 1 > cache.capacity:
+            raise err(f"generate(): {P} prompt tokens and {max_new_tokens} new ones need {P + max_new_tokens - 1} rows, the "
+                      f"KVCache has {cache.capacity}")
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError(f"generate(): prefill_chunk {prefill_chunk} < 1")
+        if not input_ids.is_cuda or not cache.k[0].is_cuda:
+            raise err("generate(): a KVCache needs the model and its inputs on the GPU (there is no CPU path)")
 
     def _generate(self, input_ids, attention_mask, position_ids, pixel_values, max_new_tokens, min_new_tokens, do_sample,
-                  temperature, top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, use_cache):
+                  temperature, top_k, top_p, repetition_penalty, eos_token_id, pad_token_id, use_cache, cache=None,
+                  prefill_chunk=None):
         B, prompt_len = input_ids.shape
         temp = max(temperature, 1e-6) if do_sample else 1.0
         eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
@@ -1471,6 +1568,16 @@ class ApertisForCausalLM(nn.Module):
             mask = torch.cat([mask.new_ones(B, n_img), mask], dim=1)
             pos = torch.cat([torch.arange(n_img, device=input_ids.device).unsqueeze(0).expand(B, -1), pos + n_img], dim=1)
         tokens, past = input_ids, None
+        rest = None
+        if cache is not None and max_new_tokens > 0:
+            # the caller's cache holds the first n positions: the rest of the prompt goes into it in pieces, all but the last
+            # here (their logits select nothing); the loop's first forward takes the last piece instead of a prefill
+            past, n = cache, cache.length
+            step = prompt_len - n if prefill_chunk is None else prefill_chunk
+            while prompt_len - n > step:
+                self._cache_forward(cache, input_ids[:, n:n + step], mask[:, :n + step])
+                n += step
+            rest = input_ids[:, n:]
         alive = torch.ones(B, dtype=torch.long, device=input_ids.device)
         # sampling or a repetition penalty on the GPU: one kernel per step selects the token (ops.sample_next); the stock block
         # below stays for CPU tensors, vocabularies the kernel does not take and SAMPLE_FUSED = False
@@ -1484,12 +1591,18 @@ class ApertisForCausalLM(nn.Module):
             px = None
             # (a step against a KVCache takes its position from the cache's length, a host integer - the value
             #  prepare_inputs_for_generation puts into every row, mask.shape[1] - 1 - so the decode kernels need no read-back)
-            out = self(input_ids=inp["input_ids"], attention_mask=inp["attention_mask"],
-                       position_ids=None if isinstance(past, ops.KVCache) else inp["position_ids"],
-                       past_key_values=inp["past_key_values"],
-                       pixel_values=inp.get("pixel_values"), use_cache=inp["use_cache"])
+            if rest is not None:
+                out, rest = self._cache_forward(cache, rest, mask), None
+            else:
+                out = self(input_ids=inp["input_ids"], attention_mask=inp["attention_mask"],
+                           position_ids=None if isinstance(past, ops.KVCache) else inp["position_ids"],
+                           past_key_values=inp["past_key_values"],
+                           pixel_values=inp.get("pixel_values"), use_cache=inp["use_cache"])
             prefill = past is None
             past = out[4] if use_cache else None
+            if cache is not None and past is not cache:
+                raise ops.ApertisHipError("generate(): a token step left the KVCache (the decode kernels did not take it); "
+                                          "the cache passed as past_key_values can no longer be continued")
             if prefill and past is not None and self._kv_cache_ok(past, tokens, max_new_tokens):
                 # standard_mha: the prefill's (k, v) move into preallocated buffers once; every later step appends in place
                 past = ops.KVCache.from_prefill(past, mask.shape[1] + max_new_tokens)
@@ -1540,6 +1653,16 @@ class ApertisForCausalLM(nn.Module):
                 return self._generate_graph_tail(tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad,
                                                  sampler=sampler, mask=mask)
         return tokens
+
+    def _cache_forward(self, cache, ids, mask):
+        """One forward of `ids` (the positions after the rows `cache` holds) that must extend the caller's cache in place: a
+        forward the KV-cache kernels did not take (it hands plain tensors back and leaves the cache behind) raises."""
+        out = self(input_ids=ids, attention_mask=mask, position_ids=None, past_key_values=cache, use_cache=True)
+        if out[4] is not cache:
+            raise ops.ApertisHipError(f"generate(): a forward of {ids.shape[1]} tokens against the KVCache did not run on the "
+                                      "KV-cache kernels (key 0 of a sequence masked, or the attention mask does not cover "
+                                      "the prompt): there is no fallback that keeps the cache")
+        return out
 
     def _kv_cache_ok(self, past, tokens, max_new_tokens):
         """Whether generate() carries this prefill's cache as an ops.KVCache (the decode kernels then take every step that

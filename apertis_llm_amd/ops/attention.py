@@ -1,5 +1,6 @@
-"""standard_mha: interleaved-pair RoPE over the full width, causal softmax attention (flash style), and single-token decode
-against a preallocated KV cache (KVCache, kv_append_rope, attention_decode).
+"""standard_mha: interleaved-pair RoPE over the full width, causal softmax attention (flash style), and decode against a
+preallocated KV cache (KVCache): single-token steps (kv_append_rope, attention_decode) and multi-token steps
+(kv_append_rope_chunk, attention_chunk).
 
 Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autograd bookkeeping only; every computation is a
 HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip).  Tensors must live on a ROCm
@@ -212,9 +213,13 @@ class KVCache:
     read the step from there and never touch `lengths`; whoever drives the steps adds one to `dev_len` after the last layer
     and writes the validity column of the new token.  WHILE THE DEVICE STATE DRIVES THE STEPS THE HOST `lengths` ARE STALE
     (and with them the views `cache[i]` hands out); step_state_end() makes them current again - from `dev_len` with one
-    host read, or from the length its caller knows - and the by-value steps may go on.  Still one continuation per cache."""
+    host read, or from the length its caller knows - and the by-value steps may go on.  Still one continuation per cache.
 
-    def __init__(self, k, v, length=0):
+    `multi_token` (a flag, default False): a forward of several tokens extends this cache in place on the chunk kernels
+    (kv_append_rope_chunk, attention_chunk) and hands the same object back, as a single-token step does; without the flag such
+    a forward runs the stock branch on the cache's views, returns plain tensors and leaves the cache as it was."""
+
+    def __init__(self, k, v, length=0, multi_token=False):
         if len(k) != len(v) or not k:
             raise ApertisHipError("KVCache: one k and one v buffer per layer")
         for a, b in zip(k, v):
@@ -225,26 +230,27 @@ class KVCache:
         if not 0 <= length <= self.capacity:
             raise ApertisHipError(f"KVCache: length {length} outside [0, {self.capacity}]")
         self.lengths = [int(length)] * len(self.k)
+        self.multi_token = bool(multi_token)
         self._ws = None
         self.dev_len = self.dev_valid = self.dev_err = None
         self.step_active, self.step_splits = False, 1
 
     @classmethod
-    def empty(cls, layers, B, capacity, W, dtype=torch.float32, device=None):
+    def empty(cls, layers, B, capacity, W, dtype=torch.float32, device=None, multi_token=False):
         if layers < 1 or B < 0 or capacity < 1 or W < 1:
             raise ApertisHipError(f"KVCache.empty: layers {layers}, B {B}, capacity {capacity}, W {W}")
         mk = lambda: [torch.empty(B, capacity, W, dtype=dtype, device=device) for _ in range(layers)]     # noqa: E731
-        return cls(mk(), mk(), 0)
+        return cls(mk(), mk(), 0, multi_token)
 
     @classmethod
-    def from_prefill(cls, past, capacity):
+    def from_prefill(cls, past, capacity, multi_token=False):
         """From a prefill's `past_key_values` (per layer (k, v), [B, L, W]): one copy per layer into buffers of `capacity`
         rows, in the prefill's dtype, once per generation."""
         L = past[0][0].shape[1]
         if capacity < L:
             raise ApertisHipError(f"KVCache.from_prefill: capacity {capacity} below the prefill's {L} positions")
         B, _, W = past[0][0].shape
-        c = cls.empty(len(past), B, capacity, W, past[0][0].dtype, past[0][0].device)
+        c = cls.empty(len(past), B, capacity, W, past[0][0].dtype, past[0][0].device, multi_token)
         for i, (k, v) in enumerate(past):
             c.k[i][:, :L].copy_(k)
             c.v[i][:, :L].copy_(v)
@@ -426,6 +432,109 @@ def attention_decode(q, cache, layer, heads, key_valid=None, splits=0):
             (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
              ptr(out), W, ptr(ws), B, Lk, heads, D, int(splits), dtype_code(q), stream_ptr()),
             work=4.0 * B * Lk * W, detail=f"{B}x{heads}x{D}", nbytes=nbytes)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------- multi-token steps
+def _chunk3d(t, B, W, what):
+    """[B, Lq, W] -> (tensor with unit inner stride, row stride, batch stride)."""
+    if t.dim() != 3 or t.shape[0] != B or t.shape[-1] != W:
+        raise ApertisHipError(f"{what}: expected [{B}, Lq, {W}], got {tuple(t.shape)}")
+    Lq = t.shape[1]
+    if t.stride(-1) != 1 or (Lq > 1 and t.stride(1) < W) or (B > 1 and t.stride(0) < Lq * t.stride(1)):
+        t = t.contiguous()
+    rs = t.stride(1) if Lq > 1 else W
+    return t, rs, (t.stride(0) if B > 1 else Lq * rs)
+
+
+def kv_append_rope_chunk(q, k, v, cache, layer, t0=None, cos=None, sin=None):
+    """A chunk of Lq tokens of every sequence into layer `layer` of `cache`, in ONE launch: rows l of q and k ([B, Lq, W]) are
+    rotated at rotary position `t0 + l` (a host integer; default: the first row appended to) with the module's fp32
+    cos_cached / sin_cached - the same bits as rope_qk at those positions - rotated k and v go into cache rows
+    `lengths[layer] + l`, IN PLACE, and that length grows by Lq.  cos = sin = None: no rotation, a plain append.  Returns
+    the rotated q [B, Lq, W].  A position outside [-max_pos, max_pos) raises IndexError as the stock module's table lookup
+    does; a chunk that does not fit raises before anything is written."""
+    _require_gpu(q, k, v, cache.k[layer], cos, sin)
+    lib = _lib.load()
+    kc, vc = cache.k[layer], cache.v[layer]
+    B, cap, W = kc.shape
+    row = cache.lengths[layer]
+    (q, q_rs, q_bs), (k, k_rs, k_bs), (v, v_rs, v_bs) = (_chunk3d(t, B, W, f"kv_append_rope_chunk {n}")
+                                                          for t, n in ((q, "q"), (k, "k"), (v, "v")))
+    Lq = q.shape[1]
+    if not (k.shape[1] == v.shape[1] == Lq and q.dtype == k.dtype == v.dtype == cache.dtype):
+        raise ApertisHipError(f"kv_append_rope_chunk: q/k/v {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)} {q.dtype} against "
+                              f"a cache of [{B}, {cap}, {W}] {cache.dtype}")
+    if row + Lq > cap:
+        raise ApertisHipError(f"kv_append_rope_chunk: {Lq} rows do not fit ({row} of {cap} rows held)")
+    max_pos = 0
+    if (cos is None) != (sin is None):
+        raise ApertisHipError("kv_append_rope_chunk: cos and sin come together")
+    t0 = row if t0 is None else int(t0)
+    if cos is not None:
+        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
+            raise ApertisHipError(f"kv_append_rope_chunk: cos/sin must be fp32 [max_pos, {W // 2}]")
+        cos, sin, max_pos = cos.contiguous(), sin.contiguous(), cos.shape[0]
+        if Lq and not (-max_pos <= t0 and t0 + Lq <= max_pos):
+            raise IndexError(f"positions {t0}..{t0 + Lq - 1} outside the rotary table of {max_pos} positions")
+    qo = torch.empty(B, Lq, W, device=q.device, dtype=q.dtype)
+    _launch("apertis_rope_kv_append_chunk", lib.apertis_rope_kv_append_chunk,
+            (ptr(q), q_rs, q_bs, ptr(k), k_rs, k_bs, ptr(v), v_rs, v_bs, ptr(cos), ptr(sin), max_pos, t0, ptr(qo), ptr(kc),
+             kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, row, B, Lq, W, dtype_code(q), stream_ptr()),
+            work=5.0 * B * Lq * W * q.element_size())
+    cache.lengths[layer] = row + Lq
+    return qo
+
+
+def attention_chunk_splits(B, heads, Lq, Lk, D):
+    """The number of runs attention_chunk cuts every wave's key tiles into when splits = 0 (a pure function of the shape)."""
+    return int(_lib.load().apertis_attention_chunk_splits(B, heads, Lq, Lk, D))
+
+
+def attention_chunk_workspace_bytes(B, heads, Lq, D, splits):
+    """Bytes of fp32 workspace attention_chunk takes from the cache for `splits` runs (0 for one)."""
+    return int(_lib.load().apertis_attention_chunk_workspace_bytes(B, heads, Lq, D, splits))
+
+
+def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0):
+    """Causal softmax attention of the Lq rows kv_append_rope_chunk has JUST appended to layer `layer` of `cache` over
+    everything the layer holds: row i of q ([B, Lq, W], the cache's dtype, D = W / heads in {64, 128}) sits at key position
+    n + i, n = lengths[layer] - Lq, and attends keys j <= n + i.  Returns O [B, Lq, W] where out_proj reads it.  key_valid:
+    [B, >= n + Lq] (the raw attention_mask, nonzero = attend; later columns are never read) or None.  splits: 0 =
+    apertis_attention_chunk_splits' choice, else 1..ATTN_DECODE_MAX_SPLITS runs of every wave's key tiles; the same inputs and
+    split count give the same bits, and at one split row i has the bits causal_attention gives row n + i of the whole
+    sequence.  Inference only (no dropout, nothing saved for a backward)."""
+    _require_gpu(q, cache.k[layer], key_valid)
+    lib = _lib.load()
+    kc, vc = cache.k[layer], cache.v[layer]
+    B, cap, W = kc.shape
+    if q.dim() != 3 or q.shape[0] != B or q.shape[1] < 1 or not attention_decode_supported(q, heads) or q.dtype != cache.dtype:
+        raise ApertisHipError(f"attention_chunk: q {tuple(q.shape)} {q.dtype} with {heads} heads against a cache of "
+                              f"[{B}, {cap}, {W}] {cache.dtype} (D 64 or 128, fp32 or bf16, one dtype)")
+    Lq, Lk = q.shape[1], cache.lengths[layer]
+    if Lq > Lk:
+        raise ApertisHipError(f"attention_chunk: {Lq} query rows but the layer holds {Lk} (kv_append_rope_chunk first)")
+    q, q_rs = _rows(q, W)
+    if q.data_ptr() % 16 or (q_rs * q.element_size()) % 16:
+        q, q_rs = q.clone(memory_format=torch.contiguous_format), W
+    D, ns, ws = W // heads, int(splits), None              # ns: the split count the workspace is sized for AND the launch takes
+    if ns == 0:
+        ns = int(lib.apertis_attention_chunk_splits(B, heads, Lq, Lk, D)) if B else 1
+    if 1 <= ns <= ATTN_DECODE_MAX_SPLITS:
+        ws = cache._workspace(max(int(lib.apertis_attention_chunk_workspace_bytes(B, heads, Lq, D, ns)), 0))
+    kv_rs = 0
+    if key_valid is not None:
+        if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < Lk:
+            raise ApertisHipError(f"attention_chunk: key_valid {tuple(key_valid.shape)}, expected ({B}, >= {Lk})")
+        if key_valid.dtype != torch.int64 or key_valid.stride(1) != 1:
+            key_valid = key_valid.to(torch.int64).contiguous()
+        kv_rs = key_valid.stride(0) if B > 1 else key_valid.shape[1]
+    out = torch.empty(B, Lq, W, device=q.device, dtype=q.dtype)
+    _launch("apertis_attention_chunk", lib.apertis_attention_chunk,
+            (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
+             ptr(out), W, ptr(ws), B, Lq, Lk - Lq, heads, D, ns, dtype_code(q), stream_ptr()),
+            work=4.0 * B * W * Lq * (Lk - Lq + (Lq + 1) / 2), detail=f"{B}x{heads}x{D}x{Lq}",
+            nbytes=(2.0 * B * Lk + 2.0 * B * Lq) * W * q.element_size())
     return out
 
 

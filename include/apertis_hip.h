@@ -49,14 +49,15 @@ extern "C" {
  * kernel; measured 15 % SLOWER at the bench shape (profiles/r6_probe_nt2i_vs_nt4r.log), so no caller sets it by default. */
 #define APERTIS_ACT_INTERLEAVED 0x400
 
-/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.11 - apertis_rope_kv_append_at,
+/* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.12 - apertis_rope_kv_append_chunk,
+ * apertis_attention_chunk, apertis_attention_chunk_splits / _workspace_bytes: multi-token KV-cache steps; 4.11 - apertis_rope_kv_append_at,
  * apertis_attention_decode_at: the KV-cache decode step at a device-held length, for graph replay; 4.10 - apertis_rope_kv_append,
  * apertis_attention_decode, apertis_attention_decode_splits / _workspace_bytes: standard_mha KV-cache decode; 4.9 - apertis_token_counts,
  * apertis_sample_next: generate()'s penalty / temperature / top-k / top-p / draw in one launch; 4.8 - apertis_rope_qk_fwd / _bwd,
  * apertis_attention_fwd / _bwd, apertis_attention_bwd_workspace_bytes: standard_mha; round 6: 4.7 - apertis_cross_entropy_fwd_bwd, apertis_layernorm_combine_bwd; round 5: 4.5 - apertis_scan_lookback_*, apertis_tiny_linear_bwd_pad; round 4: 4.4 - lean scan
  * entry points, apertis_scan_lean_fwd_dt, apertis_grouped_gemm_tn_dense_variant, apertis_weight_prep, apertis_ssm_decode_state_dt).  A host binding should
  * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does). */
-#define APERTIS_ABI_VERSION ((4 << 16) | 11)
+#define APERTIS_ABI_VERSION ((4 << 16) | 12)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
 const char *apertis_arch(void);
@@ -825,6 +826,55 @@ int apertis_attention_decode_at(const void *q, int64_t q_rs, const void *k_cache
                                 int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *len, const int64_t *key_valid,
                                 int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t H, int64_t D,
                                 int64_t splits, int dtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * standard_mha MULTI-TOKEN steps against the same KV cache: a chunk of Lq positions per sequence (a chat turn, a piece of a
+ * long prompt) is appended to a cache that holds n rows and attended causally over rows [0, n + Lq).  Inference only: no
+ * dropout, no LSE, no backward.  Cache layout and strides as above.
+ *
+ * apertis_rope_kv_append_chunk, one launch per layer and step: q, k, v are [B, Lq, W] with a row stride (*_rs >= W) and a batch
+ * stride (*_bs >= Lq * row stride) each.  Row l is rotated at position t0 + l exactly as apertis_rope_qk_fwd does (the same
+ * device code, the same bits, fp32 and bf16); rotated q goes to q_out [B, Lq, W] (contiguous), rotated k and unrotated v into
+ * cache row t_cache0 + l.
+ *   cos/sin_cached: fp32 [max_pos, W/2], or both NULL for no rotation (a plain append; q_out = q)
+ *   t0            : first rotary position, by value; t0 >= -max_pos and t0 + Lq <= max_pos (negative positions wrap), else
+ *                   APERTIS_ERR_ARG
+ *   t_cache0      : first cache row, by value; 0 <= t_cache0 and t_cache0 + Lq <= cap, else APERTIS_ERR_ARG
+ *   Every refusal comes before any launch: nothing is written.  Lq = 0 or B = 0 writes nothing and returns APERTIS_OK.
+ *
+ * apertis_attention_chunk: O[b,i,h] = sum_j P[i,j] V[b,j,h], P = softmax over j <= n + i with key_valid[b,j] != 0 of
+ * scale * q[b,i,h].K[b,j,h], scale = 1/sqrt(D) in fp32 - query row i of the chunk sits at key position n + i (its own key, which
+ * the append above wrote, included).  The algorithm, the tile step and the MFMA instructions are apertis_attention_fwd's (bf16:
+ * P rounded to bf16 for P.V; fp32 accumulation): with splits = 1 row i gets the bits apertis_attention_fwd gives row n + i of
+ * the whole sequence of n + Lq positions.
+ *   q, out        : [B, Lq, W] with row strides q_rs, out_rs (batch stride Lq * row stride)
+ *   n             : rows the cache held before the chunk, by value; n >= 0, Lq >= 1, n + Lq <= cap, else APERTIS_ERR_ARG
+ *   key_valid     : int64 [B, >= n + Lq] with row stride kv_rs (else APERTIS_ERR_ARG), or NULL.  A row with no valid key gets
+ *                   O = 0 (callers keep such rows off this path).  Cache rows >= n + Lq, mask columns >= n + Lq and the cache
+ *                   rows of masked keys are never read.
+ *   D             : 64 or 128, B * H <= 65535, q / out / cache pointers and every stride on 16-byte boundaries, else
+ *                   APERTIS_ERR_UNSUPPORTED; dtype fp32 or bf16
+ *   splits        : every wave (16 query rows) cuts its 32-key tiles into `splits` runs, one work-group each (grid
+ *                   ceil(Lq/64) x B*H x splits); 0 takes apertis_attention_chunk_splits(B, H, Lq, Lk = n + Lq, D) - the decode
+ *                   rule's form counted in waves, min(2048 / (B*H*ceil(Lq/16)), Lk / 64, APERTIS_ATTN_DECODE_MAX_SPLITS) in
+ *                   integers, at least 1 (-1 for a size < 1 or Lk < Lq): about two waves per SIMD, at least two tiles per run.
+ *                   Forced: 1..APERTIS_ATTN_DECODE_MAX_SPLITS, not bounded by the number of tiles: an empty run leaves
+ *                   (m = -inf, l = 0, o = 0), which the fold passes over.
+ *   workspace     : with splits > 1, apertis_attention_chunk_workspace_bytes bytes, 16-byte aligned (fp32 (m, l) and o[D] per
+ *                   (row, head, run); 0 bytes for splits = 1, -1 for a bad argument), folded in run order by the decode's merge
+ *                   launch over B * Lq rows.  With splits = 1 the one launch writes out and workspace may be NULL.
+ * No atomics, no waiting between work-groups: the same inputs and split count give the same bits on every run. */
+int apertis_rope_kv_append_chunk(const void *q, int64_t q_rs, int64_t q_bs, const void *k, int64_t k_rs, int64_t k_bs,
+                                 const void *v, int64_t v_rs, int64_t v_bs, const float *cos_cached, const float *sin_cached,
+                                 int64_t max_pos, int64_t t0, void *q_out, void *k_cache, int64_t kc_rs, int64_t kc_bs,
+                                 void *v_cache, int64_t vc_rs, int64_t vc_bs, int64_t cap, int64_t t_cache0, int64_t B,
+                                 int64_t Lq, int64_t W, int dtype, void *stream);
+int64_t apertis_attention_chunk_splits(int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D);
+int64_t apertis_attention_chunk_workspace_bytes(int64_t B, int64_t H, int64_t Lq, int64_t D, int64_t splits);
+int apertis_attention_chunk(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs, const void *v_cache,
+                            int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid, int64_t kv_rs, void *out,
+                            int64_t out_rs, float *workspace, int64_t B, int64_t Lq, int64_t n, int64_t H, int64_t D,
+                            int64_t splits, int dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * generate()'s next-token selection (core.py:1605-1633), one launch per token step, one 1024-thread work-group per row.
