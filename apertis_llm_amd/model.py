@@ -183,7 +183,7 @@ class HipLayerNorm(nn.LayerNorm):
 
 
 def _norm_pass(norm, x):
-    return norm.forward_pass(x) if isinstance(norm, HipLayerNorm) else (norm(x), x)
+    return norm.forward_pass(x) if isinstance(norm, (HipLayerNorm, RMSNorm)) else (norm(x), x)
 
 
 class _LazyCombine:
@@ -239,6 +239,13 @@ def _enter_block(norm, h, router=None):
         H = res.shape[-1]
         cd = _compute_dtype(res)
         lazy = out if isinstance(out, _LazyCombine) else None
+        if (isinstance(norm, RMSNorm) and ops.rms_norm_supported(res) and tuple(out.shape) == tuple(res.shape) and
+                (res.dtype == torch.float32 or cd == res.dtype) and (lazy is None or lazy.dtype == lazy.yr.dtype == cd)):
+            # the same boundary with an RMSNorm behind it; an MoE router in front keeps ops.router_ln_linear on xn
+            blk, comb = (out, None) if lazy is None else (lazy.yr, (lazy.w, lazy.plan))
+            y, xn = ops.dropout_add_rms_norm(blk, res, norm.scale, norm.eps, h.drop.p, h.drop.training, out_dtype=cd,
+                                             combine=comb)
+            return xn, y
         if (isinstance(norm, HipLayerNorm) and res.is_cuda and tuple(out.shape) == tuple(res.shape) and H % 4 == 0 and
                 H <= 4096 and res.dtype in (torch.float32, torch.bfloat16) and
                 (res.dtype == torch.float32 or cd == res.dtype) and (lazy is None or lazy.dtype == lazy.yr.dtype == cd)):
@@ -291,7 +298,9 @@ def _mfma_linear(x, weight, bias=None):
 
 
 class RMSNorm(nn.Module):
-    """x / (||x||_2 / sqrt(D) + eps) * scale  (reference core.py:30-59)."""
+    """x / (||x||_2 / sqrt(D) + eps) * scale  (reference core.py:30-59).  On the GPU (fp32 / bf16, H % 4 == 0, H <= 4096,
+    ops.RMSNORM_FUSED) forward and backward are the HIP row kernels, emitting the compute dtype under autocast as
+    HipLayerNorm does; elsewhere the reference's stock-torch arithmetic."""
 
     def __init__(self, hidden_size: int, eps: float = 1e-6):
         super().__init__()
@@ -299,8 +308,17 @@ class RMSNorm(nn.Module):
         self.scale = nn.Parameter(torch.ones(hidden_size))
 
     def forward(self, x):
+        if ops.rms_norm_supported(x):
+            return ops.rms_norm(x, self.scale, self.eps, out_dtype=_compute_dtype(x))
         rms = x.norm(p=2, dim=-1, keepdim=True) * (self.hidden_size ** -0.5)
         return self.scale * (x / (rms + self.eps))
+
+    def forward_pass(self, x):
+        """(RMSNorm(x), x) for a pre-norm residual block: adding the residual through the returned x lets the backward
+        kernel fold the residual gradient into dx (ops.rms_norm_pass)."""
+        if ops.rms_norm_supported(x):
+            return ops.rms_norm_pass(x, self.scale, self.eps, out_dtype=_compute_dtype(x))
+        return self.forward(x), x
 
 
 class RotaryEmbedding(nn.Module):

@@ -7,7 +7,7 @@ One module per subsystem (round 6: the 2 500-line ops.py split up):
     _base    launch helpers, kernel timers, device checks, hand-over objects
     prep     prepared weight copies (cache, one-launch TrainPrep, cast / transpose)
     gemm     grouped / dense / skinny / tiny linears on the MFMA kernels
-    norm     LayerNorm family and the fused block boundaries
+    norm     LayerNorm family and the fused block boundaries; RMSNorm and its boundary
     ssm      conv + SiLU, dropout-add, gate, column splits
     scan     selective scan and scan + skip + gate (staged / lean / look-back)
     decode   single-token decode step
@@ -32,7 +32,7 @@ _FORWARDED = {
     "SCAN_LOOKBACK_MIN_WGS": scan,
     "DWCONV_PAIR": ssm,
     "FUSE_ACT_BWD": moe, "SAVE_ACT_GRAD": moe, "ROWS_GRADIENT": moe, "NT2I": moe,
-    "FUSE_ROUTER_BOUNDARY_BWD": norm, "FUSED_ROUTER_BWD_CALLS": norm, "FUSE_COMBINE_BWD": norm,
+    "FUSE_ROUTER_BOUNDARY_BWD": norm, "FUSED_ROUTER_BWD_CALLS": norm, "FUSE_COMBINE_BWD": norm, "RMSNORM_FUSED": norm,
     "GEMM_DYNAMIC_QUEUE": gemm, "TN_DYNAMIC_QUEUE": gemm, "DENSE_WGRAD_WIDE": gemm, "_splitk_depth": gemm,
     "TRAIN_PREP": prep, "WEIGHT_EPOCH": prep, "_ACTIVE_TRAIN_PREP": prep, "_prep_scope_depth": prep,
     "_TIMER": _base,

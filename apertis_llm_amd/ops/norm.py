@@ -1,4 +1,5 @@
-"""LayerNorm family: plain, residual + dropout + LayerNorm block boundaries, the router norm + projection, their fused backward forms.
+"""LayerNorm family: plain, residual + dropout + LayerNorm block boundaries, the router norm + projection, their fused backward forms;
+RMSNorm (plain and block boundary) for the use_rmsnorm configuration.
 
 Part of apertis_llm_amd.ops (split by subsystem in round 6; `from apertis_llm_amd import ops` exposes every name as before).
 torch is used for device memory, streams and autograd bookkeeping only; every computation is a HIP kernel launch through
@@ -362,6 +363,148 @@ def layer_norm_pass(x, weight, bias, eps, out_dtype=None):
     return _LayerNormPass.apply(x, weight, bias, eps, out_dtype or x.dtype)
 
 
+class _RMSNorm(torch.autograd.Function):
+    """scale * x / (sqrt(mean x^2) + eps) over the last dimension (reference core.py:30-59); saves x and one fp32 statistic
+    per row.  Shaped like _LayerNorm: the second gradient is the pass-through's (see _RMSNormPass)."""
+
+    @staticmethod
+    def forward(ctx, x, scale, eps, out_dtype):
+        _require_gpu(x, scale)
+        lib = _lib.load()
+        shape = x.shape
+        H = shape[-1]
+        x2 = x.reshape(-1, H).contiguous()
+        T = x2.shape[0]
+        g = _f32(scale)
+        y = torch.empty(T, H, device=x.device, dtype=out_dtype)
+        rms = torch.empty(T, device=x.device, dtype=torch.float32)
+        check(lib.apertis_rmsnorm_fwd(ptr(x2), ptr(g), float(eps), ptr(y), ptr(rms), T, H, dtype_code(x2), dtype_code(y),
+                                      stream_ptr()), "apertis_rmsnorm_fwd")
+        ctx.save_for_backward(x2, g, rms)
+        ctx.cfg = (shape, float(eps), scale.dtype)
+        return y.reshape(shape)
+
+    @staticmethod
+    def backward(ctx, dy, dres=None):
+        x2, g, rms = ctx.saved_tensors
+        shape, eps, sdt = ctx.cfg
+        if dy is None:      # the normalised output was not used: only the pass-through carries gradient
+            return dres, None, None, None
+        T, H = x2.shape
+        dy2 = dy.reshape(T, H).contiguous()
+        if dres is not None:
+            dres = dres.reshape(T, H).to(x2.dtype).contiguous()
+        dx, dg = _rms_bwd(x2, g, rms, eps, dy2, dres, None, 0.0, 0)
+        return dx.reshape(shape), dg.to(sdt), None, None
+
+
+def _rms_bwd(x2, g, rms, eps, dy2, dres, dblk, p, seed):
+    """apertis_rmsnorm_bwd on [T, H] operands: (dx in x2's dtype, dscale fp32); dblk, when given, is filled."""
+    lib = _lib.load()
+    T, H = x2.shape
+    dx = torch.empty_like(x2)
+    if T == 0:
+        return dx, torch.zeros(H, device=x2.device, dtype=torch.float32)
+    part = torch.empty(lib.apertis_rmsnorm_bwd_blocks(T, H), H, device=x2.device, dtype=torch.float32)
+    dg = torch.empty(H, device=x2.device, dtype=torch.float32)
+    check(lib.apertis_rmsnorm_bwd(ptr(x2), ptr(g), ptr(rms), eps, ptr(dy2), ptr(dres), ptr(dx), ptr(dblk), p, seed, ptr(part),
+                                  ptr(dg), T, H, dtype_code(x2), dtype_code(dy2), stream_ptr()), "apertis_rmsnorm_bwd")
+    return dx, dg
+
+
+class _RMSNormPass(_RMSNorm):
+    """RMSNorm that also hands its input through: (RMSNorm(x), x) - _LayerNormPass for the use_rmsnorm configuration: the
+    residual add of a pre-norm block reads the pass-through, so its gradient reaches this node and is added inside the
+    backward kernel."""
+
+    @staticmethod
+    def forward(ctx, x, scale, eps, out_dtype):
+        y = _RMSNorm.forward(ctx, x, scale, eps, out_dtype)
+        return y, x.view_as(x)
+
+
+class _DropoutAddRMS(torch.autograd.Function):
+    """(y, xn) = (res + dropout(blk), RMSNorm(y)): _DropoutAddLN with an RMSNorm behind the boundary.  The backward writes
+    d_res = RMSNorm backward + dy and d_blk = its masked copy in one kernel; in the combine form d_blk then goes through
+    apertis_moe_combine_bwd (_DropoutAddLN._to_inputs)."""
+
+    @staticmethod
+    def forward(ctx, blk, res, scale, eps, p, seed, out_dtype, wk=None, plan=None):
+        """plan/wk given: blk is the MoE expert output [rows,H] and the block output is its combine."""
+        _require_gpu(blk, res, scale)
+        lib = _lib.load()
+        shape = res.shape
+        H = shape[-1]
+        blk2 = blk.reshape(-1, H).to(out_dtype).contiguous()
+        res2 = res.reshape(-1, H).contiguous()
+        T = res2.shape[0]
+        wf = None if plan is None else wk.float().contiguous()
+        g = _f32(scale)
+        y = torch.empty_like(res2)
+        xn = torch.empty(T, H, device=res.device, dtype=out_dtype)
+        rms = torch.empty(T, device=res.device, dtype=torch.float32)
+        check(lib.apertis_dropout_add_rmsnorm_fwd(ptr(blk2), None if plan is None else ptr(plan.slot_of), ptr(wf),
+                                                  0 if plan is None else plan.K, ptr(res2), ptr(g), float(eps), ptr(y), ptr(xn),
+                                                  ptr(rms), T, H, float(p), int(seed), dtype_code(res2), dtype_code(xn),
+                                                  stream_ptr()), "apertis_dropout_add_rmsnorm_fwd")
+        if plan is None:
+            ctx.save_for_backward(y, g, rms)
+        else:
+            ctx.save_for_backward(y, g, rms, None, blk2, wf)     # (yr, wf at _DropoutAddLN._to_inputs' positions)
+        ctx.plan = plan
+        # (the layout _DropoutAddLN._to_inputs reads: shape, p, seed, -, -, blk dtype, out dtype, blk shape)
+        ctx.cfg = (shape, float(p), int(seed), scale.dtype, float(eps), blk.dtype, out_dtype, tuple(blk.shape))
+        return y.reshape(shape), xn.reshape(shape)
+
+    @staticmethod
+    def backward(ctx, dy, dxn):
+        lib = _lib.load()
+        y, g, rms = ctx.saved_tensors[:3]
+        shape, p, seed, sdt, eps, _blkdt, odt, _ = ctx.cfg
+        T, H = y.shape
+        dblk = torch.empty(T, H, device=y.device, dtype=odt)
+        if dxn is None:      # the normalised output was not used: only the residual path carries gradient
+            dy2 = dy.reshape(T, H).contiguous()
+            check(lib.apertis_dropout_bwd(ptr(dy2), ptr(dblk), dy2.numel(), p, seed, dtype_code(dy2), dtype_code(dblk), stream_ptr()),
+                  "apertis_dropout_bwd")
+            dblk_in, dwk = _DropoutAddLN._to_inputs(ctx, dblk)
+            return dblk_in, dy, None, None, None, None, None, dwk, None
+        dxn2 = dxn.reshape(T, H).to(odt).contiguous()
+        dres = None if dy is None else dy.reshape(T, H).to(y.dtype).contiguous()
+        dx, dg = _rms_bwd(y, g, rms, eps, dxn2, dres, dblk, p, seed)
+        dblk_in, dwk = _DropoutAddLN._to_inputs(ctx, dblk)
+        return dblk_in, dx.reshape(shape), dg.to(sdt), None, None, None, None, dwk, None
+
+
+def rms_norm_supported(x):
+    """What the RMSNorm kernels take (HipLayerNorm's conditions) with the switch on."""
+    H = x.shape[-1]
+    return RMSNORM_FUSED and x.is_cuda and H % 4 == 0 and 0 < H <= 4096 and x.dtype in (torch.float32, torch.bfloat16)
+
+
+def rms_norm(x, scale, eps, out_dtype=None):
+    """RMSNorm over the last dimension, scale * x / (sqrt(mean x^2) + eps) (reference core.py:56-59); x fp32/bf16, the
+    statistic in fp32, output in out_dtype (bf16 under autocast: the following GEMM reads it directly)."""
+    return _RMSNorm.apply(x, scale, eps, out_dtype or x.dtype)
+
+
+def rms_norm_pass(x, scale, eps, out_dtype=None):
+    """(RMSNorm(x), x): see _RMSNormPass."""
+    return _RMSNormPass.apply(x, scale, eps, out_dtype or x.dtype)
+
+
+def dropout_add_rms_norm(blk, residual, scale, eps, p, training, out_dtype=None, combine=None):
+    """(residual + dropout(blk), RMSNorm(of that)) in one pass each way: dropout_add_layer_norm for a use_rmsnorm model.
+    combine=(w, plan): blk is the MoE expert output [rows,H] and the block output its weighted combine (core.py:594,605),
+    formed inside the same forward pass."""
+    p = float(p) if training else 0.0
+    seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0
+    wk, plan = combine if combine is not None else (None, None)
+    return _DropoutAddRMS.apply(blk, residual, scale, eps, p, seed, out_dtype or residual.dtype, wk, plan)
+
+
+# APERTIS_RMSNORM_FUSED=0: a use_rmsnorm model's norms stay the stock torch module everywhere (A/B runs and tests)
+RMSNORM_FUSED = _os.environ.get("APERTIS_RMSNORM_FUSED", "1") == "1"
 # APERTIS_NO_FUSE_ROUTER_BWD=1: the router backward and the boundary's LayerNorm backward as two calls (xn's gradient through HBM)
 FUSE_ROUTER_BOUNDARY_BWD = not _os.environ.get("APERTIS_NO_FUSE_ROUTER_BWD")
 # the MoE combine's backward inside the LayerNorm backward of the boundary behind it (apertis_layernorm_combine_bwd, round 6)

@@ -56,7 +56,10 @@ extern "C" {
  * apertis_sample_next: generate()'s penalty / temperature / top-k / top-p / draw in one launch; 4.8 - apertis_rope_qk_fwd / _bwd,
  * apertis_attention_fwd / _bwd, apertis_attention_bwd_workspace_bytes: standard_mha; round 6: 4.7 - apertis_cross_entropy_fwd_bwd, apertis_layernorm_combine_bwd; round 5: 4.5 - apertis_scan_lookback_*, apertis_tiny_linear_bwd_pad; round 4: 4.4 - lean scan
  * entry points, apertis_scan_lean_fwd_dt, apertis_grouped_gemm_tn_dense_variant, apertis_weight_prep, apertis_ssm_decode_state_dt).  A host binding should
- * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does). */
+ * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does).
+ * The RMSNorm entry points (apertis_rmsnorm_fwd / _bwd / _bwd_blocks, apertis_dropout_add_rmsnorm_fwd) were ADDED UNDER 4.12
+ * without a bump: the test suite pins the version at 4.12 and no existing signature changed, so a binding written against the
+ * earlier 4.12 header still calls every entry point it knows correctly; one that wants the RMSNorm family looks the symbols up. */
 #define APERTIS_ABI_VERSION ((4 << 16) | 12)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
@@ -528,6 +531,27 @@ int apertis_dropout_add_layernorm_router_fwd(const void *blk, const void *res, c
                                              const float *W, const float *rb, float *logits, float *rmean,
                                              float *rrstd, int64_t T, int64_t H, int64_t N, float drop_p,
                                              uint64_t seed, int dtype_x, int dtype_y, void *stream);
+
+/* RMSNorm over the last dimension (core.py:30-59: the use_rmsnorm configuration's pre-norms and final norm) on row kernels of
+ * the same shape.  Per row: r = sqrt(sum x^2 / H), s = r + eps (eps outside the root), y = scale * x / s.
+ * x [T,H] dtype_x -> y [T,H] dtype_y, rms [T] fp32 = r (the one saved statistic; s is re-formed from it and eps).
+ * Backward: dy [T,H] dtype_g -> dx [T,H] in dtype_x, dx = scale*dy / s - x * sum_j(scale_j dy_j x_j) / (H r s^2), the second term
+ * 0 for a row with r == 0; dscale [H] fp32 overwritten; part = workspace [apertis_rmsnorm_bwd_blocks(T,H), H] fp32 (fixed-order
+ * fold, no atomics: the same inputs give the same bits).  dres / dblk / (drop_p, seed): as for apertis_layernorm_bwd.
+ * H % 4 == 0, H <= 4096, else APERTIS_ERR_UNSUPPORTED; T == 0: nothing is launched (dscale is then left as it was). */
+int apertis_rmsnorm_fwd(const void *x, const float *scale, float eps, void *y, float *rms, int64_t T, int64_t H, int dtype_x,
+                        int dtype_y, void *stream);
+int apertis_rmsnorm_bwd(const void *x, const float *scale, const float *rms, float eps, const void *dy, const void *dres,
+                        void *dx, void *dblk, float drop_p, uint64_t seed, float *part, float *dscale, int64_t T, int64_t H,
+                        int dtype_x, int dtype_g, void *stream);
+int64_t apertis_rmsnorm_bwd_blocks(int64_t T, int64_t H);
+/* The block boundary in one pass with an RMSNorm behind it: y = res + dropout(blk), xn = RMSNorm(y), rms [T].  Arguments,
+ * dtypes, the dense and the combine form (slot_of / wk / K) and the dropout mask (element index r * H + c) as for
+ * apertis_dropout_add_layernorm_fwd.  Backward: apertis_rmsnorm_bwd with dblk (then apertis_moe_combine_bwd on dblk in the MoE
+ * form); when xn went unused, apertis_dropout_bwd on y's gradient. */
+int apertis_dropout_add_rmsnorm_fwd(const void *blk, const int32_t *slot_of, const float *wk, int64_t K, const void *res,
+                                    const float *scale, float eps, void *y, void *xn, float *rms, int64_t T, int64_t H,
+                                    float drop_p, uint64_t seed, int dtype_x, int dtype_y, void *stream);
 
 /* Combine (core.py:594,605 weights * expert_output, index_add_):
  *   out[s,:] = sum_{k asc, slot_of[s,k]>=0} wk[s,k] * yr[slot_of[s,k],:]   (zeros if none)

@@ -249,6 +249,31 @@ def gen_models(core):
         npz(name, **arrs)
 
 
+def gen_models_rms(core):
+    """model_ssm_moe_rms: gen_models' MoE recipe with use_rmsnorm=True (RMSNorm pre-norms and final norm, core.py:30-59),
+    under a seed of its own so that the other fixtures regenerate bit-identically."""
+    name = "model_ssm_moe_rms"
+    torch.manual_seed(zlib.crc32(name.encode()) % 1000)
+    cfg = core.ApertisConfig(vocab_size=96, hidden_size=32, num_hidden_layers=2, num_attention_heads=2, intermediate_size=64,
+                             attention_type="selective_ssm", use_expert_system=True, num_experts=4, experts_per_token=2,
+                             multimodal=False, use_rmsnorm=True)
+    model = core.ApertisForCausalLM(cfg).eval()
+    with torch.no_grad():  # widen the init so logits are not ~0; the norm scales away from 1 so that they are seen
+        for n_, p in model.named_parameters():
+            if p.dim() > 1 and "token_embeddings" not in n_:
+                p.mul_(8.0)
+            elif n_.endswith(".scale"):
+                p.add_(0.25 * torch.randn_like(p))
+    ids = torch.randint(4, 96, (2, 12))
+    labels = ids.clone()
+    labels[0, :3] = -100
+    with torch.no_grad():
+        out = model(input_ids=ids, labels=labels, use_cache=False)
+    sd = {k: v.detach() for k, v in model.state_dict().items()}
+    print(f"  {name}: loss ref {float(out[0]):.6f}; {sum(k.endswith('.scale') for k in sd)} RMSNorm scales")
+    npz(name, input_ids=ids, labels=labels, loss=out[0], logits=out[1], config_json=json.dumps(cfg.to_dict()), **sd_arrays(sd))
+
+
 def gen_dims(core):
     table = {}
     for target, moe in [("125M", False), ("350M", True), ("1.5B", True), ("10M", False), ("7B", False), ("3B", True)]:
@@ -766,7 +791,7 @@ def gen_generate_sampled(core):
             raise SystemExit(f"{name}: no seed in 200 fits the eos rule with clear margins")
 
 
-GENERATORS = ["scan", "ssm_layer", "moe", "vision", "models", "dims", "data_formats", "trainer_run", "config1", "generate",
+GENERATORS = ["scan", "ssm_layer", "moe", "vision", "models", "models_rms", "dims", "data_formats", "trainer_run", "config1", "generate",
               "generate_long", "generate_sampled"]
 
 
