@@ -551,7 +551,11 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // (LDS-DMA arrivals are waited for explicitly with wait_vmcnt where a barrier publishes them).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// a tile of a persistent NT kernel's walk (nt256p, nt352p, nt4r)
 struct PTile { int valid, e, rows_valid, n0, cols_valid; int64_t row0; };
+// `solo` of nt256p and nt352p: the K steps of a tile whose DMA the non-store waves issue alone (nt256p: measured best of 2..6;
+// nt352p, re-measured with the spread fills in round 3: 0..6 all within noise)
+constexpr int NT_SOLO = 4;
 
 // Dynamic tile queue of the persistent kernel (queue != NULL): after its first (static, XCD-affine) tile a work-group
 // takes tile indices from device counters, so a work-group that starts late - its CU was held by another kernel, e.g. an
@@ -1412,9 +1416,6 @@ grouped_gemm_nt2x_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
 // ------------------------------------------------------------------------------------------
 // KS > 1 (long K: the experts' second GEMM, K = I): KS waves of a work-group split the K range, their partial sums meet in LDS
 // and wave 0 adds them in wave order - a wave alone walked 88 dependent load -> MFMA batches' worth of K = 2816.
-#ifndef SKINNY_LONG_K_WAVES
-#define SKINNY_LONG_K_WAVES 16      // (probe switch: 4 = the K >= 512 form for every long K)
-#endif
 template <typename TO, int KS>
 __global__ void __launch_bounds__(64 * KS)
 grouped_gemm_nt_skinny_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, const float *__restrict__ bias,
@@ -1501,8 +1502,6 @@ constexpr int NT4 = 512, BM4 = 256, BN4 = 256, ROWB4 = 64;
 constexpr int SLOT4 = (BM4 + BN4) * ROWB4;   // 32 KiB: X rows, then W rows
 constexpr int RING4 = 4 * SLOT4;
 
-struct Tile4 { int valid, e, rows_valid, n0, cols_valid; int64_t row0; };
-
 template <typename TO, bool RAGGED = false, bool DYN = false>   // DYN: the dynamic tile queue (its own instantiation: as a run-time
 // switch its bookkeeping cost the static walk 5 % - 1229 against 1165 us per call, profiles/r6_nt4r_queue_static_cost.log)
 __global__ void __launch_bounds__(NT4)
@@ -1524,8 +1523,8 @@ grouped_gemm_nt4r_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
   const int S = pre_act ? 32 : 16;   // (two outputs, or a pre-activation pass and the activation pass)
 
   // virtual tile index -> tile (the two-per-CU kernel's order: an XCD takes a contiguous run, n-panel-stationary inside)
-  auto decode = [&](int v) -> Tile4 {
-    Tile4 t; t.valid = 0; t.e = 0; t.rows_valid = 0; t.n0 = 0; t.cols_valid = 0; t.row0 = 0;
+  auto decode = [&](int v) -> PTile {
+    PTile t; t.valid = 0; t.e = 0; t.rows_valid = 0; t.n0 = 0; t.cols_valid = 0; t.row0 = 0;
     const int tile = xcd_remap(v, total_tiles);
     int mt, ntile;
     tile_walk(tile, total_tiles / n_tiles, n_tiles, walk_g, walk_nb, mt, ntile);
@@ -1548,8 +1547,8 @@ grouped_gemm_nt4r_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
     return t;
   };
   int vnext = blockIdx.x;
-  auto next_valid = [&]() -> Tile4 {
-    Tile4 t; t.valid = 0; t.e = 0; t.rows_valid = 0; t.n0 = 0; t.cols_valid = 0; t.row0 = 0;
+  auto next_valid = [&]() -> PTile {
+    PTile t; t.valid = 0; t.e = 0; t.rows_valid = 0; t.n0 = 0; t.cols_valid = 0; t.row0 = 0;
     while (vnext < total_tiles) {
       t = decode(vnext);
       vnext += G;
@@ -1607,7 +1606,7 @@ grouped_gemm_nt4r_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
                  : "=v"(tkv), "=&s"(saved_exec) : "v"(addr), "v"(1), "s"(mask) : "memory");
   };
 
-  Tile4 cur = next_valid();
+  PTile cur = next_valid();
   if constexpr (dyn) if (!cur.valid) {   // (the static first tile fell on padding: nothing is in flight yet, the slow path costs nothing)
     if (tid == 0) s_tk[1] = steal();
     __syncthreads();
@@ -1628,7 +1627,7 @@ grouped_gemm_nt4r_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
   const uint32_t lds0 = lds_addr_of(smem);
   v4i fxrs, fwrs, fbrs;
   int fs = 0, fvalid = 1;
-  auto set_fill = [&](const Tile4 &t) {
+  auto set_fill = [&](const PTile &t) {
     fxrs = raw_buffer_rsrc(X + t.row0 * K, t.valid ? (uint32_t)t.rows_valid * (uint32_t)ldb : 0u);
     fwrs = raw_buffer_rsrc(W + ((int64_t)t.e * N + t.n0) * ldw, t.valid ? (uint32_t)t.cols_valid * (uint32_t)ldwb : 0u);
     if (bias) fbrs = raw_buffer_rsrc(bias + (int64_t)t.e * N + t.n0, t.valid ? (uint32_t)t.cols_valid * 4u : 0u);
@@ -1649,7 +1648,7 @@ grouped_gemm_nt4r_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
     if (q < 2) lds_dma16s(fxrs, base + (wave * 2 + q) * 1024, vx0 + (uint32_t)(q * 16 * ldb) + kv, ks);
     else lds_dma16s(fwrs, base + BM4 * ROWB4 + (wave * 2 + (q - 2)) * 1024, vw0 + wp0 + (uint32_t)((q - 2) * ldwb) + kv, ks);
   };
-  Tile4 nxt;   // the tile after cur (decoded at the top of cur, entered by the fill pointer four sub-steps before cur ends)
+  PTile nxt;   // the tile after cur (decoded at the top of cur, entered by the fill pointer four sub-steps before cur ends)
   nxt.valid = 0; nxt.e = 0; nxt.rows_valid = 0; nxt.n0 = 0; nxt.cols_valid = 0; nxt.row0 = 0;
 
   f32x4 acc[4][8];
@@ -1662,9 +1661,7 @@ grouped_gemm_nt4r_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
   // of the fill stage go out behind the first four MFMA groups (round 3: a wave sits in each `buffer_load ... lds` until the
   // address unit has taken it).  Straight-line on purpose: a uniform branch inside the run joins control flow, and hipcc then
   // waits for the LDS reads in flight at every join (lgkmcnt(0) in front of the next MFMA group).
-  // LATE: the pieces behind the LAST four groups - waves 4-7, so that the two waves of a SIMD (w and w + 4, which run this
-  // code in lock-step behind the barrier) are not both parked in the address unit's queue while the matrix pipe idles.
-  auto sub_step = [&](const frag (&acur)[4], frag (&anxt)[4], int nxt_off, uint32_t fill_off, bool late) {
+  auto sub_step = [&](const frag (&acur)[4], frag (&anxt)[4], int nxt_off, uint32_t fill_off) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (j == 0) { anxt[0] = *reinterpret_cast<const frag *>(abase + nxt_off); anxt[1] = *reinterpret_cast<const frag *>(abase + nxt_off + 16 * ROWB4); }
@@ -1673,20 +1670,15 @@ grouped_gemm_nt4r_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
       for (int i = 0; i < 4; ++i) mma(acc[i][j], acur[i], bfr[j]);
       bfr[j] = *reinterpret_cast<const frag *>(bbase + nxt_off + j * 16 * ROWB4);
       __builtin_amdgcn_sched_barrier(0);
-      // (a wave-uniform branch around the hand-issued piece only: nothing the compiler tracks is pending differently on its
-      // two sides, so the join costs no wait)
-      if (late == (j >= 4)) issue_piece(fill_off, j & 3);
+      if (j < 4) issue_piece(fill_off, j);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  // (measured at B = 44, K = 704: 1037-1045 us with the pieces of waves 4-7 behind the LAST four groups, 1013 without; wave
-  //  priorities move time between the K loop and the epilogue, not the sum - profiles/r4_probe_nt4r_stagger.log)
-#define NT4R_STAGGER 0
-#define NT4R_BARRIER lds_barrier();
-#define NT4R_PRIO 0    // 0: every wave at priority 1 inside the MFMA run; 1: waves 4-7 at priority 1 throughout, waves 0-3 at 0
-  // (a per-wave branch between an EARLY and a LATE copy of the whole run made hipcc spill the accumulators: 528 B of scratch)
-  const bool late = NT4R_STAGGER && wave >= 4;
-  if (NT4R_PRIO == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);
+  // Every wave issues its pieces behind the FIRST four groups and runs at priority 1 inside the MFMA run.  (Measured at B = 44,
+  // K = 704: 1037-1045 us with the pieces of waves 4-7 behind the LAST four groups - so that the two waves of a SIMD are not both
+  // parked in the address unit's queue - against 1013 without; waves 4-7 at priority 1 throughout and waves 0-3 at 0 moved time
+  // between the K loop and the epilogue, not the sum - profiles/r4_probe_nt4r_stagger.log.  A per-wave branch between an early
+  // and a late copy of the whole run made hipcc spill the accumulators: 528 B of scratch.)
 
   // prologue: the first four stages (nk >= 5: all of cur), stage 0's fragments
   if (bias) issue_bias();
@@ -1736,11 +1728,11 @@ grouped_gemm_nt4r_k(const bf16_t *__restrict__ X, const bf16_t *__restrict__ W, 
       if ((S_) < 3 && dyn && wave == 0) {   /* wave 0's ticket atomic behind the stores: one more operation may pass there */ \
         if (stores_behind == 0) wait_vmcnt<9>(); else if (stores_behind == 16) wait_vmcnt<25>(); else wait_vmcnt<41>(); \
       } else if (stores_behind == 0) wait_vmcnt<8>(); else if (stores_behind == 16) wait_vmcnt<24>(); else wait_vmcnt<40>(); \
-      NT4R_BARRIER                                                                                             \
+      lds_barrier();                                                                                           \
       if (fs == 0 && bias && fvalid) issue_bias();                                                             \
-      if (NT4R_PRIO == 0) __builtin_amdgcn_s_setprio(1);                                                       \
-      sub_step(AC, AN, nxt_off, (uint32_t)cur_off, late);                                                      \
-      if (NT4R_PRIO == 0) __builtin_amdgcn_s_setprio(0);                                                       \
+      __builtin_amdgcn_s_setprio(1);                                                                           \
+      sub_step(AC, AN, nxt_off, (uint32_t)cur_off);                                                            \
+      __builtin_amdgcn_s_setprio(0);                                                                           \
       if (++fs == nk) { fs = 0; set_fill(nxt); }                                                               \
       cur_off = nxt_off;                                                                                       \
     }
@@ -2151,10 +2143,10 @@ int launch_tn2(const TnProblem &q0, const TnProblem &q1, const int32_t *offsets,
 // given a round of their own: each is split along the rows into cpg/rem slices, one per CU, whose
 // partial tiles go to the caller's workspace and are summed in slice order by tn3_fold_k
 // (deterministic; no atomics).  With E=1 this is an ordinary split-K GEMM.
-// Operand images As[64 k][256 m], Bs[64 k][256 n] (512-byte k-rows) arrive by buffer_load...lds
+// Operand images As[32 k][256 m], Bs[32 k][256 n] (512-byte k-rows) arrive by buffer_load...lds
 // through descriptors sized to the group's rows - rows past the end read as zero, so there is no
-// tail path - double-buffered (2 x 64 KiB); the transposed fragment reads and the 32-byte window
-// swizzle are v2's.  The bias gradient (column sums of A) comes from the matrix pipe as well: one
+// tail path - on a ring of four 32 KiB slots (in the kernel); the transposed fragment reads and the
+// 32-byte window swizzle are v2's.  The bias gradient (column sums of A) comes from the matrix pipe as well: one
 // extra MFMA per k-block against an all-ones fragment, two m-subtiles per wave.
 // ------------------------------------------------------------------------------------------
 struct Tn3Problem {
@@ -2191,7 +2183,6 @@ __host__ __device__ inline Tn3Sched tn3_sched(int m_tiles, int n_tiles, int cpg)
   return c;
 }
 
-template <bool RING, bool STAGGER = false>
 __global__ void __launch_bounds__(NT2)
 grouped_gemm_tn3_k(Tn3Args a, const int32_t *__restrict__ offsets) {
   typedef bf16_t T;
@@ -2273,16 +2264,6 @@ grouped_gemm_tn3_k(Tn3Args a, const int32_t *__restrict__ offsets) {
     const v4i ars = raw_buffer_rsrc(A + (int64_t)r_begin * M + m0, rows > 0 ? (uint32_t)(rows * ldA - m0 * (int)sizeof(T)) : 0u);
     const v4i brs = raw_buffer_rsrc(Bm + (int64_t)r_begin * N + n0, rows > 0 ? (uint32_t)(rows * ldB - n0 * (int)sizeof(T)) : 0u);
     const uint32_t lds0 = lds_addr_of(smem);
-    auto stage = [&](int buf, int step) {
-      const uint32_t as = lds0 + buf * 2 * OPB, bs = as + OPB;
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int p = jj * 8 + wave;
-        const uint32_t row = (uint32_t)(step * BKR + 2 * p);   // in the VGPR offset: the range check ignores the scalar one
-        lds_dma16(ars, as + p * 1024, va0 + row * (uint32_t)ldA);
-        lds_dma16(brs, bs + p * 1024, vb0 + row * (uint32_t)ldB);
-      }
-    };
 
     f32x4 acc[4][8];   // [n-subtile][m-subtile]
 #pragma unroll
@@ -2331,84 +2312,70 @@ grouped_gemm_tn3_k(Tn3Args a, const int32_t *__restrict__ offsets) {
       }
       __builtin_amdgcn_s_setprio(0);
     };
-    auto nothing = [](int) {};
-    auto kblock = [&](const char *as, const char *bs) { read_frags(as, bs); mma_frags(nothing); };
-    if constexpr (RING) {
-      // four slots of 32 k-rows (16 KiB per operand), THREE stages in flight (96 KiB per CU instead of the 64 of the
-      // double buffer below): a stage of this kernel comes from HBM - every k-row of the group is read once per round -
-      // and with one 64-deep stage in flight the step took as long as the stage's latency (2.2 us against 0.9 us of
-      // MFMA work).  The DMA pieces are whole 512-byte k-rows either way, so the shallower stage costs the fill nothing
-      // (unlike the NT kernels, whose rows would shrink to 64 bytes).
-      constexpr int OPH = 32 * KROWB;
-      const int nsub = 2 * (s1 - s0);
-      // piece q (0..3) of this wave's share of stage u: q & 1 picks the operand, q >> 1 the piece (two k-rows of 512 B).
-      // Past the item's last stage the piece is still issued, from beyond the descriptor's range (it writes zeros into a
-      // slot nobody reads again and moves no data): the loop then has ONE shape and one vmcnt count
-      auto piece32 = [&](int u, int q) {
-        const uint32_t as = lds0 + (u & 3) * 2 * OPH, bs = as + OPH;
-        const int p = (q >> 1) * 8 + wave;
-        const uint32_t row = (uint32_t)(s0 * BKR + u * 32 + 2 * p);
-        const bool live = u < nsub;
-        if (q & 1) lds_dma16(brs, bs + p * 1024, live ? vb0 + row * (uint32_t)ldB : 0xfffffff0u);
-        else lds_dma16(ars, as + p * 1024, live ? va0 + row * (uint32_t)ldA : 0xfffffff0u);
-      };
-      auto stage32 = [&](int u) {
+    // four slots of 32 k-rows (16 KiB per operand), THREE stages in flight (96 KiB per CU instead of the 64 of a
+    // double buffer): a stage of this kernel comes from HBM - every k-row of the group is read once per round -
+    // and with one 64-deep stage in flight the step took as long as the stage's latency (2.2 us against 0.9 us of
+    // MFMA work).  The DMA pieces are whole 512-byte k-rows either way, so the shallower stage costs the fill nothing
+    // (unlike the NT kernels, whose rows would shrink to 64 bytes).
+    constexpr int OPH = 32 * KROWB;
+    const int nsub = 2 * (s1 - s0);
+    // piece q (0..3) of this wave's share of stage u: q & 1 picks the operand, q >> 1 the piece (two k-rows of 512 B).
+    // Past the item's last stage the piece is still issued, from beyond the descriptor's range (it writes zeros into a
+    // slot nobody reads again and moves no data): the loop then has ONE shape and one vmcnt count
+    auto piece32 = [&](int u, int q) {
+      const uint32_t as = lds0 + (u & 3) * 2 * OPH, bs = as + OPH;
+      const int p = (q >> 1) * 8 + wave;
+      const uint32_t row = (uint32_t)(s0 * BKR + u * 32 + 2 * p);   // in the VGPR offset: the range check ignores the scalar one
+      const bool live = u < nsub;
+      if (q & 1) lds_dma16(brs, bs + p * 1024, live ? vb0 + row * (uint32_t)ldB : 0xfffffff0u);
+      else lds_dma16(ars, as + p * 1024, live ? va0 + row * (uint32_t)ldA : 0xfffffff0u);
+    };
+    auto stage32 = [&](int u) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) piece32(u, q);
-      };
-      for (int u = 0; u < 3; ++u) stage32(u);
-      // top of interval u: stage u has landed once only the DMAs of the two younger stages are outstanding (vmcnt retires
-      // in order); behind the barrier every wave's share of stage u is in and nobody still reads slot (u - 1) & 3, which
-      // stage u + 3 then overwrites.  The four DMA instructions of that stage are NOT issued here in one run: a wave sits
-      // in each of them until the CU's address unit has taken it (16 cycles per KiB piece, 32 pieces per interval and CU,
-      // all eight waves at once right behind the barrier - the 0.4-0.5 us per 64-deep step that "asynchronous" fills cost
-      // every persistent kernel of this file in round 2's probes); they go out one by one between the MFMA groups
-      auto top = [&]() {
-        wait_vmcnt<8>();
-        lds_barrier();
-      };
-      auto mma_and_fill = [&](int u) {   // the MFMAs of the fragments in registers, stage u + 3 on its way between them
-        mma_frags([&](int jn) {
-          __builtin_amdgcn_sched_barrier(0);
-          piece32(u + 3, jn);
-          __builtin_amdgcn_sched_barrier(0);
-        });
-      };
-      if (!STAGGER || !lagger) {
-        for (int u = 0; u < nsub; ++u) {
-          top();
-          const char *as = smem + (u & 3) * 2 * OPH;
-          read_frags(as, as + OPH);
-          mma_and_fill(u);
-        }
-      } else if (nsub > 0) {
-        // waves 4-7 (the SIMD partners of waves 0-3) run half an interval out of phase: the MFMAs of the fragments they
-        // read in the previous interval first - while their partners, who start with the reads, leave the matrix pipe
-        // alone - then this interval's reads under the partners' MFMAs (MI355X_MICROARCH.md, two waves per SIMD, item 9).
-        // A loop of its own: with the role test inside one loop hipcc kept both roles' registers live (772 B of scratch)
+      for (int q = 0; q < 4; ++q) piece32(u, q);
+    };
+    for (int u = 0; u < 3; ++u) stage32(u);
+    // top of interval u: stage u has landed once only the DMAs of the two younger stages are outstanding (vmcnt retires
+    // in order); behind the barrier every wave's share of stage u is in and nobody still reads slot (u - 1) & 3, which
+    // stage u + 3 then overwrites.  The four DMA instructions of that stage are NOT issued here in one run: a wave sits
+    // in each of them until the CU's address unit has taken it (16 cycles per KiB piece, 32 pieces per interval and CU,
+    // all eight waves at once right behind the barrier - the 0.4-0.5 us per 64-deep step that "asynchronous" fills cost
+    // every persistent kernel of this file in round 2's probes); they go out one by one between the MFMA groups
+    auto top = [&]() {
+      wait_vmcnt<8>();
+      lds_barrier();
+    };
+    auto mma_and_fill = [&](int u) {   // the MFMAs of the fragments in registers, stage u + 3 on its way between them
+      mma_frags([&](int jn) {
+        __builtin_amdgcn_sched_barrier(0);
+        piece32(u + 3, jn);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+    };
+    if (!lagger) {
+      for (int u = 0; u < nsub; ++u) {
         top();
-        stage32(3);
-        read_frags(smem, smem + OPH);
-        for (int u = 1; u < nsub; ++u) {
-          top();
-          mma_and_fill(u);
-          const char *as = smem + (u & 3) * 2 * OPH;
-          read_frags(as, as + OPH);
-        }
-        mma_frags(nothing);
+        const char *as = smem + (u & 3) * 2 * OPH;
+        read_frags(as, as + OPH);
+        mma_and_fill(u);
       }
-      wait_vmcnt<0>();   // the zero-fill pieces past the last stage: the ring must be quiet before the next item's first DMA
-    } else {
-      if (s0 < s1) stage(0, s0);
-      for (int st = s0; st < s1; ++st) {
-        wait_vmcnt<0>();
-        __syncthreads();
-        if (st + 1 < s1) stage((st + 1 - s0) & 1, st + 1);
-        const char *as = smem + ((st - s0) & 1) * 2 * OPB, *bs = as + OPB;
-        kblock(as, bs);
-        kblock(as + 32 * KROWB, bs + 32 * KROWB);
+    } else if (nsub > 0) {
+      // waves 4-7 (the SIMD partners of waves 0-3) run half an interval out of phase: the MFMAs of the fragments they
+      // read in the previous interval first - while their partners, who start with the reads, leave the matrix pipe
+      // alone - then this interval's reads under the partners' MFMAs (MI355X_MICROARCH.md, two waves per SIMD, item 9).
+      // A loop of its own: with the role test inside one loop hipcc kept both roles' registers live (772 B of scratch)
+      top();
+      stage32(3);
+      read_frags(smem, smem + OPH);
+      for (int u = 1; u < nsub; ++u) {
+        top();
+        mma_and_fill(u);
+        const char *as = smem + (u & 3) * 2 * OPH;
+        read_frags(as, as + OPH);
       }
+      mma_frags([](int) {});
     }
+    wait_vmcnt<0>();   // the zero-fill pieces past the last stage: the ring must be quiet before the next item's first DMA
     // the next ticket rides on the barrier that ends the K loop; two slots in turn, so the slot written now was last read
     // two barriers ago (no barrier of its own: one behind the epilogue would have every wave wait for the slowest one's
     // store issue before the next item's first DMA)
@@ -2788,39 +2755,55 @@ int device_cu_count() {
   return ncu;
 }
 
-// returns APERTIS_ERR_UNSUPPORTED when the shape does not fit v3's assumptions (the caller falls back to v2)
-int launch_tn3(const Tn3Problem &q0, const Tn3Problem *q1, int64_t E, int64_t max_rows, const int32_t *offsets, float *ws,
-               int64_t ws_bytes, bool item_queue, hipStream_t st) {
-  const int nprob = q1 ? 2 : 1;
-  const int64_t groups = nprob * E;
+// What launch_tn3 and launch_tn5 share (tests/gemm_ref.py: _tn_ws_launch): the CUs dealt evenly to the (problem, expert) groups,
+// one partial-tile slot of `slot_floats` per work-group in the caller's workspace, the groups' item counters behind the slots
+// (zeroed on the launch stream when the caller asks for the item queue) and the operands' 32-bit buffer offsets.
+struct TnWsPlan { int nprob, cpg, grid; int64_t groups; int *ctr; };
+// APERTIS_ERR_UNSUPPORTED when the workspace path does not apply (nothing has been enqueued then: the caller falls back)
+int tn_ws_plan(const Tn3Problem &q0, const Tn3Problem *q1, int64_t E, int64_t max_rows, int slot_floats, float *ws, int64_t ws_bytes,
+               bool item_queue, hipStream_t st, TnWsPlan &p) {
+  p.nprob = q1 ? 2 : 1;
+  p.groups = p.nprob * E;
   const int ncu = device_cu_count();
-  if (!ws || groups > ncu) return APERTIS_ERR_UNSUPPORTED;
+  if (!ws || p.groups > ncu) return APERTIS_ERR_UNSUPPORTED;
   // (short groups - under ~2048 rows each - do not amortise a 256-row-deep slice per CU plus the fold: callers leave
   // `ws` NULL for those and get the 128 x 128 kernel; the choice is the caller's, the library has no hidden switch)
-  const int cpg = (int)(ncu / groups);
-  const int grid = (int)(groups * cpg);
-  const int64_t slots_bytes = (int64_t)grid * TN3_SLOT * (int64_t)sizeof(float);
+  p.cpg = (int)(ncu / p.groups);
+  p.grid = (int)(p.groups * p.cpg);
+  const int64_t slots_bytes = (int64_t)p.grid * slot_floats * (int64_t)sizeof(float);
   if (ws_bytes < slots_bytes + TN3_CTR_BYTES || (((uintptr_t)ws) & 15)) return APERTIS_ERR_UNSUPPORTED;
   const int64_t ldmax = std::max<int64_t>(std::max(q0.M, q0.N), q1 ? std::max(q1->M, q1->N) : 0) * 2;
   if ((max_rows + 256) * ldmax >= 0xffffffffLL) return APERTIS_ERR_UNSUPPORTED;   // 32-bit buffer offsets
-  Tn3Args a;
-  a.p0 = q0;
-  a.p1 = q1 ? *q1 : Tn3Problem{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-  a.nprob = nprob; a.E = (int)E; a.cpg = cpg; a.ws = ws;
-  a.ctr = item_queue ? reinterpret_cast<int *>(reinterpret_cast<char *>(ws) + slots_bytes) : nullptr;
-  if (a.ctr && hipMemsetAsync(a.ctr, 0, (size_t)groups * TN3_CTR_STRIDE * sizeof(int), st) != hipSuccess) return APERTIS_ERR_LAUNCH;
-  const size_t lds = 4 * 64 * 512 + 16;
-  int ring = 2;
-  auto k3 = ring == 2 ? grouped_gemm_tn3_k<true, true> : ring == 1 ? grouped_gemm_tn3_k<true, false> : grouped_gemm_tn3_k<false, false>;
-  hipFuncSetAttribute((const void *)k3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k3, dim3((unsigned)grid), dim3(NT2), lds, st, a, offsets);
+  p.ctr = item_queue ? reinterpret_cast<int *>(reinterpret_cast<char *>(ws) + slots_bytes) : nullptr;
+  if (p.ctr && hipMemsetAsync(p.ctr, 0, (size_t)p.groups * TN3_CTR_STRIDE * sizeof(int), st) != hipSuccess) return APERTIS_ERR_LAUNCH;
+  return APERTIS_OK;
+}
+// does any problem leave remainder tiles whose rows are split over several work-groups (the fold kernel then sums the slices)
+bool tn_needs_fold(const Tn3Problem &p0, const Tn3Problem &p1, int nprob, int cpg) {
   bool split = false;
   for (int q = 0; q < nprob; ++q) {
-    const Tn3Problem &pp = q ? a.p1 : a.p0;
+    const Tn3Problem &pp = q ? p1 : p0;
     const Tn3Sched sc = tn3_sched(pp.m_tiles, pp.n_tiles, cpg);
     split |= sc.rem && sc.s > 1;
   }
-  if (split) hipLaunchKernelGGL(tn3_fold_k, dim3((unsigned)(groups * std::max(1, cpg / 2)), 16), dim3(256), 0, st, a);
+  return split;
+}
+
+// returns APERTIS_ERR_UNSUPPORTED when the shape does not fit v3's assumptions (the caller falls back to v2)
+int launch_tn3(const Tn3Problem &q0, const Tn3Problem *q1, int64_t E, int64_t max_rows, const int32_t *offsets, float *ws,
+               int64_t ws_bytes, bool item_queue, hipStream_t st) {
+  TnWsPlan p;
+  const int rc = tn_ws_plan(q0, q1, E, max_rows, TN3_SLOT, ws, ws_bytes, item_queue, st, p);
+  if (rc != APERTIS_OK) return rc;
+  Tn3Args a;
+  a.p0 = q0;
+  a.p1 = q1 ? *q1 : Tn3Problem{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+  a.nprob = p.nprob; a.E = (int)E; a.cpg = p.cpg; a.ws = ws; a.ctr = p.ctr;
+  const size_t lds = 4 * 64 * 512 + 16;
+  hipFuncSetAttribute((const void *)grouped_gemm_tn3_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(grouped_gemm_tn3_k, dim3((unsigned)p.grid), dim3(NT2), lds, st, a, offsets);
+  if (tn_needs_fold(a.p0, a.p1, p.nprob, p.cpg))
+    hipLaunchKernelGGL(tn3_fold_k, dim3((unsigned)(p.groups * std::max(1, p.cpg / 2)), 16), dim3(256), 0, st, a);
   return apertis_check_launch();
 }
 
@@ -2838,43 +2821,26 @@ int tn5_variant(int64_t M, int64_t N) {
 int launch_tn5(Tn3Problem q0, const Tn3Problem *q1p, int64_t E, int64_t max_rows, const int32_t *offsets, float *ws, int64_t ws_bytes,
                bool item_queue, hipStream_t st, int force_v0 = -1) {
   Tn3Problem q1 = q1p ? *q1p : q0;
-  const int nprob = q1p ? 2 : 1;
   const int v0 = force_v0 >= 0 ? force_v0 : tn5_variant(q0.M, q0.N), v1 = q1p ? tn5_variant(q1.M, q1.N) : v0;
-  const int64_t groups = nprob * E;
-  const int ncu = device_cu_count();
-  if (!ws || v0 < 0 || v1 < 0 || groups > ncu) return APERTIS_ERR_UNSUPPORTED;
-  const int cpg = (int)(ncu / groups);
-  const int grid = (int)(groups * cpg);
-  const int64_t slots_bytes = (int64_t)grid * TN5_SLOT * (int64_t)sizeof(float);
-  if (ws_bytes < slots_bytes + TN3_CTR_BYTES || (((uintptr_t)ws) & 15)) return APERTIS_ERR_UNSUPPORTED;
-  const int64_t ldmax = std::max<int64_t>(std::max(q0.M, q0.N), std::max(q1.M, q1.N)) * 2;
-  if ((max_rows + 256) * ldmax >= 0xffffffffLL) return APERTIS_ERR_UNSUPPORTED;   // 32-bit buffer offsets
+  if (v0 < 0 || v1 < 0) return APERTIS_ERR_UNSUPPORTED;
+  TnWsPlan p;
+  const int rc = tn_ws_plan(q0, q1p, E, max_rows, TN5_SLOT, ws, ws_bytes, item_queue, st, p);
+  if (rc != APERTIS_OK) return rc;
   q0.m_tiles = (int)ceil_div64(q0.M, v0 ? 352 : 256); q0.n_tiles = (int)ceil_div64(q0.N, v0 ? 256 : 352);
   q1.m_tiles = (int)ceil_div64(q1.M, v1 ? 352 : 256); q1.n_tiles = (int)ceil_div64(q1.N, v1 ? 256 : 352);
   Tn5Args a;
   a.p0 = q0; a.p1 = q1; a.wide_m0 = v0; a.wide_m1 = v1;
-  a.nprob = nprob; a.E = (int)E; a.cpg = cpg; a.ws = ws;
-  a.slice_major = groups == 1;
-  a.ctr = item_queue ? reinterpret_cast<int *>(reinterpret_cast<char *>(ws) + slots_bytes) : nullptr;
-  if (a.ctr && hipMemsetAsync(a.ctr, 0, (size_t)groups * TN3_CTR_STRIDE * sizeof(int), st) != hipSuccess) return APERTIS_ERR_LAUNCH;
+  a.nprob = p.nprob; a.E = (int)E; a.cpg = p.cpg; a.ws = ws; a.ctr = p.ctr;
+  a.slice_major = p.groups == 1;
   const size_t lds = 3 * TN5_STAGE + 16;
   hipFuncSetAttribute((const void *)grouped_gemm_tn5_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(grouped_gemm_tn5_k, dim3((unsigned)grid), dim3(NT2), lds, st, a, offsets);
-  bool split = false;
-  for (int q = 0; q < nprob; ++q) {
-    const Tn3Problem &pp = q ? a.p1 : a.p0;
-    const Tn3Sched sc = tn3_sched(pp.m_tiles, pp.n_tiles, cpg);
-    split |= sc.rem && sc.s > 1;
-  }
-  if (split) {
-    const int cpb = groups == 1 ? 1 : 4;
-    hipLaunchKernelGGL(tn5_fold_k, dim3((unsigned)(groups * std::max(1, cpg / 2)), 88 / cpb), dim3(256), 0, st, a, cpb);
+  hipLaunchKernelGGL(grouped_gemm_tn5_k, dim3((unsigned)p.grid), dim3(NT2), lds, st, a, offsets);
+  if (tn_needs_fold(a.p0, a.p1, p.nprob, p.cpg)) {
+    const int cpb = p.groups == 1 ? 1 : 4;
+    hipLaunchKernelGGL(tn5_fold_k, dim3((unsigned)(p.groups * std::max(1, p.cpg / 2)), 88 / cpb), dim3(256), 0, st, a, cpb);
   }
   return apertis_check_launch();
 }
-
-// (behind every other kernel of this file: the kernels in front keep their places in the code object)
-#include "gemm_nt2i.h"   // grouped_gemm_nt2i_k: the saved-gradient forward with its epilogue inside the next tile's K loop (round 6)
 
 template <typename T> bool aligned16(const void *p, int64_t ld) {
   return (((uintptr_t)p) & 15) == 0 && ((ld * sizeof(T)) & 15) == 0;
@@ -2898,10 +2864,12 @@ int launch_nt(const void *A, const void *W, const float *bias, const int32_t *of
   const int64_t grid = m_tiles * n_tiles;
   if (grid > 0x7fffffffLL) return APERTIS_ERR_UNSUPPORTED;
   if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) {
+    // The decisions below are mirrored, name for name and in this order, by nt_path in tests/gemm_ref.py.
+    const bool heavy = act != APERTIS_ACT_NONE || drop_p > 0.f || pre_act || mul_pre;   // an epilogue that is more than bias + store
     // a handful of rows (the decode step): a wave per 16 output columns, operands straight from global memory
     if (max_rows <= 64 && !flagged && !pre_act && !mul_pre && drop_p <= 0.f && K % 8 == 0 && N % 4 == 0 && ldw % 8 == 0 && E <= 65535 &&
         ceil_div64(N, 16) <= 0x7fffffff) {
-      if (K >= 2048 && SKINNY_LONG_K_WAVES == 16)  // (sixteen waves: a wave's share of K = 2816 is six 32-deep steps = ONE batch in flight instead of three dependent ones)
+      if (K >= 2048)       // (sixteen waves: a wave's share of K = 2816 is six 32-deep steps = ONE batch in flight instead of three dependent ones)
         hipLaunchKernelGGL((grouped_gemm_nt_skinny_k<TO, 16>), dim3((unsigned)ceil_div64(N, 16), (unsigned)E), dim3(1024), 0, st,
                            (const bf16_t *)A, (const bf16_t *)W, bias, offsets, (TO *)C, (int)N, (int)K, (int)ldw, act, (int)max_rows);
       else if (K >= 512)   // (a wave's share is then one batch of eight 32-deep steps or a few: the K walk is a chain of round trips)
@@ -2916,39 +2884,39 @@ int launch_nt(const void *A, const void *W, const float *bias, const int32_t *of
     // One group (dense projection) takes it at any width: narrow outputs are HBM-bound and the
     // persistent kernel's cross-tile prefetch matters more than the MFMA work a partial n-tile wastes
     const bool kpad_ok = K % 64 == 0 || ldw >= ceil_div64(K, 64) * 64;
+    // (one 352-wide n-tile reads X once: 114 vs 121 us on the SSM input projection, N = 352, K = 704)
+    const bool plain352 = N == BN5 && K % 64 == 0 && ldw == K;
     // two work-groups per CU pay off when the epilogue is heavy next to the K loop (activation / dropout /
     // second output on a short K); long K loops run faster on the 256 x 256 tile (fewer operand bytes per flop).
     // ... and for the SSM block's dense projections (one group, short K, HBM-bound): 92 vs 114 us at N=352/K=704, 72 vs 89
     // at N=704/K=176, 56 vs 64 at N=400/K=176; the N=176 data gradients stay on the 256-wide tile (63 vs 60 us)
-    const bool use2x = ((act != APERTIS_ACT_NONE || drop_p > 0.f || pre_act || mul_pre) && K <= 1024 && N >= 512) ||
-                       // (one 352-wide n-tile reads X once: 114 vs 121 us on the SSM input projection, N = 352, K = 704)
-                       (E == 1 && K <= 1024 && N >= 256 && !(N == BN5 && K % 64 == 0 && ldw == K)) ||
+    const bool use2x = (heavy && K <= 1024 && N >= 512) ||
+                       (E == 1 && K <= 1024 && N >= 256 && !plain352) ||
                        // narrow expert outputs (the H = 256 family's fc2 forward / fc1 data gradient, N = 256, K = 1024):
                        // 67 us here, 77 on the 256 x 256 tile, 90 on the 128 x 128 kernel they used to fall to
                        (E > 1 && K <= 1024 && N >= 256 && N < 512) ||
                        // narrow dense outputs (the H = 256 family's x_param / out_proj data gradients, N = 64): one half-empty
                        // 128-wide n-tile of this kernel instead of the 128 x 128 register-staged kernel (29 us for 42 MB there)
                        (E == 1 && K <= 1024 && N >= 64 && N < 128);
+    const bool big = max_rows >= 4096 && E <= 1024;   // what every 256-row kernel below asks of the rows and the groups
     // outputs a multiple of 352 wide with a plain epilogue: the 256 x 352 tile (two passes over X for N = 704 instead of three)
-    const bool use352 = !use2x && act == APERTIS_ACT_NONE && drop_p <= 0.f && !pre_act && !mul_pre && N % BN5 == 0 && K % 64 == 0 &&
-                        ldw == K && K >= 128 && max_rows >= 4096 && E <= 1024;
-    if (use352) {
+    if (!use2x && !heavy && N % BN5 == 0 && K % 64 == 0 && ldw == K && K >= 128 && big) {
       const int nt5 = (int)(N / BN5);
       const int64_t grid5 = (ceil_div64(max_rows, BM2) + E) * nt5;
       if (grid5 < 0x7fffffffLL) {
         const int gp = (int)std::min<int64_t>(grid5, device_cu_count());   // one persistent work-group per CU
         const size_t lds5 = 2 * BUF5 + 4096 + 16;                           // ring + group offsets
-        constexpr int solo = 4;   // (re-measured with the spread fills, round 3: 0..6 all within noise)
         if (tile_queue && hipMemsetAsync(tile_queue, 0, NTQ_INTS * sizeof(int32_t), st) != hipSuccess) return APERTIS_ERR_LAUNCH;
         auto k5 = grouped_gemm_nt352p_k<TO>;
         hipFuncSetAttribute((const void *)k5, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5);
         hipLaunchKernelGGL(k5, dim3((unsigned)gp), dim3(NT2), lds5, st, (const bf16_t *)A, (const bf16_t *)W, bias, offsets, (TO *)C,
-                           (int)N, (int)K, (int)E, nt5, (int)grid5, solo, (int *)tile_queue);
+                           (int)N, (int)K, (int)E, nt5, (int)grid5, NT_SOLO, (int *)tile_queue);
         return apertis_check_launch();
       }
     }
     // the persistent 256 x 256 tile on a four-slot ring (grouped_gemm_nt4r_k): every epilogue form of the two-per-CU kernel
     const bool ragged2x = K % 32 != 0;
+    const bool pad32_ok = !ragged2x || ldw >= ceil_div64(K, 32) * 32;   // W's rows zero-padded to whole 32-deep sub-steps
     // Taken for the calls with a heavy epilogue on a short K (the expert fc1 forward and the fused fc2 data gradient; the dense
     // FFN's as one group).  Same box, best of 5 cold runs, two-per-CU kernel -> this one (tools/probes/gemm_probe.hip, PROBE_R4):
     //   H=704 I=2816 B=32: saved-gradient forward 1195-1200 -> 1096-1105 us, fused data gradient 949-951 -> 792-797
@@ -2956,39 +2924,19 @@ int launch_nt(const void *A, const void *W, const float *bias, const int32_t *of
     //   H=256 I=1024 B=16: 193 -> 154-166, 181 -> 108            H=896 I=3584: 820-882 -> 749-757, 715-725 -> 612-628
     // Plain epilogues stay where they were (N=1024, K=256: 78 us there, 88 here; N=3584, K=896: 565 there, 508 here - not routed).
     // A caller that passes a tile queue (data-parallel runs: a collective may hold CUs) keeps the non-persistent kernel.
-    const bool use4r = ((act != APERTIS_ACT_NONE || drop_p > 0.f || pre_act || mul_pre) && K <= 1024 && N >= 512) ||
+    const bool use4r = (heavy && K <= 1024 && N >= 512) ||
                        // ... and for the SSM block's dense projections (one group, short K: byte- and latency-bound - the stage
                        // stream through tile boundaries hides a tile's prologue and epilogue, and 256-wide n-tiles read X half as
                        // often).  Same box, B = 44 (`gemm_probe 44 704 2816 dense`), two-per-CU -> this kernel: N=704 K=176 121 ->
                        // 102 us, N=704 K=352 162 -> 141, N=448 K=176 83 -> 74, N=176 K=448 63-67 -> 60, N=176 K=704 85-92 -> 83;
                        // N=352 K=704 stays on the 352-wide tile (107-110 there, 111 here)
-                       (E == 1 && K <= 1024 && N >= 128 && !(N == BN5 && K % 64 == 0 && ldw == K));
-    // the saved-gradient forward (GELU; the expert fc1 forward) with K >= 512: one wave per SIMD, the epilogue of tile i inside
-    // the K loop of tile i + 1 (grouped_gemm_nt2i_k, gemm_nt2i.h).  Not under a tile queue (data-parallel steps: the ring kernel).
-    // Bit-identical to the ring kernel and, at the bench shape, SLOWER (1678 against 1452 us: with one wave per SIMD the six
-    // LDS-DMA pieces of a sub-step stall the only wave that could feed the matrix pipe - profiles/r6_probe_nt2i_vs_nt4r.log): taken
-    // only when the caller asks for it (APERTIS_ACT_INTERLEAVED).
-    if ((act_flags & APERTIS_ACT_INTERLEAVED) && (act_flags & APERTIS_ACT_SAVE_GRAD) && pre_act && !mul_pre && act == APERTIS_ACT_GELU && !tile_queue && K % 32 == 0 &&
-        K >= 512 && ldw == K && N % 8 == 0 && N >= 512 && max_rows >= 4096 && E <= 1024) {
-      const int nt5 = (int)ceil_div64(N, BN3);
-      const int64_t grid5 = (ceil_div64(max_rows, BM3) + E) * nt5;
-      if (grid5 < 0x7fffffffLL) {
-        const int gp = (int)std::min<int64_t>(grid5, device_cu_count());
-        const int lds5 = RING5I + 4 * 1024;   // ring + a bias area per wave
-        auto k5 = drop_p > 0.f ? grouped_gemm_nt2i_k<TO, true> : grouped_gemm_nt2i_k<TO, false>;
-        hipFuncSetAttribute((const void *)k5, hipFuncAttributeMaxDynamicSharedMemorySize, lds5);
-        hipLaunchKernelGGL(k5, dim3((unsigned)gp), dim3(NT3), lds5, st, (const bf16_t *)A, (const bf16_t *)W, bias, offsets, (TO *)C,
-                           (TO *)pre_act, (int)N, (int)K, (int)ldw, (int)E, nt5, (int)grid5, drop_p, seed, 4, 8);
-        return apertis_check_launch();
-      }
-    }
+                       (E == 1 && K <= 1024 && N >= 128 && !plain352);
     // (a caller's tile queue - data-parallel steps - is taken when the kernel's ticket hand-over fits: K >= 352 and a grid that
     //  is a multiple of the 8 XCDs; otherwise such calls stay on the queue-driven two-per-CU / 256 x 256 kernels below.  Round 6:
     //  the N > 1 step used to lose this kernel altogether - 956 against 902 us per expert NT call at B = 44)
     const int64_t grid4q = (ceil_div64(max_rows, BM4) + E) * ceil_div64(N, BN4);
     const bool queue4_ok = tile_queue && ceil_div64(K, 32) >= 11 && grid4q >= device_cu_count() && device_cu_count() % 8 == 0;
-    if (use4r && !(mul_pre && bias) && (!tile_queue || queue4_ok) && (!ragged2x || ldw >= ceil_div64(K, 32) * 32) && K > 128 && K % 8 == 0 && N % 8 == 0 &&
-        N >= 128 && max_rows >= 4096 && E <= 1024) {
+    if (use4r && !(mul_pre && bias) && (!tile_queue || queue4_ok) && pad32_ok && K > 128 && K % 8 == 0 && N % 8 == 0 && N >= 128 && big) {
       const int nt4 = (int)ceil_div64(N, BN4);
       const int64_t grid4 = (ceil_div64(max_rows, BM4) + E) * nt4;
       if (grid4 < 0x7fffffffLL) {
@@ -3009,7 +2957,7 @@ int launch_nt(const void *A, const void *W, const float *bias, const int32_t *of
         return apertis_check_launch();
       }
     }
-    if (use2x && (!ragged2x || ldw >= ceil_div64(K, 32) * 32) && K >= 96 && K % 8 == 0 && N % 8 == 0 && N >= 64 && max_rows >= 4096 && E <= 1024) {
+    if (use2x && pad32_ok && K >= 96 && K % 8 == 0 && N % 8 == 0 && N >= 64 && big) {
       const int nt3 = (int)ceil_div64(N, BN3);
       const int64_t grid3 = (ceil_div64(max_rows, BM3) + E) * nt3;
       if (grid3 < 0x7fffffffLL) {
@@ -3028,19 +2976,18 @@ int launch_nt(const void *A, const void *W, const float *bias, const int32_t *of
       }
     }
     if (flagged) return APERTIS_ERR_UNSUPPORTED;
-    if (kpad_ok && (N >= 512 || (E == 1 && N >= 128)) && max_rows >= 4096 && E <= 1024) {
+    if (kpad_ok && (N >= 512 || (E == 1 && N >= 128)) && big) {
       const int nt2 = (int)ceil_div64(N, BN2);
       const int64_t grid2 = (ceil_div64(max_rows, BM2) + E) * nt2;
       if (grid2 < 0x7fffffffLL) {
         const int ncu = device_cu_count();
         const int gp = (int)std::min<int64_t>(grid2, ncu);          // one persistent work-group per CU
         size_t ldsp = 4 * TILE2_BYTES + 4096 + 16;                   // ring + group offsets
-        constexpr int solo = 4;   // K steps of a tile whose DMA the non-store waves issue alone (measured best of 2..6)
         if (tile_queue && hipMemsetAsync(tile_queue, 0, NTQ_INTS * sizeof(int32_t), st) != hipSuccess) return APERTIS_ERR_LAUNCH;
         auto kp = (K % 64 == 0 && ldw == K) ? grouped_gemm_nt256p_k<TO, false> : grouped_gemm_nt256p_k<TO, true>;
         hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
         hipLaunchKernelGGL(kp, dim3((unsigned)gp), dim3(NT2), ldsp, st, (const bf16_t *)A, (const bf16_t *)W, bias, offsets,
-                           (TO *)C, (TO *)pre_act, (const TO *)mul_pre, (int)N, (int)K, (int)ldw, (int)E, nt2, (int)grid2, solo,
+                           (TO *)C, (TO *)pre_act, (const TO *)mul_pre, (int)N, (int)K, (int)ldw, (int)E, nt2, (int)grid2, NT_SOLO,
                            act, drop_p, seed, (int *)tile_queue);
         return apertis_check_launch();
       }
@@ -3120,12 +3067,7 @@ extern "C" int64_t apertis_grouped_gemm_tn_workspace_bytes(int64_t E, int n_prob
 // from about a quarter of a million output elements on.  (Its first form lost everywhere below a dozen tiles - 234 us for
 // dW [352, 704]: the fold of a single group's 85 slices per tile ran on 66 work-groups; it now takes one 1024-float chunk per
 // work-group, and the work-groups that share a row slice are neighbours on one XCD.)
-#ifndef TN_DENSE_MIN_FILL
-#define TN_DENSE_MIN_FILL 60
-#endif
-#ifndef TN_DENSE_MIN_AREA
-#define TN_DENSE_MIN_AREA 240000
-#endif
+constexpr int64_t TN_DENSE_MIN_FILL = 60, TN_DENSE_MIN_AREA = 240000;
 extern "C" int apertis_grouped_gemm_tn_dense_variant(int64_t M, int64_t N) {
   if (M < 128 || N < 128 || M % 8 || N % 8 || M * N < TN_DENSE_MIN_AREA) return -1;
   auto area = [&](int64_t tm, int64_t tn) { return ceil_div64(M, tm) * ceil_div64(N, tn) * tm * tn; };
@@ -3216,11 +3158,9 @@ extern "C" int apertis_grouped_gemm_tn_pair_q(const void *A0, const void *B0, fl
                   (int)ceil_div64(N0, 256)};
     Tn3Problem p1{(const bf16_t *)A1, (const bf16_t *)B1, dW1, dbias1, (int)M1, (int)N1, (int)ceil_div64(M1, 256),
                   (int)ceil_div64(N1, 256)};
-    bool v5 = true;
-    if (v5) {   // the 704-wide family: 256 x 352 / 352 x 256 tiles
-      const int rc5 = launch_tn5(p0, &p1, E, max_rows, offsets, (float *)ws, ws_bytes, item_queue != 0, (hipStream_t)stream);
-      if (rc5 != APERTIS_ERR_UNSUPPORTED) return rc5;
-    }
+    // the 704-wide family: 256 x 352 / 352 x 256 tiles
+    const int rc5 = launch_tn5(p0, &p1, E, max_rows, offsets, (float *)ws, ws_bytes, item_queue != 0, (hipStream_t)stream);
+    if (rc5 != APERTIS_ERR_UNSUPPORTED) return rc5;
     const int rc = launch_tn3(p0, &p1, E, max_rows, offsets, (float *)ws, ws_bytes, item_queue != 0, (hipStream_t)stream);
     if (rc != APERTIS_ERR_UNSUPPORTED) return rc;
   }

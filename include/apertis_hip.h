@@ -44,10 +44,6 @@ extern "C" {
  *            the epilogue instead of the activation derivative and the mask hash. */
 #define APERTIS_ACT_SAVE_GRAD 0x100
 #define APERTIS_ACT_MUL_SAVED 0x200
-/* with APERTIS_ACT_SAVE_GRAD: ask for the interleaved-epilogue kernel (grouped_gemm_nt2i_k, round 6: one wave per SIMD, the
- * epilogue of tile i between the MFMA groups of tile i + 1; K % 32 == 0, K >= 512, no tile queue).  Same bits as the default
- * kernel; measured 15 % SLOWER at the bench shape (profiles/r6_probe_nt2i_vs_nt4r.log), so no caller sets it by default. */
-#define APERTIS_ACT_INTERLEAVED 0x400
 
 /* Library/ABI version: (major<<16)|minor.  Bumped when a signature changes or an entry point is added (4.12 - apertis_rope_kv_append_chunk,
  * apertis_attention_chunk, apertis_attention_chunk_splits / _workspace_bytes: multi-token KV-cache steps; 4.11 - apertis_rope_kv_append_at,

@@ -1,5 +1,5 @@
 """float64 CPU references, a mirror of the host-side dispatch and the case tables of the grouped GEMM kernels
-(csrc/grouped_gemm.hip, csrc/gemm_nt2i.h), shared by tests/test_gemm_paths_cpu.py (no device: the references against torch in
+(csrc/grouped_gemm.hip), shared by tests/test_gemm_paths_cpu.py (no device: the references against torch in
 float64, the grid against int64 arithmetic, the mask against a scalar transcription, the tables against the mirror) and
 tests/test_gemm_paths_gpu.py (the kernels, through the C ABI, against the references).
 
@@ -33,7 +33,7 @@ from decode_step_ref import dyadic, dyadic_sum_bits, round_bf16  # noqa: F401  (
 F32, BF16 = torch.float32, torch.bfloat16
 OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -2
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU = 0, 1, 2, 3
-SAVE_GRAD, MUL_SAVED, INTERLEAVED = 0x100, 0x200, 0x400
+SAVE_GRAD, MUL_SAVED = 0x100, 0x200
 MAX_DEPTH = (2 ** 24 - 1 - 248) // 961          # 17 457
 
 
@@ -172,7 +172,7 @@ def _cdiv(a, b):
 
 
 # kernel -> (tile height, tile width, K step)
-NT_TILES = {"nt_skinny": (16, 16, 32), "nt352p": (256, 352, 64), "nt2i": (256, 128, 32), "nt4r": (256, 256, 32),
+NT_TILES = {"nt_skinny": (16, 16, 32), "nt352p": (256, 352, 64), "nt4r": (256, 256, 32),
             "nt2x": (256, 128, 32), "nt256p": (256, 256, 64), "nt": (128, 128, 64)}
 
 
@@ -253,9 +253,6 @@ def nt_path(dtype, dtype_out, max_rows, N, K, ldw, E, act_flags, drop_p, has_pre
         ragged2x = K % 32 != 0
         pad32_ok = not ragged2x or ldw >= _cdiv(K, 32) * 32
         use4r = (heavy and K <= 1024 and N >= 512) or (E == 1 and K <= 1024 and N >= 128 and not plain352)
-        if ((act_flags & INTERLEAVED) and (act_flags & SAVE_GRAD) and has_pre and not has_mul and act == ACT_GELU and
-                not has_queue and K % 32 == 0 and K >= 512 and ldw == K and N % 8 == 0 and N >= 512 and big):
-            return _nt_hit("nt2i", ("bf16", drop_p > 0.0), max_rows, N, K, ldw, E, epi)
         queue4_ok = has_queue and _cdiv(K, 32) >= 11 and (_cdiv(max_rows, 256) + E) * _cdiv(N, 256) >= ncu and ncu % 8 == 0
         if (use4r and not (has_mul and has_bias) and (not has_queue or queue4_ok) and pad32_ok and K > 128 and K % 8 == 0 and
                 N % 8 == 0 and N >= 128 and big):
@@ -327,7 +324,7 @@ def _tn_ws_launch(kind, probs, variants, E, max_rows, item_queue, ncu):
                           wide_m=v if kind == "tn5" else None))
     fold = any(f["rem"] and f["s"] > 1 for f in facts)
     kname = "grouped_gemm_tn3_k" if kind == "tn3" else "grouped_gemm_tn5_k"
-    targs = (True, True) if kind == "tn3" else ()
+    targs = ()                                                 # neither kernel is a template
     launches = [(kname, targs)] + ([(f"{kind}_fold_k", ())] if fold else [])
     return {"kernel": kname, "targs": targs, "cpg": cpg, "grid": groups * cpg, "problems": facts, "fold": fold, "pair": len(probs) == 2,
             "item_queue": bool(item_queue), "launches": launches,
@@ -447,10 +444,6 @@ NT_CASES = [
     nt("352p-e7-n704-k128-queue", E7, 704, 128, queue=True),
     nt("352p-big", BIG, 2816, 128, max_rows=BIG_ROWS),                        # 304 valid tiles: second tiles, the ring carried over
     nt("352p-big-queue", BIG, 2816, 128, max_rows=BIG_ROWS, queue=True),      # ... and tickets drawn from the queue
-    # --- nt2i (the interleaved saved-gradient forward; GELU only: tolerance rows)
-    nt("2i-k512-n520", E7, 520, 512, act=ACT_GELU, pre=True, flags=SAVE_GRAD | INTERLEAVED, bound=5),
-    nt("2i-big", BIG, 1416, 512, act=ACT_GELU, pre=True, flags=SAVE_GRAD | INTERLEAVED, max_rows=BIG_ROWS, bound=5),   # 456 valid tiles
-    nt("2i-k544-n648-drop", E7, 648, 544, act=ACT_GELU, p=0.5, pre=True, flags=SAVE_GRAD | INTERLEAVED, bias=False, bound=5),
     # --- nt4r<ragged, queue>
     nt("4r-relu-drop", E7, 520, 160, act=ACT_RELU, p=0.5),
     nt("4r-none-drop-nobias", E7, 512, 352, p=0.5, bias=False),
@@ -662,7 +655,7 @@ def tn_inputs(c):
 
 
 # every instantiation a launch can name (launch_nt; launch_tn2 / launch_tn3 / launch_tn5 and the fp32 kernel; both fold kernels)
-NT_PATHS = (["nt_skinny<bf16,1>", "nt_skinny<bf16,4>", "nt_skinny<bf16,16>", "nt352p<bf16>", "nt2i<bf16,False>", "nt2i<bf16,True>"] +
+NT_PATHS = (["nt_skinny<bf16,1>", "nt_skinny<bf16,4>", "nt_skinny<bf16,16>", "nt352p<bf16>"] +
             [f"nt4r<bf16,{r},{q}>" for r in (False, True) for q in (False, True)] + ["nt2x<bf16,False>", "nt2x<bf16,True>",
              "nt256p<bf16,False>", "nt256p<bf16,True>", "nt<bf16,bf16>", "nt<bf16,f32>", "nt<f32,f32>"])
 TN_KERNELS = ["grouped_gemm_tn_k", "grouped_gemm_tn2_k", "grouped_gemm_tn3_k", "grouped_gemm_tn5_k", "tn3_fold_k", "tn5_fold_k"]
@@ -736,17 +729,11 @@ def check_case_tables_cover_every_dispatch_path(ncu=256):
             assert ("walks-on", "static") in f, path
         if path in ("nt352p<bf16>", "nt256p<bf16,False>", "nt256p<bf16,True>", "nt4r<bf16,False,True>"):
             assert ("walks-on", "queue") in f, path
-        if path.startswith("nt2i"):
-            assert "walks-on" in g, path
-        fb = g if path.startswith("nt2i") else f
-        assert ("bias", True) in fb and ("bias", False) in fb, path
+        assert ("bias", True) in f and ("bias", False) in f, path
         if path.startswith("nt352p"):                              # plain epilogue, N % 352 == 0, K % 64 == 0, ldw == K by its launcher
             assert ("queue", True) in f and ("queue", False) in f
             continue
         assert ("n_partial", True) in f, path
-        if path.startswith("nt2i"):                                # GELU with the saved gradient only; K % 32 == 0, ldw == K
-            assert ("epi", "save_grad") in f
-            continue
         assert {("act", a) for a in (ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU)} <= g, (path, g)
         if path.startswith("nt_skinny"):                           # no dropout / second output in the skinny kernel
             assert ("k_padded", True) in f and ("k_padded", False) in f, path

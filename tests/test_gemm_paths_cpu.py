@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import gemm_ref as R
-from gemm_ref import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SILU, BF16, ERR_ARG, ERR_UNSUPPORTED, F32, INTERLEAVED, MUL_SAVED, SAVE_GRAD
+from gemm_ref import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SILU, BF16, ERR_ARG, ERR_UNSUPPORTED, F32, MUL_SAVED, SAVE_GRAD
 
 
 def _eq(a, b, tol=1e-12):
@@ -199,8 +199,6 @@ def test_nt_mirror_on_hand_computed_points():
     assert _nt(big, 704, 2816) == "nt352p<bf16>" and _nt(big, 704, 2816, queue=True) == "nt352p<bf16>"
     assert _nt(big, 2816, 704, act=ACT_GELU | SAVE_GRAD, p=0.1, pre=True) == "nt4r<bf16,False,False>"
     assert _nt(big, 2816, 704, act=MUL_SAVED, mul=True, bias=False) == "nt4r<bf16,False,False>"
-    assert _nt(big, 2816, 704, act=ACT_GELU | SAVE_GRAD | INTERLEAVED, p=0.1, pre=True) == "nt2i<bf16,True>"
-    assert _nt(big, 2816, 704, act=ACT_GELU | SAVE_GRAD | INTERLEAVED, pre=True, queue=True) == "nt4r<bf16,False,True>"
     assert _nt(big, 2816, 704) == "nt352p<bf16>" and _nt(big, 1024, 256) == "nt256p<bf16,False>"      # (2816 = 8 x 352)
     assert _nt(big, 3584, 896) == "nt256p<bf16,False>"
     assert _nt(big, 256, 1024) == "nt2x<bf16,False>"                             # the H = 256 family's narrow expert outputs

@@ -1,4 +1,4 @@
-"""The grouped GEMM kernels of csrc/grouped_gemm.hip (and gemm_nt2i.h) against the float64 references of tests/gemm_ref.py, at every
+"""The grouped GEMM kernels of csrc/grouped_gemm.hip against the float64 references of tests/gemm_ref.py, at every
 path of launch_nt and of the TN entry points, through the C ABI (so that pre_act, act_bwd_pre, ldw, dtype_out, the tile queue and
 the workspace are in the test's hands).  The tables and the mirror that says which kernel a row runs live in gemm_ref.py;
 test_gemm_paths_cpu.py holds the mirror to hand-computed points, and test_profiler_sees_the_kernels_the_mirror_names holds it to
@@ -13,7 +13,7 @@ apertis_act_dropout_bwd.
 
 GELU and SiLU outputs and the SAVE_GRAD derivative are compared with a tolerance.  What the activation is fed: EVERY bf16-output
 epilogue rounds the pre-activation to bf16 first (`to_f32(from_f32<TO>(v))` in grouped_gemm_nt_k, the skinny kernel, nt256p_out_round
-and nt2x_epilogue - EPI_BOTH packs it with pack_bf16x2 - and gemm_nt2i.h starts from the same rounded values), so the reference is
+and nt2x_epilogue - EPI_BOTH packs it with pack_bf16x2), so the reference is
 float64 on round_bf16(pre); with an fp32 output (TO = float) that rounding is the identity and the reference is float64 on the
 exact pre-activation.  Tolerance of a bf16 output: ONE bf16 rounding, rtol 8e-3 with the floor 1e-5 of the tensor's maximum
 (tests/test_decode_step_gpu.py's figure); fp32 outputs: rtol 1e-4, same floor.  The bf16-operand kernels evaluate GELU in a
@@ -348,11 +348,11 @@ def test_profiler_sees_the_kernels_the_mirror_names(dev):
     included where the name shows them.  A stock torch kernel launched first tells a blind profiler (skip) from one that sees
     torch's kernel but not ours (failure).
     How the names come back depends on the profiler's demangler (gemm_ref.kernel_name_targs).  Seen on an MI355X with torch 2.10
-    / ROCm 7.0, over all 172 launches: fp32 and non-template kernels demangled in full; a bf16 kernel whose first value argument is
-    0 / false / 4 / 16 still MANGLED (every argument legible: nt4r<*, false, *>, nt2x<false>, nt256p<false>, nt2i<false>, nt352p,
+    / ROCm 7.0, over all 169 launches: fp32 and non-template kernels demangled in full; a bf16 kernel whose first value argument is
+    0 / false / 4 / 16 still MANGLED (every argument legible: nt4r<*, false, *>, nt2x<false>, nt256p<false>, nt352p,
     nt_k<bf16, *>, nt_skinny<4 | 16>); a bf16 kernel whose first value argument is 1 / true GARBLED ("<bool _Accum, bool, E, false>":
     the demangler, not knowing the type code DF16b, swallows the literal behind it) with only later booleans intact - nt4r<*, true, *>,
-    nt2x<true>, nt256p<true>, nt2i<true>, nt_skinny<1>, 22 launches.  So a garbled name is held to a mirror's prediction whose first
+    nt2x<true>, nt256p<true>, nt_skinny<1>, 21 launches.  So a garbled name is held to a mirror's prediction whose first
     value argument is true / 1 and whose later booleans are the legible ones: together with the mangled and demangled names
     that pins every template argument on this build.  The FIGURE lines say, per kernel, how many launches came back in which form.
     """
