@@ -111,6 +111,8 @@ SIGNATURES = {
     "apertis_rmsnorm_bwd_blocks": (_i64, [_i64, _i64]),
     "apertis_dropout_add_rmsnorm_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i64, _f32, _u64, _i32, _i32,
                                                _vp]),
+    "apertis_swiglu_fwd": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp]),
+    "apertis_swiglu_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "apertis_moe_combine_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
     "apertis_moe_combine_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                        _i32, _i32, _vp]),

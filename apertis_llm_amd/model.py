@@ -947,7 +947,9 @@ class ApertisAttention(nn.Module):
 
 
 class SwiGLUFFN(nn.Module):
-    """w_down(silu(w_gate x) * w_up x), width 2/3*I rounded up to 256 (reference core.py:925-993)."""
+    """w_down(silu(w_gate x) * w_up x), width 2/3*I rounded up to 256 (reference core.py:925-993).  On the GPU (fp32 / bf16,
+    H % 8 == 0, ops.SWIGLU_FUSED) the block is ops.swiglu_mlp: w_gate | w_up as one stacked GEMM, the gate on its HIP kernel, the
+    down projection, one autograd node that keeps x and the stacked pre-activation only; elsewhere the stock-torch line."""
 
     def __init__(self, config: ApertisConfig, intermediate_size: Optional[int] = None):
         super().__init__()
@@ -960,7 +962,19 @@ class SwiGLUFFN(nn.Module):
         self.w_down = nn.Linear(self.ffn_dim, self.hidden_size, bias=False)
         self.dropout = nn.Dropout(config.hidden_dropout_prob)
 
+    def _stacked_gate_up(self):
+        """w_gate | w_up as one [2 F, H] weight (they share their input): prepared per step / per generate()."""
+        srcs = (self.w_gate.weight, self.w_up.weight)
+        w_gu = ops.prepared_weight(("swiglu_gu", id(self)), srcs)
+        if w_gu is None:
+            w_gu = ops.cached_prep("swiglu_gu", srcs, lambda: torch.cat(srcs, dim=0))
+        return w_gu
+
     def forward(self, x):
+        if ops.swiglu_supported(x, self.ffn_dim):
+            y = ops.swiglu_mlp(x.reshape(-1, x.shape[-1]), self._stacked_gate_up(), self.w_down.weight,
+                               compute_dtype=_compute_dtype(x))
+            return self.dropout(y.reshape(*x.shape[:-1], self.hidden_size))
         return self.dropout(self.w_down(F.silu(self.w_gate(x)) * self.w_up(x)))
 
 
@@ -983,10 +997,14 @@ class ApertisFeedForward(nn.Module):
         self.output_dropout = nn.Dropout(config.hidden_dropout_prob)
 
     def register_train_prep(self, prep):
-        """The plain dense FFN's two weights into a TrainPrep (the expert system registers its own)."""
+        """The plain dense FFN's two weights, or the SwiGLU block's stacked gate | up and its down projection, into a TrainPrep
+        (the expert system registers its own)."""
         if isinstance(self.ffn, nn.Sequential):
             prep.add_plain(self.ffn[0].weight)
             prep.add_plain(self.ffn[3].weight)
+        elif isinstance(self.ffn, SwiGLUFFN):
+            prep.add_stack(("swiglu_gu", id(self.ffn)), (self.ffn.w_gate.weight, self.ffn.w_up.weight))
+            prep.add_plain(self.ffn.w_down.weight)
 
     def _dense_ffn(self, x):
         """Linear -> act -> Dropout -> Linear (core.py:861-866).  On the GPU the plain (non-MoE, non-SwiGLU) FFN runs on the

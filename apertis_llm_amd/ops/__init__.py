@@ -12,6 +12,7 @@ One module per subsystem (round 6: the 2 500-line ops.py split up):
     scan     selective scan and scan + skip + gate (staged / lean / look-back)
     decode   single-token decode step
     moe      gate, plan, gather-LN, combine, small-batch entrance, expert MLP
+    swiglu   SwiGLU feed-forward: stacked gate | up GEMM, the gate kernel, the down projection
     loss     cross-entropy, fused LM head + cross-entropy
     attention  standard_mha: RoPE, causal flash attention, KV-cache decode
     sample   generate()'s next-token selection (penalty, temperature, top-k, top-p, draw) in one launch
@@ -23,9 +24,9 @@ on `ops` still reaches the code that looks at it.
 import sys as _sys
 import types as _types
 
-from . import _base, prep, gemm, norm, ssm, scan, decode, moe, loss, attention, sample
+from . import _base, prep, gemm, norm, ssm, scan, decode, moe, swiglu, loss, attention, sample
 
-_MODULES = (_base, prep, gemm, norm, ssm, scan, decode, moe, loss, attention, sample)
+_MODULES = (_base, prep, gemm, norm, ssm, scan, decode, moe, swiglu, loss, attention, sample)
 # switches and counters that are REBOUND at run time (by tests, tools, parallel.py or the code itself): owner module per name
 _FORWARDED = {
     "SCAN_SINGLE_PASS": scan, "SCAN_LEAN": scan, "SCAN_LEAN_BWD": scan, "SCAN_LOOKBACK": scan, "SCAN_DT_FUSED": scan,
@@ -38,6 +39,7 @@ _FORWARDED = {
     "_TIMER": _base,
     "ATTN_FUSED": attention, "ATTN_DECODE_FUSED": attention, "ATTN_DECODE_GRAPH": attention,
     "SAMPLE_FUSED": sample, "SAMPLE_UNIFORMS": sample,
+    "SWIGLU_FUSED": swiglu,
 }
 for _m in _MODULES:
     for _k, _v in vars(_m).items():

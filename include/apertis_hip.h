@@ -55,7 +55,8 @@ extern "C" {
  * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does).
  * The RMSNorm entry points (apertis_rmsnorm_fwd / _bwd / _bwd_blocks, apertis_dropout_add_rmsnorm_fwd) were ADDED UNDER 4.12
  * without a bump: the test suite pins the version at 4.12 and no existing signature changed, so a binding written against the
- * earlier 4.12 header still calls every entry point it knows correctly; one that wants the RMSNorm family looks the symbols up. */
+ * earlier 4.12 header still calls every entry point it knows correctly; one that wants the RMSNorm family looks the symbols up.
+ * The SwiGLU entry points (apertis_swiglu_fwd / _bwd) joined them the same way, for the same reason: still 4.12. */
 #define APERTIS_ABI_VERSION ((4 << 16) | 12)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
@@ -548,6 +549,22 @@ int64_t apertis_rmsnorm_bwd_blocks(int64_t T, int64_t H);
 int apertis_dropout_add_rmsnorm_fwd(const void *blk, const int32_t *slot_of, const float *wk, int64_t K, const void *res,
                                     const float *scale, float eps, void *y, void *xn, float *rms, int64_t T, int64_t H,
                                     float drop_p, uint64_t seed, int dtype_x, int dtype_y, void *stream);
+
+/* The SwiGLU gate of the use_swiglu feed-forward (core.py:925-993) between its two GEMMs, bandwidth-bound.
+ * gu [rows, 2F] (row pitch 2F) is the output of ONE GEMM against the row-stacked weight [w_gate; w_up]: columns [0, F) the gate
+ * pre-activation g, columns [F, 2F) u.  With s = sigmoid(g):
+ *   forward   h [rows, F]     = g s u
+ *   backward  dgu [rows, 2F]:   dgu[r, c] = dh u s (1 + g (1 - s)),  dgu[r, F + c] = dh g s;
+ *             h_out [rows, F] (optional, a buffer other than dh) = g s u again - in bf16 the forward's bits - so that a caller
+ *             need not keep h for the down projection's weight gradient.
+ * fp32 arithmetic in both dtypes: IEEE expf / division for APERTIS_F32, the hardware exp2 / rcp of the GEMM epilogues for
+ * APERTIS_BF16, one rounding per output; g far in either tail (exp overflow / underflow) gives the finite limit.  16-byte
+ * accesses per lane, 64-bit offsets, a capped grid that strides over the rest.
+ * A null gu / h / dh / dgu, rows < 0, F <= 0, an unknown dtype: APERTIS_ERR_ARG.  F % 8 (bf16) / F % 4 (fp32), F >= 2^30 or a
+ * pointer off a 16-byte boundary: APERTIS_ERR_UNSUPPORTED.  rows == 0: APERTIS_OK, nothing is launched. */
+int apertis_swiglu_fwd(const void *gu, void *h, int64_t rows, int64_t F, int dtype, void *stream);
+int apertis_swiglu_bwd(const void *dh, const void *gu, void *dgu, void *h_out, int64_t rows, int64_t F, int dtype,
+                       void *stream);
 
 /* Combine (core.py:594,605 weights * expert_output, index_add_):
  *   out[s,:] = sum_{k asc, slot_of[s,k]>=0} wk[s,k] * yr[slot_of[s,k],:]   (zeros if none)

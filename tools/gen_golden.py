@@ -274,6 +274,55 @@ def gen_models_rms(core):
     npz(name, input_ids=ids, labels=labels, loss=out[0], logits=out[1], config_json=json.dumps(cfg.to_dict()), **sd_arrays(sd))
 
 
+def gen_models_swiglu(core):
+    """model_ssm_swiglu_rms: gen_models_rms' recipe with use_swiglu=True added (SwiGLUFFN, core.py:925-993).  The expert settings
+    stay in on purpose: SwiGLU wins over MoE (core.py:849-859) and the fixture pins it.  A seed of its own, so that the other
+    fixtures regenerate bit-identically.  Prints how far the logits move when every w_down is zeroed - the fixture must be able
+    to see the block - and widens the feed-forward weights further until that is at least 1e-2 of the largest logit."""
+    name = "model_ssm_swiglu_rms"
+    torch.manual_seed(zlib.crc32(name.encode()) % 1000)
+    cfg = core.ApertisConfig(vocab_size=96, hidden_size=32, num_hidden_layers=2, num_attention_heads=2, intermediate_size=64,
+                             attention_type="selective_ssm", use_expert_system=True, num_experts=4, experts_per_token=2,
+                             multimodal=False, use_rmsnorm=True, use_swiglu=True)
+    model = core.ApertisForCausalLM(cfg).eval()
+    with torch.no_grad():  # widen the init so logits are not ~0; the norm scales away from 1 so that they are seen
+        for n_, p in model.named_parameters():
+            if p.dim() > 1 and "token_embeddings" not in n_:
+                p.mul_(8.0)
+            elif n_.endswith(".scale"):
+                p.add_(0.25 * torch.randn_like(p))
+    ids = torch.randint(4, 96, (2, 12))
+    labels = ids.clone()
+    labels[0, :3] = -100
+    ffn = [p for n_, p in model.named_parameters() if any(t in n_ for t in (".w_gate.", ".w_up.", ".w_down."))]
+    downs = [p for n_, p in model.named_parameters() if ".w_down." in n_]
+    assert len(ffn) == 3 * cfg.num_hidden_layers and len(downs) == cfg.num_hidden_layers, [n_ for n_, _ in model.named_parameters()]
+    for extra in (1, 2, 4, 8):
+        with torch.no_grad():
+            out = model(input_ids=ids, labels=labels, use_cache=False)
+            kept = [p.clone() for p in downs]
+            for p in downs:
+                p.zero_()
+            off = model(input_ids=ids, labels=labels, use_cache=False)
+            for p, k in zip(downs, kept):
+                p.copy_(k)
+        moved = float((off[1] - out[1]).abs().max() / out[1].abs().max())
+        print(f"  {name}: feed-forward weights x{8 * extra}: zeroing every w_down moves the logits by {moved:.3e} of the largest")
+        if moved >= 1e-2:
+            break
+        with torch.no_grad():
+            for p in ffn:
+                p.mul_(2.0)
+    else:
+        raise SystemExit(f"{name}: the logits do not see the feed-forward block")
+    sd = {k: v.detach() for k, v in model.state_dict().items()}
+    ffn_dim = sd["model.layers.0.feed_forward.ffn.w_down.weight"].shape[1] if "model.layers.0.feed_forward.ffn.w_down.weight" in sd else -1
+    print(f"  {name}: loss ref {float(out[0]):.6f}; largest |logit| {float(out[1].abs().max()):.4f}; ffn_dim {ffn_dim}; "
+          f"{sum(k.endswith('.scale') for k in sd)} RMSNorm scales; {sum('w_gate' in k for k in sd)} SwiGLU blocks, "
+          f"{sum('expert' in k for k in sd)} expert tensors")
+    npz(name, input_ids=ids, labels=labels, loss=out[0], logits=out[1], config_json=json.dumps(cfg.to_dict()), **sd_arrays(sd))
+
+
 def gen_dims(core):
     table = {}
     for target, moe in [("125M", False), ("350M", True), ("1.5B", True), ("10M", False), ("7B", False), ("3B", True)]:
@@ -791,7 +840,7 @@ def gen_generate_sampled(core):
             raise SystemExit(f"{name}: no seed in 200 fits the eos rule with clear margins")
 
 
-GENERATORS = ["scan", "ssm_layer", "moe", "vision", "models", "models_rms", "dims", "data_formats", "trainer_run", "config1", "generate",
+GENERATORS = ["scan", "ssm_layer", "moe", "vision", "models", "models_rms", "models_swiglu", "dims", "data_formats", "trainer_run", "config1", "generate",
               "generate_long", "generate_sampled"]
 
 
