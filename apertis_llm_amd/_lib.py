@@ -182,6 +182,7 @@ SIGNATURES = {
     "apertis_attention_chunk_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
     "apertis_attention_chunk": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
                                        _i64, _i64, _i64, _i64, _i32, _vp]),
+    "apertis_attention_dead_rows": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
     "apertis_token_counts": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "apertis_sample_next": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _f32, _i32, _f32, _i64, _f32, _u64, _vp, _i64, _vp, _vp, _vp,
                                    _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -802,7 +802,9 @@ class ApertisAttention(nn.Module):
     def _fused_ok(self, q, att_mask, past_kv, output_att):
         """Whether this call takes the HIP RoPE + causal attention kernels: on the GPU, fp32 or bf16, D 64 or 128, no KV cache
         to extend, no attention weights asked for, and every query row keeps at least one valid key (a row without one gets a
-        uniform average over all keys in the reference, finfo.min saturating; the model's mask says so, _AttnMask)."""
+        uniform average over all keys in the reference, finfo.min saturating; the model's mask says so, _AttnMask) - or,
+        with ops.ATTN_LEFT_PAD, such rows exist (`att_mask.dead_rows`) and this is inference (eval, no grad): ops.causal_attention
+        then fills them with that average."""
         if not (ops.ATTN_FUSED and q.is_cuda and past_kv is None and not output_att
                 and ops.attention_supported(q, self.num_attention_heads)):
             return False
@@ -811,22 +813,27 @@ class ApertisAttention(nn.Module):
         if not isinstance(att_mask, _AttnMask):          # an additive mask handed in directly: only the stock path reads it
             return False
         kv = att_mask.key_valid
+        if att_mask.dead_rows and (self.training or torch.is_grad_enabled()):
+            return False
         return att_mask.fused_ok and (kv is None or tuple(kv.shape) == tuple(q.shape[:2]))
 
     def _fused_attention(self, q, k, v, att_mask, pos_ids, use_c):
         key_valid, default_pos = (att_mask.key_valid, att_mask.default_pos) if att_mask is not None else (None, False)
+        dead_rows = att_mask is not None and att_mask.dead_rows
         if self.rope is not None:
             # (the model's own positions 0..L-1 go in as None: explicit ones are range-checked on the host, a sync per call)
             q, k = ops.rope_qk(q, k, None if default_pos else pos_ids, self.rope.cos_cached, self.rope.sin_cached)
         cache = (k, v) if use_c else None
-        ctxv = ops.causal_attention(q, k, v, self.num_attention_heads, key_valid, self.attention_dropout.p, self.training)
+        ctxv = ops.causal_attention(q, k, v, self.num_attention_heads, key_valid, self.attention_dropout.p, self.training,
+                                    dead_rows=dead_rows)
         return self.out_proj(ctxv), cache
 
     def _decode_ok(self, q, att_mask, past_kv, output_att, use_c):
         """Whether this call is a single-token step the KV-cache decode kernels take: the past is a layer of an ops.KVCache
         with room for one more row and the projections' dtype, one query position, inference (no grad, eval, use_cache, no
         attention weights), on the GPU, D 64 or 128, both switches on, the position known on the host, and key 0 of every
-        sequence valid (the model's mask says so, _AttnMask: no row without a valid key).  Anything else with a KVCache in
+        sequence valid - with ops.ATTN_LEFT_PAD: any key of every sequence (the model's mask says so, _AttnMask: no row
+        without a valid key).  Anything else with a KVCache in
         flight runs the stock branch on the cache's views and returns plain tensors.
         A cache whose DEVICE step state is active (att_mask.step_cache; a captured graph replays such a step) brings length,
         position and key validity in device buffers: no host position, no host length, and the room in the cache and in the
@@ -867,7 +874,8 @@ class ApertisAttention(nn.Module):
         the past is a layer of an ops.KVCache that opted in (`multi_token`) with no device step state active, in the
         projections' dtype and with room for the Lq > 1 new rows; inference (no grad, eval, use_cache, no attention weights),
         on the GPU, D 64 or 128, both switches on; the model's own positions, known on the host (n .. n + Lq - 1); key 0 of
-        every sequence valid, so that every row has a valid key; the mask None or [B, n + Lq].  Anything else runs the stock
+        every sequence valid, so that every row has a valid key, or with ops.ATTN_LEFT_PAD the rows without one filled in
+        afterwards (`att_mask.dead_rows`); the mask None or [B, n + Lq].  Anything else runs the stock
         branch on the cache's views, as every multi-token forward against a cache without the flag does."""
         if not (isinstance(past_kv, ops.KVLayer) and past_kv.cache.multi_token and not past_kv.cache.step_active
                 and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and q.is_cuda and q.shape[1] > 1 and use_c and not output_att
@@ -884,7 +892,7 @@ class ApertisAttention(nn.Module):
         cache, layer = past_kv.cache, past_kv.layer
         cos, sin = (self.rope.cos_cached, self.rope.sin_cached) if self.rope is not None else (None, None)
         q = ops.kv_append_rope_chunk(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
-        ctxv = ops.attention_chunk(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
+        ctxv = ops.attention_chunk(q, cache, layer, self.num_attention_heads, att_mask.key_valid, dead_rows=att_mask.dead_rows)
         return self.out_proj(ctxv), cache
 
     def _heads(self, t):
@@ -916,7 +924,7 @@ class ApertisAttention(nn.Module):
             proxy = None
         else:
             # decode with a plain-tensor KV cache (or what the decode kernels do not take of a KVCache: its views are the
-            # past), output_attentions, other head dims, CPU, left padding: stock torch.
+            # past), output_attentions, other head dims, CPU, left padding without ops.ATTN_LEFT_PAD: stock torch.
             if isinstance(att_mask, _AttnMask):
                 att_mask = att_mask.additive()
             k, v = self.k_proj(x), self.v_proj(x)
@@ -1085,13 +1093,18 @@ class _AttnMask:
     valid key) and the step's position as a HOST integer (None when the caller gave position_ids: only a tensor knows them).
     A multi-token step against a `multi_token` KVCache reads the same two: `pos_host` is then the position of its first token.
     `step_cache`: the KVCache whose device step state carries length, position and key validity of this step instead (no
-    host integer, no mask tensor here)."""
-    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host", "step_cache")
+    host integer, no mask tensor here).
+    `dead_rows` (only with ops.ATTN_LEFT_PAD): key 0 of some sequence is masked (left padding), so a multi-token forward may
+    hold query rows without a valid key; the kernels still run, inference only, and ops.attention_dead_rows gives those rows
+    the reference's value."""
+    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host", "step_cache", "dead_rows")
 
-    def __init__(self, key_valid, fused_ok, default_pos, make_additive, decode_ok=False, pos_host=None, step_cache=None):
+    def __init__(self, key_valid, fused_ok, default_pos, make_additive, decode_ok=False, pos_host=None, step_cache=None,
+                 dead_rows=False):
         self.key_valid, self.fused_ok, self.default_pos = key_valid, fused_ok, default_pos
         self._make, self._additive = make_additive, None
         self.decode_ok, self.pos_host, self.step_cache = decode_ok, pos_host, step_cache
+        self.dead_rows = dead_rows
 
     def additive(self):
         if self._make is not None:
@@ -1206,23 +1219,32 @@ class ApertisModel(nn.Module):
 
     def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos, pos_host=None, step_cache=None):
         """The standard_mha layers' mask (_AttnMask).  One host sync when a mask is given, as before: whether anything is
-        padded and whether key 0 of every sequence is valid (then every query row has a valid key: right padding, the
+        padded, whether key 0 of every sequence is valid (then every query row has a valid key: right padding, the
         trainer's form, stays on the fused path with no cache, and a step against a KVCache on the decode kernels - a
-        finished sequence of generate() keeps key 0) come back together.  A step on a cache's device step state
-        (`step_cache`) has no mask tensor and NO host sync: the validity is the cache's buffer, and key 0 of every sequence
-        was valid when the state was activated (column 0 does not change afterwards)."""
+        finished sequence of generate() keeps key 0) and whether every sequence has a valid key at all come back together.
+        With ops.ATTN_LEFT_PAD a batch whose key 0 is masked somewhere (left padding) qualifies as well, marked `dead_rows`,
+        as long as every sequence has a valid key: a single-token step then has one, and the rows of a longer forward that
+        have none are filled in after the attention (ops.attention_dead_rows).  A multi-token piece going into a KVCache
+        (`pos_host` given) may still lie wholly inside a sequence's padding - the valid keys come with a later piece - and
+        the fill covers that exactly, so the last condition is not asked of it: with the switch on, a sequence that is
+        masked throughout such a piece takes the chunk kernels too.  A step on a cache's device step state (`step_cache`) has
+        no mask tensor and NO host sync: the validity is the cache's buffer, and every sequence had a valid key (key 0,
+        without ops.ATTN_LEFT_PAD) when the state was activated (those columns do not change afterwards)."""
         if step_cache is not None:
             return _AttnMask(None, False, False, None, True, None, step_cache)
         default_pos = default_pos and past_len == 0
         if attention_mask is None:
             return _AttnMask(None, True, default_pos, None, True, pos_host)
         valid = attention_mask.bool()
-        all_valid, col0 = torch.stack((valid.all(), valid[:, 0].all())).tolist()
+        all_valid, col0, each_any = torch.stack((valid.all(), valid[:, 0].all(), valid.any(1).all())).tolist()
         if all_valid:
             return _AttnMask(None, True, default_pos, None, True, pos_host)
-        return _AttnMask(attention_mask, bool(col0) and past_len == 0, default_pos,
+        piece = pos_host is not None and input_shape[1] > 1
+        dead_rows = bool(ops.ATTN_LEFT_PAD and not col0 and (each_any or piece))
+        ok = bool(col0) or dead_rows
+        return _AttnMask(attention_mask, ok and past_len == 0, default_pos,
                          lambda: self._prepare_decoder_attention_mask(attention_mask, input_shape, inputs_embeds, past_len),
-                         bool(col0), pos_host)
+                         ok, pos_host, dead_rows=dead_rows)
 
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
@@ -1696,8 +1718,9 @@ class ApertisForCausalLM(nn.Module):
         out = self(input_ids=ids, attention_mask=mask, position_ids=None, past_key_values=cache, use_cache=True)
         if out[4] is not cache:
             raise ops.ApertisHipError(f"generate(): a forward of {ids.shape[1]} tokens against the KVCache did not run on the "
-                                      "KV-cache kernels (key 0 of a sequence masked, or the attention mask does not cover "
-                                      "the prompt): there is no fallback that keeps the cache")
+                                      "KV-cache kernels (key 0 of a sequence masked without APERTIS_MHA_LEFT_PAD=1, a sequence "
+                                      "with no valid key, or the attention mask does not cover the prompt): there is no "
+                                      "fallback that keeps the cache")
         return out
 
     def _kv_cache_ok(self, past, tokens, max_new_tokens):
@@ -1723,7 +1746,8 @@ class ApertisForCausalLM(nn.Module):
         """Whether the remaining `left` token steps of a standard_mha model replay as a graph (opt-in: ops.ATTN_DECODE_GRAPH):
         every precondition of ApertisAttention._decode_ok that does not change from step to step, checked ONCE - the past is
         an ops.KVCache in the dtype the projections produce, with room for every remaining row; the rotary table reaches the
-        last position; key 0 of every sequence is valid (one host read here; column 0 does not change afterwards).  Anything
+        last position; key 0 of every sequence is valid, or with ops.ATTN_LEFT_PAD some key of every sequence (one host read
+        here; the columns so far do not change afterwards).  Anything
         else stays on the eager loop, which raises where it always did when a position runs off the table."""
         if not (ops.ATTN_DECODE_GRAPH and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and isinstance(past, ops.KVCache)
                 and not past.step_active and len(set(past.lengths)) == 1 and not self.config.output_attentions):
@@ -1735,7 +1759,9 @@ class ApertisForCausalLM(nn.Module):
                 and len(past) == len(self.model.layers) and ops.attention_decode_supported(past.k[0], attn.num_attention_heads)
                 and (attn.rope is None or n + left <= attn.rope.cos_cached.shape[0])):
             return False
-        return mask is None or (tuple(mask.shape) == (B, n + 1) and bool(mask[:, 0].all()))
+        if mask is None or tuple(mask.shape) != (B, n + 1):
+            return mask is None
+        return bool(mask.bool().any(1).all() if ops.ATTN_LEFT_PAD else mask[:, 0].all())
 
     def _generate_graph_tail(self, tokens, past, alive, left, prompt_len, min_new_tokens, eos, pad, sampler=None, mask=None):
         """Decoding of `left` more tokens through a captured HIP graph of the single-token step (reference core.py:1578-1644:

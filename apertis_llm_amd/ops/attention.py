@@ -1,10 +1,10 @@
 """standard_mha: interleaved-pair RoPE over the full width, causal softmax attention (flash style), and decode against a
 preallocated KV cache (KVCache): single-token steps (kv_append_rope, attention_decode) and multi-token steps
-(kv_append_rope_chunk, attention_chunk).
+(kv_append_rope_chunk, attention_chunk); the dead query rows of a left-padded batch (attention_dead_rows).
 
 Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autograd bookkeeping only; every computation is a
-HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip).  Tensors must live on a ROCm
-device.
+HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip, csrc/attention_deadrows.hip).
+Tensors must live on a ROCm device.
 """
 import os
 
@@ -17,6 +17,10 @@ from ._base import _launch, _require_gpu, _rows
 # the model's standard_mha layers take the fused path below (RoPE + attention kernels) when this is on and the call qualifies
 # (ApertisAttention._fused_ok); off: the stock torch attention everywhere (A/B and tests)
 ATTN_FUSED = True
+# a batch whose key 0 is masked in some sequence (left padding) takes the fused / chunk / decode kernels too, inference only:
+# its dead query rows - no valid key at or before their own position - are filled in by attention_dead_rows below.  OFF by
+# default (APERTIS_MHA_LEFT_PAD=1 turns it on): tests pin that such a batch runs the stock path under the default switches
+ATTN_LEFT_PAD = os.environ.get("APERTIS_MHA_LEFT_PAD", "0") == "1"
 
 
 def _positions(position_ids, B, L, max_pos):
@@ -138,14 +142,68 @@ def attention_supported(q, heads):
             and q.dtype in (torch.float32, torch.bfloat16))
 
 
-def causal_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=False):
+def _mask_rows(what, key_valid, B, Lk):
+    """key_valid [B, >= Lk] as the kernels read it: (int64 tensor with unit inner stride, row stride)."""
+    if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < Lk:
+        raise ApertisHipError(f"{what}: key_valid {tuple(key_valid.shape)}, expected ({B}, >= {Lk})")
+    if key_valid.dtype != torch.int64 or key_valid.stride(1) != 1:
+        key_valid = key_valid.to(torch.int64).contiguous()
+    return key_valid, (key_valid.stride(0) if B > 1 else key_valid.shape[1])
+
+
+def attention_dead_rows(out, v, key_valid, n=0):
+    """The dead rows of a causal attention output, IN PLACE on `out` [B, Lq, W]: row i sits at key position n + i and is dead
+    iff key_valid[b, :n + i + 1] is all zero (left padding; any mask).  The reference's finfo.min masks saturate on such a row
+    and its softmax is uniform over all Lk = n + Lq keys, so the row becomes the column mean of v[b, :Lk] (fp32 accumulation,
+    one rounding), the same for every head; causal_attention and attention_chunk leave zeros there.  Every other row keeps its
+    bits.  v: [B, >= Lk, W] in out's dtype (fp32 or bf16; a KV-cache buffer's strides are taken as they are); key_valid:
+    [B, >= Lk], nonzero = attend.  Returns `out`.  Inference only: nothing is saved for a backward."""
+    _require_gpu(out, v, key_valid)
+    if (out.dim() != 3 or v.dim() != 3 or out.shape[1] < 1 or out.dtype != v.dtype
+            or out.dtype not in (torch.float32, torch.bfloat16) or v.shape[0] != out.shape[0] or v.shape[2] != out.shape[2]
+            or n < 0 or v.shape[1] < n + out.shape[1] or key_valid is None):
+        raise ApertisHipError(f"attention_dead_rows: out {tuple(out.shape)} {out.dtype}, v {tuple(v.shape)} {v.dtype}, n {n} "
+                              "(out [B, Lq, W] and v [B, >= n + Lq, W], one dtype, fp32 or bf16, with a key_valid)")
+    B, Lq, W = out.shape
+    Lk, es = n + Lq, out.element_size()
+    if W % (16 // es):
+        raise ApertisHipError(f"attention_dead_rows: width {W} is not a multiple of {16 // es}")
+    o, o_rs, o_bs = _chunk3d(out, B, W, "attention_dead_rows out")
+    if o is not out or out.data_ptr() % 16 or (o_rs * es) % 16 or (B > 1 and (o_bs * es) % 16):
+        raise ApertisHipError("attention_dead_rows: out is written in place: unit inner stride, rows and batches on 16-byte "
+                              "boundaries")
+    v, v_rs, v_bs = _chunk3d(v[:, :Lk], B, W, "attention_dead_rows v")
+    if v.data_ptr() % 16 or (v_rs * es) % 16 or (B > 1 and (v_bs * es) % 16):
+        v = v.clone(memory_format=torch.contiguous_format)
+        v_rs, v_bs = W, Lk * W
+    key_valid, kv_rs = _mask_rows("attention_dead_rows", key_valid, B, Lk)
+    _launch("apertis_attention_dead_rows", _lib.load().apertis_attention_dead_rows,
+            (ptr(v), v_rs, v_bs, ptr(key_valid), kv_rs, ptr(out), o_rs, o_bs, B, Lq, int(n), W, dtype_code(out), stream_ptr()),
+            work=float(B) * Lk * W, detail=f"{B}x{Lk}x{W}", nbytes=float(B) * Lk * W * es)
+    return out
+
+
+def _dead_rows_inference(what, training, dropout_p, *ts):
+    """dead_rows=True is inference only: the reference's backward of a dead row is a dense uniform row that reaches every
+    key, and the backward kernels do not compute it."""
+    if (torch.is_grad_enabled() and any(t.requires_grad for t in ts)) or (training and dropout_p > 0):
+        raise ApertisHipError(f"{what}: dead_rows=True is inference only (no input that requires grad under autograd, no "
+                              "attention dropout in training)")
+
+
+def causal_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=False, dead_rows=False):
     """softmax(Q K^T / sqrt(D) + causal and key-padding mask) V per head, with attention dropout in training.
     q, k, v: [B, L, heads*D] (head h in columns [h*D, (h+1)*D)), one dtype, fp32 or bf16, D in {64, 128}; returns O in the same
     layout (out_proj reads it directly).  key_valid: [B, L] (the raw attention_mask, nonzero = attend) or None.  Dropout keeps
     element (i, j) of head (b, h) by the library's counter hash with a seed drawn from torch's RNG here (a checkpointed
     recompute draws the same one); the backward regenerates the mask.  Saved for the backward: q, k, v, O and LSE [B, heads, L]
-    fp32, never an L x L tensor."""
+    fp32, never an L x L tensor.
+    A query row with no valid key at or before it (left padding) comes out as zeros; dead_rows=True (inference only: it raises
+    when an input requires grad under autograd, or with dropout in training) fills such rows with the reference's value
+    instead, the column mean of v over all L keys (attention_dead_rows)."""
     _require_gpu(q, k, v, key_valid)
+    if dead_rows:
+        _dead_rows_inference("causal_attention", training, dropout_p, q, k, v)
     if not (q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype) or not attention_supported(q, heads):
         raise ApertisHipError(f"causal_attention: q/k/v {tuple(q.shape)} {q.dtype} with {heads} heads (D 64 or 128, fp32 or bf16, "
                               "one shape and dtype)")
@@ -159,7 +217,10 @@ def causal_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=Fal
     if not 0.0 <= p < 1.0:
         raise ApertisHipError(f"causal_attention: dropout_p {dropout_p} outside [0, 1)")
     seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0
-    return _CausalAttention.apply(q, k, v, int(heads), key_valid, p, seed)
+    out = _CausalAttention.apply(q, k, v, int(heads), key_valid, p, seed)
+    if dead_rows and key_valid is not None and B:
+        attention_dead_rows(out, v, key_valid)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------- KV-cache decode
@@ -496,15 +557,19 @@ def attention_chunk_workspace_bytes(B, heads, Lq, D, splits):
     return int(_lib.load().apertis_attention_chunk_workspace_bytes(B, heads, Lq, D, splits))
 
 
-def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0):
+def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0, dead_rows=False):
     """Causal softmax attention of the Lq rows kv_append_rope_chunk has JUST appended to layer `layer` of `cache` over
     everything the layer holds: row i of q ([B, Lq, W], the cache's dtype, D = W / heads in {64, 128}) sits at key position
     n + i, n = lengths[layer] - Lq, and attends keys j <= n + i.  Returns O [B, Lq, W] where out_proj reads it.  key_valid:
     [B, >= n + Lq] (the raw attention_mask, nonzero = attend; later columns are never read) or None.  splits: 0 =
     apertis_attention_chunk_splits' choice, else 1..ATTN_DECODE_MAX_SPLITS runs of every wave's key tiles; the same inputs and
     split count give the same bits, and at one split row i has the bits causal_attention gives row n + i of the whole
-    sequence.  Inference only (no dropout, nothing saved for a backward)."""
+    sequence.  Inference only (no dropout, nothing saved for a backward).  A row with no valid key at or before it comes out
+    as zeros; dead_rows=True fills such rows (after the merge of the runs) with the reference's value, the column mean of the
+    layer's v rows [0, n + Lq) (attention_dead_rows; it raises when q requires grad under autograd)."""
     _require_gpu(q, cache.k[layer], key_valid)
+    if dead_rows:
+        _dead_rows_inference("attention_chunk", False, 0.0, q)
     lib = _lib.load()
     kc, vc = cache.k[layer], cache.v[layer]
     B, cap, W = kc.shape
@@ -535,6 +600,8 @@ def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0):
              ptr(out), W, ptr(ws), B, Lq, Lk - Lq, heads, D, ns, dtype_code(q), stream_ptr()),
             work=4.0 * B * W * Lq * (Lk - Lq + (Lq + 1) / 2), detail=f"{B}x{heads}x{D}x{Lq}",
             nbytes=(2.0 * B * Lk + 2.0 * B * Lq) * W * q.element_size())
+    if dead_rows and key_valid is not None and B:
+        attention_dead_rows(out, vc, key_valid, Lk - Lq)
     return out
 
 

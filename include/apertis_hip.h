@@ -913,6 +913,24 @@ int apertis_attention_chunk(const void *q, int64_t q_rs, const void *k_cache, in
                             int64_t out_rs, float *workspace, int64_t B, int64_t Lq, int64_t n, int64_t H, int64_t D,
                             int64_t splits, int dtype, void *stream);
 
+/* apertis_attention_dead_rows: the DEAD query rows of a causal attention under a key-padding mask (left padding), filled in
+ * after apertis_attention_fwd / apertis_attention_chunk, which write zeros there.  Row i of a chunk of Lq query rows sits at key
+ * position n + i (n = 0: a whole sequence); it is dead iff no j <= n + i has key_valid[b, j] != 0, i.e. n + i < first_valid[b],
+ * the first nonzero of the Lk = n + Lq mask columns (Lk if there is none; any mask, not only contiguous padding).  The
+ * reference adds finfo.min for both masks, so such a row's softmax is uniform over ALL Lk keys: for dead rows
+ *   out[b, i, 0:W] = (1 / Lk) * sum_{j < Lk} V[b, j, 0:W]      (fp32 accumulation, rounded once to the dtype)
+ * and every other element of out keeps its bits.  Head-agnostic: W = H * D columns.
+ *   v          : [B, >= Lk, W], row stride v_rs >= W, batch stride v_bs >= Lk * v_rs (a KV-cache buffer as it is)
+ *   key_valid  : int64 [B, >= Lk], row stride kv_rs >= Lk, nonzero = attend; not NULL
+ *   out        : [B, Lq, W], row stride out_rs >= W, batch stride out_bs >= Lq * out_rs
+ * fp32 or bf16.  Pointers and strides in bytes are multiples of 16 and W of 16 bytes' worth of elements, B <= 65535, else
+ * APERTIS_ERR_UNSUPPORTED; a NULL pointer, W <= 0, Lq < 1, n < 0 or a short stride is APERTIS_ERR_ARG, all before any launch.
+ * One launch, grid (column blocks of 256 bytes, B): a sequence without a dead row costs one pass over its mask row; the
+ * others read their V once (B_pad * Lk * W elements).  No atomics: the same inputs give the same bits. */
+int apertis_attention_dead_rows(const void *v, int64_t v_rs, int64_t v_bs, const int64_t *key_valid, int64_t kv_rs, void *out,
+                                int64_t out_rs, int64_t out_bs, int64_t B, int64_t Lq, int64_t n, int64_t W, int dtype,
+                                void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * generate()'s next-token selection (core.py:1605-1633), one launch per token step, one 1024-thread work-group per row.
  *
