@@ -17,6 +17,11 @@
 // Every product is oriented so that the later product sums over the row index of the earlier one (S^T = K Q^T then
 // O^T += V^T P^T), so no accumulator ever changes lanes.  bf16: P and dS are rounded to bf16 for their products.
 // The tiles and the forward's per-tile step live in attn_tile.h: the chunk kernel of attention_decode.hip runs the same step.
+//
+// CAUSAL = false is the bidirectional form (apertis_attention_full_fwd / _bwd: the vision tower): every wave walks every tile
+// of the other side and the diagonal leaves the predicates; everything else - tiles, MFMA forms, dropout hash, one writer per
+// output row - is shared.  A sequence with no valid key at all gets O = 0, LSE = +inf and zero gradients, which is what the
+// causal form gives a row without a valid key.
 #include "attn_tile.h"
 #include "rope_common.h"
 
@@ -36,13 +41,14 @@ struct AttnArgs {
 };
 
 // ---------------------------------------------------------------------------------------------------------- forward
-template <typename T, int D, bool DROP>
+template <typename T, int D, bool DROP, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_fwd_k(AttnArgs a) {
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t L = a.L;
   const int bh = blockIdx.y, H = a.H, b = bh / H, h = bh - b * H;
   const int64_t nblk = (L + WG_ROWS - 1) / WG_ROWS;
-  const int64_t q0 = (nblk - 1 - blockIdx.x) * WG_ROWS + (threadIdx.x >> 6) * ROWS;     // heaviest blocks first
+  // causal: heaviest blocks first; bidirectional: every block walks all of L, plain order
+  const int64_t q0 = (CAUSAL ? nblk - 1 - blockIdx.x : (int64_t)blockIdx.x) * WG_ROWS + (threadIdx.x >> 6) * ROWS;
   if (q0 >= L) return;
   const T *qp = static_cast<const T *>(a.q) + (int64_t)b * L * a.q_rs + h * D;
   const T *kp = static_cast<const T *>(a.k) + (int64_t)b * L * a.k_rs + h * D;
@@ -56,7 +62,7 @@ __global__ __launch_bounds__(256) void attn_fwd_k(AttnArgs a) {
   f32x4 acc[D / 16];
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int64_t last = min(q0 + ROWS - 1, L - 1);
+  const int64_t last = CAUSAL ? min(q0 + ROWS - 1, L - 1) : L - 1;
   const uint64_t drow = (uint64_t)bh * (uint64_t)L + (uint64_t)qi;
   for (int64_t kb = 0; kb <= last; kb += TILE) {
     const int64_t nrows = L - kb;
@@ -64,7 +70,9 @@ __global__ __launch_bounds__(256) void attn_fwd_k(AttnArgs a) {
         qf, kp, a.k_rs, vp, a.v_rs, kb, sl2, m, lsum, acc, lane, [=](int64_t kr) { return kr < L; },
         [=](int t) {
           const int64_t key = kb + tile_row(g, t);
-          bool ok = key <= qi && key < L;
+          bool ok;
+          if constexpr (CAUSAL) ok = key <= qi && key < L;
+          else ok = key < L;
           if (kv && ok) ok = kv[key] != 0;
           return ok;
         },
@@ -98,8 +106,8 @@ __global__ __launch_bounds__(256) void attn_dsum_k(AttnArgs a, int64_t rows) {
   a.dsum[(b * a.H + h) * a.L + i] = s;
 }
 
-// dK, dV for the 16 keys of a wave: loop over the query tiles at or below the diagonal
-template <typename T, int D, bool DROP>
+// dK, dV for the 16 keys of a wave: loop over the query tiles at or below the diagonal (bidirectional: over all of them)
+template <typename T, int D, bool DROP, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_k(AttnArgs a) {
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t L = a.L;
@@ -122,7 +130,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(AttnArgs a) {
   f32x4 dk[D / 16], dv[D / 16];
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt) dk[dt] = dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int64_t qb = k0 & ~(int64_t)(TILE - 1); qb < L; qb += TILE) {
+  for (int64_t qb = CAUSAL ? k0 & ~(int64_t)(TILE - 1) : 0; qb < L; qb += TILE) {
     f32x4 pd[2], ds[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -136,7 +144,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t qi = qb + 16 * s + 4 * g + r;
-        const bool ok = kok && qi < L && kj <= qi;
+        bool ok;
+        if constexpr (CAUSAL) ok = kok && qi < L && kj <= qi;
+        else ok = kok && qi < L;
         const float p = ok ? exp2f(sv[r] * sl2 - lse[qi] * LOG2E_F) : 0.f;
         float dpr = dp[r], pdr = p;
         if constexpr (DROP) {
@@ -158,14 +168,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(AttnArgs a) {
   store_cols<T, D>(static_cast<T *>(a.dv) + (bo + kj) * a.d_rs + h * D, dv, 1.f, lane);
 }
 
-// dQ for the 16 queries of a wave: loop over the key tiles at or below the diagonal
-template <typename T, int D, bool DROP>
+// dQ for the 16 queries of a wave: loop over the key tiles at or below the diagonal (bidirectional: over all of them)
+template <typename T, int D, bool DROP, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t L = a.L;
   const int bh = blockIdx.y, H = a.H, b = bh / H, h = bh - b * H;
   const int64_t nblk = (L + WG_ROWS - 1) / WG_ROWS;
-  const int64_t q0 = (nblk - 1 - blockIdx.x) * WG_ROWS + (threadIdx.x >> 6) * ROWS;
+  const int64_t q0 = (CAUSAL ? nblk - 1 - blockIdx.x : (int64_t)blockIdx.x) * WG_ROWS + (threadIdx.x >> 6) * ROWS;
   if (q0 >= L) return;
   const int64_t bo = (int64_t)b * L;
   const T *qp = static_cast<const T *>(a.q) + bo * a.q_rs + h * D;
@@ -185,7 +195,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
   f32x4 dq[D / 16];
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int64_t last = min(q0 + ROWS - 1, L - 1);
+  const int64_t last = CAUSAL ? min(q0 + ROWS - 1, L - 1) : L - 1;
   for (int64_t kb = 0; kb <= last; kb += TILE) {
     f32x4 ds[2];
 #pragma unroll
@@ -200,7 +210,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t key = kb + 16 * s + 4 * g + r;
-        bool ok = qok && key <= qi;
+        bool ok;
+        if constexpr (CAUSAL) ok = qok && key <= qi;
+        else ok = qok && key < L;
         if (kv && ok) ok = kv[key] != 0;
         const float p = ok ? exp2f(sv[r] * sl2 - lse2) : 0.f;
         float dpr = dp[r];
@@ -215,25 +227,25 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(AttnArgs a) {
   store_cols<T, D>(static_cast<T *>(a.dq) + (bo + qi) * a.d_rs + h * D, dq, a.scale, lane);
 }
 
-template <typename T, int D, bool DROP> int launch_fwd(const AttnArgs &a, int64_t B, hipStream_t st) {
+template <typename T, int D, bool DROP, bool CAUSAL> int launch_fwd(const AttnArgs &a, int64_t B, hipStream_t st) {
   const dim3 grid((unsigned)ceil_div64(a.L, WG_ROWS), (unsigned)(B * a.H));
-  hipLaunchKernelGGL((attn_fwd_k<T, D, DROP>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((attn_fwd_k<T, D, DROP, CAUSAL>), grid, dim3(256), 0, st, a);
   return apertis_check_launch();
 }
-template <typename T, int D, bool DROP> int launch_bwd(const AttnArgs &a, int64_t B, hipStream_t st) {
+template <typename T, int D, bool DROP, bool CAUSAL> int launch_bwd(const AttnArgs &a, int64_t B, hipStream_t st) {
   const int64_t rows = B * a.L;
   hipLaunchKernelGGL((attn_dsum_k<T, D>), dim3((unsigned)ceil_div64(rows * a.H, 256)), dim3(256), 0, st, a, rows);
   const dim3 grid((unsigned)ceil_div64(a.L, WG_ROWS), (unsigned)(B * a.H));
-  hipLaunchKernelGGL((attn_bwd_dkv_k<T, D, DROP>), grid, dim3(256), 0, st, a);
-  hipLaunchKernelGGL((attn_bwd_dq_k<T, D, DROP>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((attn_bwd_dkv_k<T, D, DROP, CAUSAL>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((attn_bwd_dq_k<T, D, DROP, CAUSAL>), grid, dim3(256), 0, st, a);
   return apertis_check_launch();
 }
 
-template <bool BWD> int dispatch(const AttnArgs &a, int64_t B, int64_t D, int dtype, bool drop, hipStream_t st) {
-#define APERTIS_ATTN_CASE(T, DD)                                                                            \
-  if (D == DD) {                                                                                            \
-    if constexpr (BWD) return drop ? launch_bwd<T, DD, true>(a, B, st) : launch_bwd<T, DD, false>(a, B, st); \
-    else return drop ? launch_fwd<T, DD, true>(a, B, st) : launch_fwd<T, DD, false>(a, B, st);              \
+template <bool BWD, bool CAUSAL> int dispatch(const AttnArgs &a, int64_t B, int64_t D, int dtype, bool drop, hipStream_t st) {
+#define APERTIS_ATTN_CASE(T, DD)                                                                                                \
+  if (D == DD) {                                                                                                                \
+    if constexpr (BWD) return drop ? launch_bwd<T, DD, true, CAUSAL>(a, B, st) : launch_bwd<T, DD, false, CAUSAL>(a, B, st);   \
+    else return drop ? launch_fwd<T, DD, true, CAUSAL>(a, B, st) : launch_fwd<T, DD, false, CAUSAL>(a, B, st);                \
   }
   if (dtype == APERTIS_F32) {
     APERTIS_ATTN_CASE(float, 64)
@@ -319,6 +331,35 @@ int rope_entry(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const i
   return apertis_check_launch();
 }
 
+template <bool CAUSAL>
+int attention_fwd_entry(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs, const int64_t *key_valid,
+                        void *out, int64_t out_rs, float *lse, int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p,
+                        uint64_t seed, int dtype, void *stream) {
+  const int rc = attn_check({q, k, v, out, lse}, {q_rs, k_rs, v_rs, out_rs}, B, L, H, D, dropout_p, dtype);
+  if (rc) return rc;
+  if (B == 0 || L == 0) return APERTIS_OK;
+  AttnArgs a = make_args(L, H, D, dropout_p, seed);
+  a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.key_valid = key_valid;
+  a.q_rs = q_rs; a.k_rs = k_rs; a.v_rs = v_rs; a.o_rs = out_rs;
+  return dispatch<false, CAUSAL>(a, B, D, dtype, dropout_p > 0.f, (hipStream_t)stream);
+}
+
+template <bool CAUSAL>
+int attention_bwd_entry(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs, const void *out,
+                        int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse, const int64_t *key_valid,
+                        float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B, int64_t L, int64_t H, int64_t D,
+                        float dropout_p, uint64_t seed, int dtype, void *stream) {
+  const int rc = attn_check({q, k, v, out, dout, lse, workspace, dq, dk, dv}, {q_rs, k_rs, v_rs, out_rs, dout_rs, d_rs}, B, L,
+                            H, D, dropout_p, dtype);
+  if (rc) return rc;
+  if (B == 0 || L == 0) return APERTIS_OK;
+  AttnArgs a = make_args(L, H, D, dropout_p, seed);
+  a.q = q; a.k = k; a.v = v; a.o = out; a.dout = dout; a.lse = (float *)lse; a.key_valid = key_valid; a.dsum = workspace;
+  a.dq = dq; a.dk = dk; a.dv = dv;
+  a.q_rs = q_rs; a.k_rs = k_rs; a.v_rs = v_rs; a.o_rs = out_rs; a.do_rs = dout_rs; a.d_rs = d_rs;
+  return dispatch<true, CAUSAL>(a, B, D, dtype, dropout_p > 0.f, (hipStream_t)stream);
+}
+
 }  // namespace
 
 extern "C" int apertis_rope_qk_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const int64_t *position_ids,
@@ -339,13 +380,7 @@ extern "C" int apertis_rope_qk_bwd(const void *dq_out, int64_t dq_rs, const void
 extern "C" int apertis_attention_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
                                      const int64_t *key_valid, void *out, int64_t out_rs, float *lse, int64_t B, int64_t L,
                                      int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream) {
-  const int rc = attn_check({q, k, v, out, lse}, {q_rs, k_rs, v_rs, out_rs}, B, L, H, D, dropout_p, dtype);
-  if (rc) return rc;
-  if (B == 0 || L == 0) return APERTIS_OK;
-  AttnArgs a = make_args(L, H, D, dropout_p, seed);
-  a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.key_valid = key_valid;
-  a.q_rs = q_rs; a.k_rs = k_rs; a.v_rs = v_rs; a.o_rs = out_rs;
-  return dispatch<false>(a, B, D, dtype, dropout_p > 0.f, (hipStream_t)stream);
+  return attention_fwd_entry<true>(q, q_rs, k, k_rs, v, v_rs, key_valid, out, out_rs, lse, B, L, H, D, dropout_p, seed, dtype, stream);
 }
 
 extern "C" int64_t apertis_attention_bwd_workspace_bytes(int64_t B, int64_t L, int64_t H) {
@@ -358,13 +393,22 @@ extern "C" int apertis_attention_bwd(const void *q, int64_t q_rs, const void *k,
                                      const int64_t *key_valid, float *workspace, void *dq, void *dk, void *dv, int64_t d_rs,
                                      int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype,
                                      void *stream) {
-  const int rc = attn_check({q, k, v, out, dout, lse, workspace, dq, dk, dv}, {q_rs, k_rs, v_rs, out_rs, dout_rs, d_rs}, B, L,
-                            H, D, dropout_p, dtype);
-  if (rc) return rc;
-  if (B == 0 || L == 0) return APERTIS_OK;
-  AttnArgs a = make_args(L, H, D, dropout_p, seed);
-  a.q = q; a.k = k; a.v = v; a.o = out; a.dout = dout; a.lse = (float *)lse; a.key_valid = key_valid; a.dsum = workspace;
-  a.dq = dq; a.dk = dk; a.dv = dv;
-  a.q_rs = q_rs; a.k_rs = k_rs; a.v_rs = v_rs; a.o_rs = out_rs; a.do_rs = dout_rs; a.d_rs = d_rs;
-  return dispatch<true>(a, B, D, dtype, dropout_p > 0.f, (hipStream_t)stream);
+  return attention_bwd_entry<true>(q, q_rs, k, k_rs, v, v_rs, out, out_rs, dout, dout_rs, lse, key_valid, workspace, dq, dk, dv, d_rs,
+                                   B, L, H, D, dropout_p, seed, dtype, stream);
+}
+
+// the bidirectional pair (the vision tower): the same checks, the CAUSAL = false kernels
+extern "C" int apertis_attention_full_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                          const int64_t *key_valid, void *out, int64_t out_rs, float *lse, int64_t B, int64_t L,
+                                          int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream) {
+  return attention_fwd_entry<false>(q, q_rs, k, k_rs, v, v_rs, key_valid, out, out_rs, lse, B, L, H, D, dropout_p, seed, dtype, stream);
+}
+
+extern "C" int apertis_attention_full_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                          const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
+                                          const int64_t *key_valid, float *workspace, void *dq, void *dk, void *dv, int64_t d_rs,
+                                          int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype,
+                                          void *stream) {
+  return attention_bwd_entry<false>(q, q_rs, k, k_rs, v, v_rs, out, out_rs, dout, dout_rs, lse, key_valid, workspace, dq, dk, dv, d_rs,
+                                    B, L, H, D, dropout_p, seed, dtype, stream);
 }

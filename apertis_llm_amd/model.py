@@ -26,6 +26,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .multimodal import UnifiedMultimodalEncoder
+from .ops._base import _compute_dtype          # (shared with the vision tower)
 
 logger = logging.getLogger(__name__)
 
@@ -151,15 +152,6 @@ def _activation_module(name: str) -> nn.Module:
 
 def _activation_name(name: str) -> str:
     return name if name in ("gelu", "relu", "silu", "swish") else "gelu"
-
-
-def _compute_dtype(t: torch.Tensor) -> torch.dtype:
-    """bf16 under torch.autocast (the reference trains under fp16 autocast, pipeline.py:533; the
-    MI355X build maps that to bf16 and drops the GradScaler), else the tensor's own dtype."""
-    if torch.is_autocast_enabled():
-        dt = torch.get_autocast_dtype("cuda")
-        return torch.bfloat16 if dt in (torch.bfloat16, torch.float16) else dt
-    return t.dtype if t.dtype in (torch.float32, torch.bfloat16) else torch.float32
 
 
 class HipLayerNorm(nn.LayerNorm):

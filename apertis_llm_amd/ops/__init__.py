@@ -14,7 +14,7 @@ One module per subsystem (round 6: the 2 500-line ops.py split up):
     moe      gate, plan, gather-LN, combine, small-batch entrance, expert MLP
     swiglu   SwiGLU feed-forward: stacked gate | up GEMM, the gate kernel, the down projection
     loss     cross-entropy, fused LM head + cross-entropy
-    attention  standard_mha: RoPE, causal flash attention, KV-cache decode
+    attention  standard_mha: RoPE, causal flash attention, KV-cache decode; the vision tower's bidirectional attention
     sample   generate()'s next-token selection (penalty, temperature, top-k, top-p, draw) in one launch
 `from apertis_llm_amd import ops; ops.<name>` reaches every name of every module, private helpers included (tests and tools use
 them).  The module-level SWITCHES (SCAN_LOOKBACK, TRAIN_PREP, GEMM_DYNAMIC_QUEUE, ...) live in the module whose code reads them;
@@ -38,7 +38,7 @@ _FORWARDED = {
     "TRAIN_PREP": prep, "WEIGHT_EPOCH": prep, "_ACTIVE_TRAIN_PREP": prep, "_prep_scope_depth": prep,
     "_TIMER": _base,
     "ATTN_FUSED": attention, "ATTN_DECODE_FUSED": attention, "ATTN_DECODE_GRAPH": attention,
-    "ATTN_LEFT_PAD": attention,
+    "ATTN_LEFT_PAD": attention, "VIT_FUSED": attention,
     "SAMPLE_FUSED": sample, "SAMPLE_UNIFORMS": sample,
     "SWIGLU_FUSED": swiglu,
 }

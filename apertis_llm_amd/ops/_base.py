@@ -20,6 +20,15 @@ def _f32(t):
     return t.detach().float().contiguous()
 
 
+def _compute_dtype(t):
+    """bf16 under torch.autocast (the reference trains under fp16 autocast, pipeline.py:533; the
+    MI355X build maps that to bf16 and drops the GradScaler), else the tensor's own dtype."""
+    if torch.is_autocast_enabled():
+        dt = torch.get_autocast_dtype("cuda")
+        return torch.bfloat16 if dt in (torch.bfloat16, torch.float16) else dt
+    return t.dtype if t.dtype in (torch.float32, torch.bfloat16) else torch.float32
+
+
 _TIMER = None
 
 

@@ -1,6 +1,7 @@
 """standard_mha: interleaved-pair RoPE over the full width, causal softmax attention (flash style), and decode against a
 preallocated KV cache (KVCache): single-token steps (kv_append_rope, attention_decode) and multi-token steps
-(kv_append_rope_chunk, attention_chunk); the dead query rows of a left-padded batch (attention_dead_rows).
+(kv_append_rope_chunk, attention_chunk); the dead query rows of a left-padded batch (attention_dead_rows).  The vision tower's
+bidirectional attention (full_attention, full_attention_qkv: the same kernels with the diagonal compiled out).
 
 Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autograd bookkeeping only; every computation is a
 HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip, csrc/attention_deadrows.hip).
@@ -221,6 +222,153 @@ def causal_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=Fal
     if dead_rows and key_valid is not None and B:
         attention_dead_rows(out, v, key_valid)
     return out
+
+
+# ------------------------------------------------------------------------------------------- bidirectional attention
+# the vision tower (multimodal.py) runs its encoder layers on the project's kernels - LayerNorm boundaries, MFMA GEMMs, the
+# attention below, the expert-MLP pair - when this is on and the tower qualifies (UnifiedMultimodalEncoder.fused_supported).
+# OFF by default (APERTIS_VIT_FUSED=1 turns it on): it changes the default path's bits and the tower's train-mode dropout
+# stream (counter hash instead of Philox); flipping the default is a change of its own
+VIT_FUSED = os.environ.get("APERTIS_VIT_FUSED", "0") == "1"
+
+
+def _full_attn_flops(B, L, H, D):
+    """Bidirectional forward: 4*B*H*D*L^2 (two products over the whole square)."""
+    return 4.0 * B * H * D * L * L
+
+
+def _full_fwd(q, q_rs, k, k_rs, v, v_rs, key_valid, B, L, W, heads, p, seed):
+    """One apertis_attention_full_fwd launch: (O [B, L, W] packed, LSE [B, heads, L] fp32)."""
+    lib = _lib.load()
+    out = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
+    lse = torch.empty(B, heads, L, device=q.device, dtype=torch.float32)
+    _launch("apertis_attention_full_fwd", lib.apertis_attention_full_fwd,
+            (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(key_valid), ptr(out), W, ptr(lse), B, L, heads, W // heads, p, seed,
+             dtype_code(q), stream_ptr()), work=_full_attn_flops(B, L, heads, W // heads))
+    return out, lse
+
+
+def _full_bwd(q, q_rs, k, k_rs, v, v_rs, out, dout, lse, key_valid, dq, dk, dv, d_rs, B, L, W, heads, p, seed):
+    """One apertis_attention_full_bwd launch into dq, dk, dv (one row stride d_rs)."""
+    lib = _lib.load()
+    dout = dout.to(q.dtype)
+    dout, do_rs = _rows(dout, W)
+    if dout.data_ptr() % 16 or (do_rs * dout.element_size()) % 16:
+        dout, do_rs = dout.clone(memory_format=torch.contiguous_format), W
+    ws = torch.empty(lib.apertis_attention_bwd_workspace_bytes(B, L, heads) // 4, device=q.device, dtype=torch.float32)
+    _launch("apertis_attention_full_bwd", lib.apertis_attention_full_bwd,
+            (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(out), W, ptr(dout), do_rs, ptr(lse), ptr(key_valid), ptr(ws), ptr(dq),
+             ptr(dk), ptr(dv), d_rs, B, L, heads, W // heads, p, seed, dtype_code(q), stream_ptr()),
+            work=2.5 * _full_attn_flops(B, L, heads, W // heads))
+
+
+class _FullAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, heads, key_valid, p, seed):
+        B, L, W = q.shape
+        q, q_rs = _rows(q, W)
+        k, k_rs = _rows(k, W)
+        v, v_rs = _rows(v, W)
+        out, lse = _full_fwd(q, q_rs, k, k_rs, v, v_rs, key_valid, B, L, W, heads, p, seed)
+        ctx.save_for_backward(q, k, v, out, lse, key_valid)
+        ctx.cfg = (heads, p, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, key_valid = ctx.saved_tensors
+        heads, p, seed = ctx.cfg
+        B, L, W = q.shape
+        dq = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
+        dk = torch.empty_like(dq)
+        dv = torch.empty_like(dq)
+        _full_bwd(q, q.stride(-2), k, k.stride(-2), v, v.stride(-2), out, dout, lse, key_valid, dq, dk, dv, W, B, L, W, heads,
+                  p, seed)
+        return dq, dk, dv, None, None, None, None
+
+
+class _FullAttentionQKV(torch.autograd.Function):
+    """_FullAttention on the column slices of ONE [B, L, 3W] tensor: nothing is copied on the way in (row stride 3W), and the
+    backward writes dq | dk | dv into the column slices of ONE [B, L, 3W] gradient - three slice backwards would each
+    materialise a zero-filled [B, L, 3W] and autograd would add them."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, p, seed):
+        B, L, W3 = qkv.shape
+        W = W3 // 3
+        qkv, rs = _rows(qkv, W3)
+        if qkv.data_ptr() % 16 or (rs * qkv.element_size()) % 16:
+            qkv, rs = qkv.clone(memory_format=torch.contiguous_format), W3
+        out, lse = _full_fwd(qkv[..., :W], rs, qkv[..., W:2 * W], rs, qkv[..., 2 * W:], rs, None, B, L, W, heads, p, seed)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.cfg = (heads, p, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        heads, p, seed = ctx.cfg
+        B, L, W3 = qkv.shape
+        W, rs = W3 // 3, qkv.stride(-2)
+        d = torch.empty(B, L, W3, device=qkv.device, dtype=qkv.dtype)
+        _full_bwd(qkv[..., :W], rs, qkv[..., W:2 * W], rs, qkv[..., 2 * W:], rs, out, dout, lse, None, d[..., :W],
+                  d[..., W:2 * W], d[..., 2 * W:], W3, B, L, W, heads, p, seed)
+        return d, None, None, None
+
+
+def full_attention_supported(q, heads, packed=False):
+    """Whether full_attention takes q [B, L, heads*D] - or, packed=True, full_attention_qkv takes qkv [B, L, 3*heads*D] - of
+    this dtype, head dim and batch (D 64 or 128, fp32 or bf16, B*heads <= 65535: the grid's y dimension)."""
+    if q.dim() != 3 or heads < 1 or (packed and q.shape[-1] % 3):
+        return False
+    W = q.shape[-1] // 3 if packed else q.shape[-1]
+    return (W % heads == 0 and W // heads in (64, 128) and q.dtype in (torch.float32, torch.bfloat16)
+            and q.shape[0] * heads <= 65535)
+
+
+def _full_p_seed(what, dropout_p, training):
+    p = float(dropout_p) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ApertisHipError(f"{what}: dropout_p {dropout_p} outside [0, 1)")
+    return p, (int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0)
+
+
+def full_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=False):
+    """softmax(Q K^T / sqrt(D) + key-padding mask) V per head WITHOUT a causal mask (bidirectional: the vision tower), with
+    attention dropout in training.  The layout contract of causal_attention: q, k, v [B, L, heads*D] (head h in columns
+    [h*D, (h+1)*D)), one dtype, fp32 or bf16, D in {64, 128}, B*heads <= 65535, row-strided views taken as they are; returns
+    O in the same layout.  key_valid: [B, L] (nonzero = attend), ANY pattern, holes included, or None.  Dropout: the counter
+    hash of causal_attention with a seed drawn from torch's RNG here; the backward regenerates the mask and is deterministic
+    (no atomics).  Saved for the backward: q, k, v, O and LSE [B, heads, L] fp32, never an L x L tensor.
+    There is no dead-row notion here - every query sees the same keys.  A SEQUENCE WITH NO VALID KEY AT ALL comes out as
+    zeros (LSE +inf) and all three of its gradients are zero."""
+    _require_gpu(q, k, v, key_valid)
+    if not (q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype) or not full_attention_supported(q, heads):
+        raise ApertisHipError(f"full_attention: q/k/v {tuple(q.shape)} {q.dtype} with {heads} heads (D 64 or 128, fp32 or bf16, "
+                              "one shape and dtype, B*heads <= 65535)")
+    B, L, _ = q.shape
+    if key_valid is not None:
+        if tuple(key_valid.shape) != (B, L):
+            raise ApertisHipError(f"full_attention: key_valid {tuple(key_valid.shape)}, expected ({B}, {L})")
+        if key_valid.dtype != torch.int64 or not key_valid.is_contiguous():
+            key_valid = key_valid.to(torch.int64).contiguous()
+    p, seed = _full_p_seed("full_attention", dropout_p, training)
+    return _FullAttention.apply(q, k, v, int(heads), key_valid, p, seed)
+
+
+def full_attention_qkv(qkv, heads, dropout_p=0.0, training=False):
+    """full_attention (no key mask) on the stacked [B, L, 3*W] output of ONE in-projection GEMM: q, k, v are its three column
+    slices, read in place with row stride 3*W, and the backward returns ONE [B, L, 3*W] gradient whose column slices the two
+    backward kernels wrote (dq | dk | dv).  Bit-identical to full_attention on copies of the slices.  Raises on a width
+    whose slices do not start on 16-byte boundaries."""
+    _require_gpu(qkv)
+    if not full_attention_supported(qkv, heads, packed=True):
+        raise ApertisHipError(f"full_attention_qkv: qkv {tuple(qkv.shape)} {qkv.dtype} with {heads} heads ([B, L, 3*heads*D], "
+                              "D 64 or 128, fp32 or bf16, B*heads <= 65535)")
+    if (qkv.shape[-1] // 3 * qkv.element_size()) % 16:
+        raise ApertisHipError(f"full_attention_qkv: the slices of width {qkv.shape[-1] // 3} are not 16-byte aligned")
+    p, seed = _full_p_seed("full_attention_qkv", dropout_p, training)
+    return _FullAttentionQKV.apply(qkv, int(heads), p, seed)
 
 
 # ---------------------------------------------------------------------------------------------------- KV-cache decode

@@ -56,7 +56,8 @@ extern "C" {
  * The RMSNorm entry points (apertis_rmsnorm_fwd / _bwd / _bwd_blocks, apertis_dropout_add_rmsnorm_fwd) were ADDED UNDER 4.12
  * without a bump: the test suite pins the version at 4.12 and no existing signature changed, so a binding written against the
  * earlier 4.12 header still calls every entry point it knows correctly; one that wants the RMSNorm family looks the symbols up.
- * The SwiGLU entry points (apertis_swiglu_fwd / _bwd) joined them the same way, for the same reason: still 4.12. */
+ * The SwiGLU entry points (apertis_swiglu_fwd / _bwd) joined them the same way, for the same reason: still 4.12.
+ * So did the bidirectional attention pair of the vision tower (apertis_attention_full_fwd / _bwd): still 4.12. */
 #define APERTIS_ABI_VERSION ((4 << 16) | 12)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
@@ -796,6 +797,21 @@ int apertis_attention_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_
                           const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
                           const int64_t *key_valid, float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B,
                           int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
+
+/* The same pair WITHOUT the causal mask (bidirectional: the vision tower's encoder layers):
+ *   O[b,i,h] = sum_{j < L, key_valid[b,j] != 0} drop(P[i,j]) V[b,j,h],  P = softmax over those j.
+ * Arguments, layouts, limits (D 64 / 128, fp32 / bf16, B*H <= 65535, 16-byte rows), checks before any launch, the dropout hash,
+ * the workspace (apertis_attention_bwd_workspace_bytes) and the determinism of the backward (no atomics: dK, dV per 64-key
+ * block, dQ per 64-query block) are those of apertis_attention_fwd / _bwd; the kernels are the same templates with the
+ * diagonal compiled out.  key_valid may hold any pattern, holes included.  A SEQUENCE WITH NO VALID KEY AT ALL gets O = 0 and
+ * LSE = +inf for every one of its rows, and dq = dk = dv = 0 (what the causal pair gives a row without a valid key). */
+int apertis_attention_full_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                               const int64_t *key_valid, void *out, int64_t out_rs, float *lse, int64_t B, int64_t L, int64_t H,
+                               int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
+int apertis_attention_full_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                               const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
+                               const int64_t *key_valid, float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B,
+                               int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * standard_mha single-token decode against a preallocated KV cache (the attention of core.py:639-700 with a past):
