@@ -812,10 +812,17 @@ class ApertisAttention(nn.Module):
     def _fused_attention(self, q, k, v, att_mask, pos_ids, use_c):
         key_valid, default_pos = (att_mask.key_valid, att_mask.default_pos) if att_mask is not None else (None, False)
         dead_rows = att_mask is not None and att_mask.dead_rows
+        layout = att_mask.layout if att_mask is not None else None
         if self.rope is not None:
-            # (the model's own positions 0..L-1 go in as None: explicit ones are range-checked on the host, a sync per call)
-            q, k = ops.rope_qk(q, k, None if default_pos else pos_ids, self.rope.cos_cached, self.rope.sin_cached)
+            # (the model's own positions 0..L-1 go in as None: explicit ones are range-checked on the host, a sync per call;
+            #  a layout's positions lie in [0, L) by construction: L against the table is the whole check)
+            q, k = ops.rope_qk(q, k, None if default_pos else pos_ids, self.rope.cos_cached, self.rope.sin_cached,
+                               in_range=layout is not None and att_mask.layout_pos)
         cache = (k, v) if use_c else None
+        if layout is not None:
+            ctxv = ops.document_attention(q, k, v, self.num_attention_heads, layout, key_valid, self.attention_dropout.p,
+                                          self.training)
+            return self.out_proj(ctxv), cache
         ctxv = ops.causal_attention(q, k, v, self.num_attention_heads, key_valid, self.attention_dropout.p, self.training,
                                     dead_rows=dead_rows)
         return self.out_proj(ctxv), cache
@@ -1088,11 +1095,17 @@ class _AttnMask:
     host integer, no mask tensor here).
     `dead_rows` (only with ops.ATTN_LEFT_PAD): key 0 of some sequence is masked (left padding), so a multi-token forward may
     hold query rows without a valid key; the kernels still run, inference only, and ops.attention_dead_rows gives those rows
-    the reference's value."""
-    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host", "step_cache", "dead_rows")
+    the reference's value.
+    `layout` (packed rows, `document_ids`): the ops.DocumentLayout of this forward, computed once; the fused path then runs
+    ops.document_attention, and the additive mask is the block-diagonal causal one.  `layout_pos`: the positions the layers
+    receive are the layout's own (positions within each document, all in [0, L)), so the per-layer RoPE call does not
+    range-check them on the host again."""
+    __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host", "step_cache", "dead_rows",
+                 "layout", "layout_pos")
 
     def __init__(self, key_valid, fused_ok, default_pos, make_additive, decode_ok=False, pos_host=None, step_cache=None,
-                 dead_rows=False):
+                 dead_rows=False, layout=None, layout_pos=False):
+        self.layout, self.layout_pos = layout, layout_pos
         self.key_valid, self.fused_ok, self.default_pos = key_valid, fused_ok, default_pos
         self._make, self._additive = make_additive, None
         self.decode_ok, self.pos_host, self.step_cache = decode_ok, pos_host, step_cache
@@ -1209,6 +1222,32 @@ class ApertisModel(nn.Module):
             return None
         return (1.0 - allow.to(inputs_embeds.dtype)) * torch.finfo(inputs_embeds.dtype).min
 
+    def _packed_layout(self, document_ids, input_shape, attention_mask, past_key_values, use_c, pixel_values):
+        """The ops.DocumentLayout of a packed forward, after the checks that keep such a forward well defined: standard_mha
+        (an SSM state would run across documents), no cache in or out, no image tokens in front of the rows, and no key
+        masking - the pad tail of a packed row is a document of its own, so every query keeps a key and attention_mask is
+        None or all ones (one host read, and only when a mask is given).  Every violation raises ValueError."""
+        if self.config.attention_type != "standard_mha":
+            raise ValueError(f"document_ids: packed rows need attention_type 'standard_mha', not "
+                             f"{self.config.attention_type!r} (the recurrent state would run across documents)")
+        if past_key_values is not None or use_c:
+            raise ValueError("document_ids: packed rows take no past_key_values and no use_cache=True")
+        if pixel_values is not None:
+            raise ValueError("document_ids: packed rows take no pixel_values")
+        if tuple(document_ids.shape) != tuple(input_shape):
+            raise ValueError(f"document_ids of shape {tuple(document_ids.shape)} for inputs of {tuple(input_shape)}")
+        if attention_mask is not None and not bool(attention_mask.bool().all()):
+            raise ValueError("document_ids: attention_mask must be None or all ones (give the pad tail a document id of its own)")
+        return ops.document_layout(document_ids)
+
+    @staticmethod
+    def _document_additive_mask(layout, dtype):
+        """The stock branch's additive mask of packed rows [B, 1, L, L]: 0 where start[b, i] <= j <= i, finfo.min elsewhere."""
+        L = layout.start.shape[1]
+        j = torch.arange(L, device=layout.start.device)
+        allow = (j[None, None, :] <= j[None, :, None]) & (j[None, None, :] >= layout.start[:, :, None])
+        return ((1.0 - allow.to(dtype)) * torch.finfo(dtype).min).unsqueeze(1)
+
     def _attention_mask(self, attention_mask, input_shape, inputs_embeds, past_len, default_pos, pos_host=None, step_cache=None):
         """The standard_mha layers' mask (_AttnMask).  One host sync when a mask is given, as before: whether anything is
         padded, whether key 0 of every sequence is valid (then every query row has a valid key: right padding, the
@@ -1241,14 +1280,19 @@ class ApertisModel(nn.Module):
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, pixel_values=None, use_cache=None, output_attentions=None,
-                output_hidden_states=None, return_dict=None):
-        """past_key_values: a prefill's tuple of per-layer pairs (plain tensors in, plain tensors out), or for standard_mha an
+                output_hidden_states=None, return_dict=None, document_ids=None):
+        """document_ids: int64 [B, L], non-decreasing along L - PACKED rows (standard_mha, no cache): a run of equal ids is
+        one document, a token attends within its document only and, with position_ids = None, is positioned within it (the
+        pad tail of a row is a document of its own, so no attention_mask goes with it); _packed_layout has the rules.
+        past_key_values: a prefill's tuple of per-layer pairs (plain tensors in, plain tensors out), or for standard_mha an
         ops.KVCache: a single-token step then appends to it IN PLACE on the decode kernels and hands the same object back
         (position_ids = None: the step's position is the cache's length); a cache with `multi_token` set takes a forward of
         several tokens the same way, on the chunk kernels; a call the kernels do not take runs the stock branch on the
         cache's views and hands back plain tensors."""
         cfg = self.config
         use_c = cfg.use_cache if use_cache is None else use_cache
+        if document_ids is not None:
+            use_c = bool(use_cache)               # (a packed forward keeps no cache: the configuration's default does not apply)
         out_att = cfg.output_attentions if output_attentions is None else output_attentions
         out_hs = cfg.output_hidden_states if output_hidden_states is None else output_hidden_states
         if input_ids is not None and inputs_embeds is not None:
@@ -1270,6 +1314,12 @@ class ApertisModel(nn.Module):
         elif past_key_values is not None and past_key_values[0] is not None and not ssm:
             past_len = past_key_values[0][0].shape[1]
         pos = position_ids
+        layout = None
+        if document_ids is not None:
+            layout = self._packed_layout(document_ids, (B, Lq), attention_mask, past_key_values, use_c, pixel_values)
+            attention_mask = None
+            if pos is None:
+                pos = layout.positions
         if dev_step:
             if cfg.position_embedding_type == "absolute" and self.abs_pos_embeddings is not None:
                 raise ops.ApertisHipError("absolute position embeddings need the step's position on the host: not with a "
@@ -1293,10 +1343,14 @@ class ApertisModel(nn.Module):
             logger.warning("pixel_values provided with past_key_values: image ignored for this step")
         x = self.embed_dropout(x)
         own_pos = position_ids is None and pos_layers is pos
-        mask = None if ssm else self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len, own_pos,
-                                                     past_len if own_pos and kv_cache is not None
-                                                     and (x.shape[1] == 1 or kv_cache.multi_token) else None,
-                                                     kv_cache if dev_step else None)
+        if layout is not None:
+            mask = _AttnMask(None, True, False, lambda: self._document_additive_mask(layout, x.dtype), layout=layout,
+                             layout_pos=own_pos)
+        else:
+            mask = None if ssm else self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len, own_pos,
+                                                         past_len if own_pos and kv_cache is not None
+                                                         and (x.shape[1] == 1 or kv_cache.multi_token) else None,
+                                                         kv_cache if dev_step else None)
 
         all_hs, all_att, all_cache = [], [], []
         lbs, rzs = [], []
@@ -1462,13 +1516,20 @@ class ApertisForCausalLM(nn.Module):
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, pixel_values=None, labels=None, use_cache=None, output_attentions=None,
-                output_hidden_states=None):
+                output_hidden_states=None, document_ids=None):
         """Returns the reference's 7-tuple (loss, logits, hidden_states, attentions,
-        past_key_values, lb_loss, rz_loss)  (core.py:1361-1472)."""
+        past_key_values, lb_loss, rz_loss)  (core.py:1361-1472).
+        document_ids (packed rows, ApertisModel.forward): the label of a document's first token at t >= 1 is ignored, so
+        the shifted loss never asks the last token of one document for the first of the next; the loss stays the mean over
+        the remaining targets."""
         outs = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                           past_key_values=past_key_values, inputs_embeds=inputs_embeds, pixel_values=pixel_values,
                           use_cache=use_cache, output_attentions=output_attentions,
-                          output_hidden_states=output_hidden_states)
+                          output_hidden_states=output_hidden_states, document_ids=document_ids)
+        if document_ids is not None and labels is not None:
+            first = torch.zeros_like(document_ids, dtype=torch.bool)
+            first[:, 1:] = document_ids[:, 1:] != document_ids[:, :-1]
+            labels = labels.masked_fill(first, -100)
         hs = outs[0]
         if self.config.multimodal and pixel_values is not None and past_key_values is None and input_ids is not None:
             start = hs.shape[1] - input_ids.shape[1]                     # text positions are last, core.py:1399-1406
@@ -1537,6 +1598,8 @@ class ApertisForCausalLM(nn.Module):
         again silently."""
         if input_ids is None:
             raise ValueError("input_ids must be provided.")
+        if kwargs.get("document_ids") is not None:
+            raise ValueError("generate(): packed rows (document_ids) are a training form; generate one sequence per row")
         if past_key_values is not None:
             self._generate_cache_check(past_key_values, input_ids, position_ids, pixel_values, max_new_tokens, use_cache,
                                        prefill_chunk)

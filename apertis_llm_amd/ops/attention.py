@@ -1,7 +1,8 @@
 """standard_mha: interleaved-pair RoPE over the full width, causal softmax attention (flash style), and decode against a
 preallocated KV cache (KVCache): single-token steps (kv_append_rope, attention_decode) and multi-token steps
 (kv_append_rope_chunk, attention_chunk); the dead query rows of a left-padded batch (attention_dead_rows).  The vision tower's
-bidirectional attention (full_attention, full_attention_qkv: the same kernels with the diagonal compiled out).
+bidirectional attention (full_attention, full_attention_qkv: the same kernels with the diagonal compiled out).  Packed rows
+(document_layout, document_attention: the causal kernels under a document mask, with the tiles of other documents skipped).
 
 Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autograd bookkeeping only; every computation is a
 HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip, csrc/attention_deadrows.hip).
@@ -24,13 +25,15 @@ ATTN_FUSED = True
 ATTN_LEFT_PAD = os.environ.get("APERTIS_MHA_LEFT_PAD", "0") == "1"
 
 
-def _positions(position_ids, B, L, max_pos):
+def _positions(position_ids, B, L, max_pos, in_range=False):
     """(int64 tensor or None, batch stride).  Explicit positions are range-checked here, on the host: the stock module's
     cos_cached[position_ids] raises IndexError for them, so this does too (one sync; the model passes None for its own
-    arange positions)."""
-    if position_ids is None:
+    arange positions).  in_range: the caller vouches that every position lies in [0, L) (a document layout's positions:
+    ops.document_layout built them), so L against the table is the whole check and nothing is read back."""
+    if position_ids is None or in_range:
         if L > max_pos:
             raise IndexError(f"sequence length {L} exceeds the rotary table ({max_pos} positions)")
+    if position_ids is None:
         return None, 0
     pos = position_ids
     if pos.dim() == 1:
@@ -39,7 +42,7 @@ def _positions(position_ids, B, L, max_pos):
         raise ApertisHipError(f"position_ids of shape {tuple(position_ids.shape)} for q of [{B}, {L}, ...]")
     if pos.dtype != torch.int64 or pos.stride(-1) != 1:
         pos = pos.to(torch.int64).contiguous()
-    if pos.numel():
+    if pos.numel() and not in_range:
         lo, hi = torch.aminmax(pos)
         lo, hi = int(lo), int(hi)
         if lo < -max_pos or hi >= max_pos:            # (negative positions wrap, as torch indexing wraps them)
@@ -78,17 +81,18 @@ class _RopeQK(torch.autograd.Function):
         return dq, dk, None, None, None, None
 
 
-def rope_qk(q, k, position_ids, cos, sin):
+def rope_qk(q, k, position_ids, cos, sin, in_range=False):
     """RotaryEmbedding.forward applied to q and k [B, L, W] in one launch (reference core.py:258-293: interleaved pairs over the
     FULL width).  cos / sin: the module's fp32 cos_cached / sin_cached [max_pos, W/2]; position_ids int64 [1 or B, L] or None
-    (positions 0..L-1).  Bit-identical to the stock module for fp32 and bf16; q and k share a shape and a dtype."""
+    (positions 0..L-1).  Bit-identical to the stock module for fp32 and bf16; q and k share a shape and a dtype.
+    in_range=True: the positions are known to lie in [0, L) (_positions), no host range check."""
     _require_gpu(q, k, position_ids, cos, sin)
     if q.shape != k.shape or q.dtype != k.dtype or q.dim() != 3:
         raise ApertisHipError(f"rope_qk: q {tuple(q.shape)} {q.dtype} and k {tuple(k.shape)} {k.dtype} must match, [B, L, W]")
     B, L, W = q.shape
     if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
         raise ApertisHipError(f"rope_qk: cos/sin must be fp32 [max_pos, {W // 2}]")
-    pos, pos_bs = _positions(position_ids, B, L, cos.shape[0])
+    pos, pos_bs = _positions(position_ids, B, L, cos.shape[0], in_range)
     return _RopeQK.apply(q, k, pos, pos_bs, cos.contiguous(), sin.contiguous())
 
 
@@ -222,6 +226,116 @@ def causal_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=Fal
     if dead_rows and key_valid is not None and B:
         attention_dead_rows(out, v, key_valid)
     return out
+
+
+# --------------------------------------------------------------------------------- packed rows: document-masked attention
+class DocumentLayout:
+    """What document_layout returns: `start` / `end` int32 [B, L] (first token / one past the last token of each token's
+    document, as the kernels read them), `positions` int64 [B, L] (index - start: the position within the document) and
+    `pairs`, a host integer: the number of (query, key) pairs the mask keeps in the whole batch, sum of len*(len+1)/2."""
+    __slots__ = ("start", "end", "positions", "pairs")
+
+    def __init__(self, start, end, positions, pairs):
+        self.start, self.end, self.positions, self.pairs = start, end, positions, pairs
+
+
+def document_layout(document_ids):
+    """The layout of packed rows from `document_ids` [B, L] (integers, non-decreasing along L in every row: a document is a
+    run of equal ids).  Built with torch ops on the ids' device (a running maximum over the run starts and its mirror over
+    the run ends), once per forward; ONE host read brings back the check - ids that decrease raise ValueError - together
+    with the pair count of the launches' work accounting."""
+    ids = document_ids
+    if ids.dim() != 2 or ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise ValueError(f"document_ids must be integers [B, L], got {tuple(ids.shape)} {ids.dtype}")
+    B, L = ids.shape
+    if L >= 2 ** 31:
+        raise ValueError(f"document_ids: rows of {L} tokens do not fit the int32 layout")
+    idx = torch.arange(L, device=ids.device)
+    step = ids[:, 1:] - ids[:, :-1]
+    first = torch.ones(B, L, dtype=torch.bool, device=ids.device)
+    last = torch.ones(B, L, dtype=torch.bool, device=ids.device)
+    first[:, 1:] = step != 0
+    last[:, :-1] = step != 0
+    if L:
+        start = torch.cummax(torch.where(first, idx, 0), dim=1).values
+        end = torch.cummin(torch.where(last, idx + 1, L).flip(1), dim=1).values.flip(1)
+    else:
+        start = end = torch.zeros(B, 0, dtype=torch.int64, device=ids.device)
+    positions = idx - start
+    decreasing, pairs = torch.stack(((step < 0).sum(), (positions + 1).sum())).tolist()
+    if decreasing:
+        raise ValueError("document_ids must not decrease along a row (documents are contiguous runs of equal ids)")
+    return DocumentLayout(start.to(torch.int32).contiguous(), end.to(torch.int32).contiguous(), positions, int(pairs))
+
+
+class _DocumentAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, heads, key_valid, start, end, pairs, p, seed):
+        lib = _lib.load()
+        B, L, W = q.shape
+        D = W // heads
+        q, q_rs = _rows(q, W)
+        k, k_rs = _rows(k, W)
+        v, v_rs = _rows(v, W)
+        out = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
+        lse = torch.empty(B, heads, L, device=q.device, dtype=torch.float32)
+        _launch("apertis_attention_doc_fwd", lib.apertis_attention_doc_fwd,
+                (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(key_valid), ptr(start), ptr(end), ptr(out), W, ptr(lse), B, L,
+                 heads, D, p, seed, dtype_code(q), stream_ptr()), work=4.0 * heads * D * pairs)
+        ctx.save_for_backward(q, k, v, out, lse, key_valid, start, end)
+        ctx.cfg = (heads, pairs, p, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        q, k, v, out, lse, key_valid, start, end = ctx.saved_tensors
+        heads, pairs, p, seed = ctx.cfg
+        B, L, W = q.shape
+        D = W // heads
+        dout = dout.to(q.dtype)
+        dout, do_rs = _rows(dout, W)
+        if dout.data_ptr() % 16:
+            dout = dout.clone()
+        ws = torch.empty(lib.apertis_attention_bwd_workspace_bytes(B, L, heads) // 4, device=q.device, dtype=torch.float32)
+        dq = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
+        dk = torch.empty_like(dq)
+        dv = torch.empty_like(dq)
+        _launch("apertis_attention_doc_bwd", lib.apertis_attention_doc_bwd,
+                (ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(v), v.stride(-2), ptr(out), W, ptr(dout), do_rs, ptr(lse),
+                 ptr(key_valid), ptr(start), ptr(end), ptr(ws), ptr(dq), ptr(dk), ptr(dv), W, B, L, heads, D, p, seed,
+                 dtype_code(q), stream_ptr()), work=2.5 * 4.0 * heads * D * pairs)
+        return dq, dk, dv, None, None, None, None, None, None, None
+
+
+def document_attention(q, k, v, heads, layout, key_valid=None, dropout_p=0.0, training=False):
+    """causal_attention on PACKED rows: query i of row b attends key j iff layout.start[b, i] <= j <= i (and key_valid),
+    so the documents of a row - contiguous runs, document_layout - do not see each other.  The layout contract, the dropout
+    hash and seed, the saved tensors and the determinism of the backward are causal_attention's; with one document per row
+    every output and gradient has causal_attention's bits.  The kernels skip the key tiles in front of a wave's earliest
+    document and the query tiles past a wave's latest document end: the work is the documents' triangles
+    (4*heads*D*layout.pairs flops forward), not the row's."""
+    _require_gpu(q, k, v, key_valid)
+    if not (q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype) or not attention_supported(q, heads):
+        raise ApertisHipError(f"document_attention: q/k/v {tuple(q.shape)} {q.dtype} with {heads} heads (D 64 or 128, fp32 or "
+                              "bf16, one shape and dtype)")
+    B, L, _ = q.shape
+    if not isinstance(layout, DocumentLayout):
+        raise ApertisHipError("document_attention: layout is what ops.document_layout returns")
+    for t in (layout.start, layout.end):
+        if tuple(t.shape) != (B, L) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != q.device:
+            raise ApertisHipError(f"document_attention: layout of {tuple(t.shape)} {t.dtype} on {t.device} for q of [{B}, {L}, ...] "
+                                  f"on {q.device}")
+    if key_valid is not None:
+        if tuple(key_valid.shape) != (B, L):
+            raise ApertisHipError(f"document_attention: key_valid {tuple(key_valid.shape)}, expected ({B}, {L})")
+        if key_valid.dtype != torch.int64 or not key_valid.is_contiguous():
+            key_valid = key_valid.to(torch.int64).contiguous()
+    p = float(dropout_p) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ApertisHipError(f"document_attention: dropout_p {dropout_p} outside [0, 1)")
+    seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0
+    return _DocumentAttention.apply(q, k, v, int(heads), key_valid, layout.start, layout.end, layout.pairs, p, seed)
 
 
 # ------------------------------------------------------------------------------------------- bidirectional attention

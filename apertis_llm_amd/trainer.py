@@ -17,6 +17,8 @@ checkpoint layout, so that a reference training configuration runs unchanged and
     the epoch when `dynamic_batch_sizing`.
 Deviations: autocast is bf16 without a GradScaler (`fp16=True` selects it); data parallelism is
 `BucketedDataParallel` (RCCL, one reduction per optimizer step) instead of DDP; wandb logging is not wired.
+`pack_sequences=True` (keyword-only, `training_config.pack_sequences`; not in the reference, off by default) wraps the
+datasets in `data.PackedDataset`: a standard_mha model then trains on rows without pad tokens.
 `history` records what the reference only logs (loss per optimizer step, learning rates, validation losses,
 checkpoint names) - it is what tests/ compare with the reference run captured in tests/golden/trainer_run.npz.
 """
@@ -34,7 +36,7 @@ from torch.utils.data import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
 from . import ops
-from .data import ApertisFineTuneDataset, ApertisPretrainDataset, load_vocabulary
+from .data import ApertisFineTuneDataset, ApertisPretrainDataset, PackedDataset, load_vocabulary
 from .model import ApertisConfig, ApertisForCausalLM, create_apertis_model
 from .parallel import BucketedDataParallel
 from .training import build_optimizer, build_train_prep, clip_and_step, prepared_step
@@ -53,7 +55,8 @@ class ApertisTrainer:
                  gpu_ids: Optional[List[int]] = None, distributed_training: bool = False, local_rank: int = -1,
                  stop_event: Optional[threading.Event] = None, is_fine_tuning: bool = False,
                  original_tokenizer_path_for_ft_hf: Optional[str] = None,
-                 original_manual_vocab_path_for_ft: Optional[str] = None, *, shuffle: bool = True, num_workers: int = 4):
+                 original_manual_vocab_path_for_ft: Optional[str] = None, *, shuffle: bool = True, num_workers: int = 4,
+                 pack_sequences: bool = False):
         self.model, self.train_dataset, self.val_dataset = model, train_dataset, val_dataset
         self.output_dir, self.batch_size, self.learning_rate = output_dir, batch_size, learning_rate
         self.weight_decay, self.num_epochs, self.warmup_steps = weight_decay, num_epochs, warmup_steps
@@ -68,6 +71,13 @@ class ApertisTrainer:
         self.original_manual_vocab_path_for_ft = original_manual_vocab_path_for_ft
         self.use_gradient_checkpointing = use_gradient_checkpointing
         self._shuffle, self._num_workers = shuffle, num_workers
+        self.pack_sequences = pack_sequences
+        if pack_sequences:
+            # several items per row (data.PackedDataset): no pad tokens through the model, attention within each document
+            if getattr(getattr(model, "config", None), "attention_type", None) != "standard_mha":
+                raise ValueError("pack_sequences=True needs a standard_mha model (packed rows carry document_ids)")
+            self.train_dataset = self._packed(train_dataset)
+            self.val_dataset = self._packed(val_dataset) if val_dataset else val_dataset
         if use_wandb:
             logger.warning("wandb logging is not wired in this trainer; metrics are kept in trainer.history")
         os.makedirs(output_dir, exist_ok=True)
@@ -116,6 +126,16 @@ class ApertisTrainer:
         self.history: Dict[str, list] = {"loss": [], "lr": [], "val_loss": [], "checkpoints": []}
 
     # --------------------------------------------------------------------------------------------------------
+    def _packed(self, dataset):
+        """`dataset` wrapped for pack_sequences: rows of the dataset's own max_length, filled with its own pad id."""
+        max_length = getattr(dataset, "max_length", None)
+        if max_length is None:
+            max_length = dataset[0]["input_ids"].shape[0]
+        pad = getattr(dataset, "pad_token_id", getattr(dataset, "pad_token_id_for_data", None))
+        if pad is None:
+            pad = self.model.config.pad_token_id
+        return PackedDataset(dataset, max_length, pad)
+
     def _create_dataloaders(self):
         pin = self.device.type == "cuda"
         sampler = (DistributedSampler(self.train_dataset, num_replicas=self.world_size, rank=self.local_rank, shuffle=True)
@@ -250,8 +270,9 @@ class ApertisTrainer:
         torch.save(self.model.state_dict(), os.path.join(ckpt, "pytorch_model.bin"))
         if hasattr(self.model, "config") and hasattr(self.model.config, "save_pretrained"):
             self.model.config.save_pretrained(ckpt)
-        tok = getattr(self.train_dataset, "tokenizer", None)
-        if self.is_fine_tuning and getattr(self.train_dataset, "is_hf_tokenizer", False) and hasattr(tok, "save_pretrained"):
+        source = self.train_dataset.dataset if isinstance(self.train_dataset, PackedDataset) else self.train_dataset
+        tok = getattr(source, "tokenizer", None)
+        if self.is_fine_tuning and getattr(source, "is_hf_tokenizer", False) and hasattr(tok, "save_pretrained"):
             tok.save_pretrained(ckpt)
         elif self.original_manual_vocab_path_for_ft and os.path.exists(self.original_manual_vocab_path_for_ft):
             shutil.copy(self.original_manual_vocab_path_for_ft, os.path.join(ckpt, "vocab.json"))
@@ -365,7 +386,8 @@ def build_from_config(config: Dict[str, Any], stop_event: Optional[threading.Eve
         g("use_gradient_checkpointing", True), g("eval_every_n_epochs", 1), g("dynamic_batch_sizing", True), g("gpu_ids"),
         g("distributed_training", False), g("local_rank", -1), stop_event=stop_event, is_fine_tuning=finetune,
         original_tokenizer_path_for_ft_hf=tok_path if (finetune and hf_tok is not None) else None,
-        original_manual_vocab_path_for_ft=tok_path if vocab is not None else None, **trainer_kwargs)
+        original_manual_vocab_path_for_ft=tok_path if vocab is not None else None,
+        **{"pack_sequences": g("pack_sequences", False), **trainer_kwargs})
 
 
 def train_from_config(config_path: str, stop_event: Optional[threading.Event] = None):

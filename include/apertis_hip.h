@@ -57,7 +57,8 @@ extern "C" {
  * without a bump: the test suite pins the version at 4.12 and no existing signature changed, so a binding written against the
  * earlier 4.12 header still calls every entry point it knows correctly; one that wants the RMSNorm family looks the symbols up.
  * The SwiGLU entry points (apertis_swiglu_fwd / _bwd) joined them the same way, for the same reason: still 4.12.
- * So did the bidirectional attention pair of the vision tower (apertis_attention_full_fwd / _bwd): still 4.12. */
+ * So did the bidirectional attention pair of the vision tower (apertis_attention_full_fwd / _bwd): still 4.12.
+ * So did the document-masked causal pair of packed rows (apertis_attention_doc_fwd / _bwd): still 4.12, 117 entry points. */
 #define APERTIS_ABI_VERSION ((4 << 16) | 12)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
@@ -812,6 +813,28 @@ int apertis_attention_full_bwd(const void *q, int64_t q_rs, const void *k, int64
                                const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
                                const int64_t *key_valid, float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B,
                                int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
+
+/* The causal pair under a DOCUMENT mask (packed rows: several independent sequences, contiguous, in one row of L tokens):
+ *   O[b,i,h] = sum_{doc_start[b,i] <= j <= i, key_valid[b,j] != 0} drop(P[i,j]) V[b,j,h],  P = softmax over those j.
+ *   doc_start     : int32 [B,L], index of the first token of the document token i belongs to (doc_start[b,i] <= i)
+ *   doc_end       : int32 [B,L], one past the last token of that document (doc_end[b,j] > j); the mask as a key sees it is
+ *                   j <= i < doc_end[b,j].  Both describe the same partition of the row into runs; NULL: APERTIS_ERR_ARG
+ * Every other argument, layout, limit (D 64 / 128, fp32 / bf16, B*H <= 65535, 16-byte rows), check before any launch, the
+ * dropout hash (indices as in apertis_attention_fwd: row (b*H+h)*L + i, key j, L columns), the workspace
+ * (apertis_attention_bwd_workspace_bytes) and the determinism of the backward are those of apertis_attention_fwd / _bwd; the
+ * kernels are the same templates with one more predicate.  Key tiles in front of the earliest document of a wave's 16
+ * queries, and query tiles past the latest document end of a wave's 16 keys, are never touched: the work is the documents'
+ * triangles, not the row's.  With one document per row (doc_start = 0, doc_end = L) every output has the bits of
+ * apertis_attention_fwd / _bwd.  Values outside [0, L] in either array only mask: no address is formed from them. */
+int apertis_attention_doc_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                              const int64_t *key_valid, const int32_t *doc_start, const int32_t *doc_end, void *out,
+                              int64_t out_rs, float *lse, int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p,
+                              uint64_t seed, int dtype, void *stream);
+int apertis_attention_doc_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                              const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
+                              const int64_t *key_valid, const int32_t *doc_start, const int32_t *doc_end, float *workspace,
+                              void *dq, void *dk, void *dv, int64_t d_rs, int64_t B, int64_t L, int64_t H, int64_t D,
+                              float dropout_p, uint64_t seed, int dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * standard_mha single-token decode against a preallocated KV cache (the attention of core.py:639-700 with a past):
