@@ -455,6 +455,74 @@ dwconv_silu_fwd_kn(const T *__restrict__ x, int64_t x_rs, const float *__restric
   }
 }
 
+// ---- the forward of LEFT-PADDED rows (generate()'s prefill under ops.ssm.SSM_LEFT_PAD): batch row b's sequence begins at token
+// start[b].  A tap that falls before it reads as zero - what t - j < 0 is to the kernels above - and the output rows before it
+// are exact zeros, so that x_param_proj (no bias) hands the scan Bt = C = dt_in = 0 there and the state stays at 0 up to the
+// first real token.  One form for every width 2..16 and every Dn % 4 == 0: a work-group takes (batch, 64 tokens, CB <= 64
+// 4-channel chunks).  The tile's pad rows are a PREFIX, [0, first): they are zero-filled by all threads and never loaded or
+// convolved - `first` is uniform over the work-group, no lane tests a row - and a tile that is all pad ends there.  The other
+// rows and the k - 1 before them come into LDS as fp32 (rows before start[b]: zeros, not loaded) next to the taps, transposed
+// to [k][CB] so that one 16-byte read brings tap q of a thread's four channels; thread (rg, p) owns chunk p of rows first + rg,
+// first + rg + RG, ...  Each output is bias + sum_q w[q] * x[t - (k-1) + q], q ascending, rounded to the io dtype before SiLU:
+// the sum of the kernels above term for term, so a row's outputs from start[b] on carry the bits those kernels give the row
+// alone.  This runs once per generate() and layer; the taps cost an LDS read per term instead of k registers per channel.
+template <typename T>
+__global__ void __launch_bounds__(256)
+dwconv_silu_start_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
+                    const int32_t *__restrict__ start, T *__restrict__ out, int64_t out_rs, int64_t L, int CPR, int k, int CB,
+                    int nchunks, int ncb) {
+  constexpr int TT = CONV_TILE_T;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float4 *tile = reinterpret_cast<float4 *>(smem);   // [TT + k - 1][CB]
+  float4 *taps = tile + (TT + k - 1) * CB;           // [k][CB]
+  const int tid = threadIdx.x;
+  const int cb = (int)(blockIdx.x % ncb);
+  const int64_t bt = blockIdx.x / ncb, b = bt / nchunks;
+  const int64_t t0 = (bt - b * nchunks) * TT;
+  const int rows = (int)min((int64_t)TT, L - t0);
+  const int c_lo = cb * CB, nc = min(CB, CPR - c_lo);
+  const int64_t s = min(max((int64_t)start[b], (int64_t)0), L);
+  const int first = (int)min(max(s - t0, (int64_t)0), (int64_t)rows);
+  const T *xb = x + b * L * x_rs + c_lo * 4;
+  T *ob = out + (b * L + t0) * out_rs + c_lo * 4;
+  for (int i = tid; i < first * nc; i += 256) {
+    const int r = i / nc, c = i - r * nc;
+    st4<T>(ob + (int64_t)r * out_rs + c * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+  }
+  if (first == rows) return;
+  const int nrow = rows - first + k - 1;             // tile row j = token t0 + first - (k - 1) + j
+  const int64_t tf = t0 + first - (k - 1);
+  for (int i = tid; i < nrow * nc; i += 256) {
+    const int r = i / nc, c = i - r * nc;
+    const int64_t t = tf + r;
+    tile[r * CB + c] = t >= s ? ld4<T>(xb + t * x_rs + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  for (int i = tid; i < k * nc; i += 256) {
+    const int q = i / nc, c = i - q * nc;
+    const float *wc = w + (int64_t)(c_lo + c) * 4 * k + q;
+    taps[q * CB + c] = make_float4(wc[0], wc[k], wc[2 * k], wc[3 * k]);
+  }
+  __syncthreads();
+  const int rg = tid / CB, p = tid - rg * CB, RG = 256 / CB;
+  if (rg >= RG || p >= nc) return;
+  const float *bp = bias + (c_lo + p) * 4;
+  const float4 bv = make_float4(bp[0], bp[1], bp[2], bp[3]);
+  for (int r = rg; r < rows - first; r += RG) {
+    float acc[4] = {bv.x, bv.y, bv.z, bv.w};
+    for (int q = 0; q < k; ++q) {
+      const float4 f = tile[(r + q) * CB + p], wq = taps[q * CB + p];
+      acc[0] += wq.x * f.x; acc[1] += wq.y * f.y; acc[2] += wq.z * f.z; acc[3] += wq.w * f.w;
+    }
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float sj = to_f32(from_f32<T>(acc[j]));  // conv output is stored in the activation dtype before SiLU
+      o[j] = siluf_(sj);
+    }
+    st4<T>(ob + (int64_t)(first + r) * out_rs + p * 4, make_float4(o[0], o[1], o[2], o[3]));
+  }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 dwconv_silu_bwd_kn(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
@@ -855,6 +923,24 @@ extern "C" int apertis_dwconv_silu_fwd(const void *x, int64_t x_rs, const float 
   }
   CONV_DISPATCH(k, dtype_io, hipLaunchKernelGGL((dwconv_silu_fwd_k<T, KW>), grid, block, 0, st, (const T *)x, x_rs, w, bias,
                                                 (T *)out, out_rs, B, L, (int)Dn));
+  return apertis_check_launch();
+}
+
+extern "C" int apertis_dwconv_silu_start_fwd(const void *x, int64_t x_rs, const float *w, const float *bias, const int32_t *start,
+                                             void *out, int64_t out_rs, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
+                                             void *stream) {
+  if (!x || !w || !bias || !start || !out || B < 0 || L < 0) return APERTIS_ERR_ARG;
+  if (dtype_io != APERTIS_F32 && dtype_io != APERTIS_BF16) return APERTIS_ERR_ARG;
+  if (!rows_ok(Dn) || (x_rs | out_rs) % 4 || x_rs < Dn || out_rs < Dn || k < 2 || k > CONV_KMAX) return APERTIS_ERR_UNSUPPORTED;
+  const uintptr_t piece = dtype_io == APERTIS_BF16 ? 8 : 16;        // a thread moves four channels at a time
+  if ((uintptr_t)x % piece || (uintptr_t)out % piece) return APERTIS_ERR_UNSUPPORTED;
+  if (B == 0 || L == 0) return APERTIS_OK;
+  const int CPR = (int)(Dn / 4), CB = std::min(CPR, 64);
+  const int64_t nchunks = ceil_div64(L, CONV_TILE_T), ncb = ceil_div64(CPR, CB);
+  if (nchunks >= 0x7fffffffLL || B * nchunks * ncb >= 0x7fffffffLL) return APERTIS_ERR_UNSUPPORTED;
+  const size_t lds = (size_t)(CONV_TILE_T + 2 * k - 1) * CB * sizeof(float4);   // tile + taps: at most 95 rows of 1 KiB
+  CONV_TYPES(dtype_io, launch_lds(dwconv_silu_start_k<T>, dim3((unsigned)(B * nchunks * ncb)), dim3(256), lds, (hipStream_t)stream,
+                                  (const T *)x, x_rs, w, bias, start, (T *)out, out_rs, L, CPR, (int)k, CB, (int)nchunks, (int)ncb));
   return apertis_check_launch();
 }
 

@@ -340,6 +340,15 @@ class RotaryEmbedding(nn.Module):
 # ----------------------------------------------------------------------------------------------
 # SelectiveLinearAttention  (reference core.py:295-401) on HIP kernels
 # ----------------------------------------------------------------------------------------------
+class _SsmStarts:
+    """What ApertisModel.forward hands the SSM layers in the mask slot (None otherwise) for a left-padded prefill under
+    ops.SSM_LEFT_PAD: `start` int32 [B], the first valid token of every row (ops.left_pad_starts)."""
+    __slots__ = ("start",)
+
+    def __init__(self, start):
+        self.start = start
+
+
 class SelectiveLinearAttention(nn.Module):
     """in_proj_x/z -> depthwise causal conv + SiLU -> x_param_proj -> (dt feats, Bt, C) ->
     softplus(dt_proj_head) -> selective scan -> +D*x -> *SiLU(z) -> out_proj.
@@ -492,7 +501,12 @@ class SelectiveLinearAttention(nn.Module):
             # (core.py:369-373); reproduced as is so cached decode matches `apertis chat`
             conv_in = torch.cat([conv_prev.transpose(1, 2).to(xp.dtype), xp], dim=1)
         conv_state = conv_in[:, -(kw - 1):].transpose(1, 2).detach() if use_cache else None
-        if hidden_states.is_cuda and ops.DWCONV_PAIR:
+        if isinstance(attention_mask, _SsmStarts):
+            # left-padded prefill under ops.SSM_LEFT_PAD (ApertisModel._ssm_left_pad has the conditions: inference, no incoming
+            # cache): a row's pads count as "before the sequence" - the conv output is exactly 0 there, x_param_proj has no
+            # bias, so Bt = C = dt_in = 0 and the state every scan form carries stays at 0 up to the first real token
+            xc_p = xc = ops.dwconv_silu(conv_in, self.conv1d.weight, self.conv1d.bias, start=attention_mask.start)
+        elif hidden_states.is_cuda and ops.DWCONV_PAIR:
             # (two views of the one conv output, one per consumer - x_param_proj and the scan: the conv backward adds their
             #  gradients where it reads the rows)
             xc_p, xc = ops.dwconv_silu_pair(conv_in, self.conv1d.weight, self.conv1d.bias)  # core.py:373-375
@@ -1277,6 +1291,29 @@ class ApertisModel(nn.Module):
                          lambda: self._prepare_decoder_attention_mask(attention_mask, input_shape, inputs_embeds, past_len),
                          ok, pos_host, dead_rows=dead_rows)
 
+    def _ssm_left_pad(self, attention_mask, x, past_key_values, pixel_values, output_att):
+        """The SSM layers' mask slot: None - they read no mask, as in the reference, so the pads of a left-padded row run
+        through conv and scan - or, with ops.SSM_LEFT_PAD, a _SsmStarts for a LEFT-PADDED PREFILL, which then gives every row
+        what it gets alone (SelectiveLinearAttention.forward).  Only for: inference (eval, no autograd) on the GPU, a
+        selective_ssm model, no incoming past_key_values, no image prefix (the conv would have to reach over the pads between
+        image and text), no absolute position embeddings (a row alone would be positioned from 0), no output_attentions; a
+        mask [B, L] whose rows are all 0...0 1...1 (ops.left_pad_starts) with at least ssm_conv_kernel - 1 valid tokens each,
+        so that the cached conv window holds real inputs only, and with a pad somewhere.  Anything else: None, today's path.
+        Two host reads, per prefill."""
+        cfg = self.config
+        if not (ops.SSM_LEFT_PAD and attention_mask is not None and x.is_cuda and not self.training
+                and not torch.is_grad_enabled() and cfg.attention_type == "selective_ssm" and past_key_values is None
+                and pixel_values is None and cfg.position_embedding_type != "absolute" and not output_att
+                and tuple(attention_mask.shape) == tuple(x.shape[:2])):
+            return None
+        start = ops.left_pad_starts(attention_mask)
+        if start is None:
+            return None
+        longest_pad = int(start.max())
+        if longest_pad == 0 or x.shape[1] - longest_pad < cfg.ssm_conv_kernel - 1:
+            return None
+        return _SsmStarts(start.to(x.device))
+
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, pixel_values=None, use_cache=None, output_attentions=None,
@@ -1346,11 +1383,14 @@ class ApertisModel(nn.Module):
         if layout is not None:
             mask = _AttnMask(None, True, False, lambda: self._document_additive_mask(layout, x.dtype), layout=layout,
                              layout_pos=own_pos)
+        elif ssm:
+            # (the SSM layers read no mask, as in the reference - under ops.SSM_LEFT_PAD the starts of a left-padded prefill)
+            mask = self._ssm_left_pad(attention_mask, x, past_key_values, pixel_values, out_att)
         else:
-            mask = None if ssm else self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len, own_pos,
-                                                         past_len if own_pos and kv_cache is not None
-                                                         and (x.shape[1] == 1 or kv_cache.multi_token) else None,
-                                                         kv_cache if dev_step else None)
+            mask = self._attention_mask(attention_mask, (B, x.shape[1]), x, past_len, own_pos,
+                                        past_len if own_pos and kv_cache is not None
+                                        and (x.shape[1] == 1 or kv_cache.multi_token) else None,
+                                        kv_cache if dev_step else None)
 
         all_hs, all_att, all_cache = [], [], []
         lbs, rzs = [], []

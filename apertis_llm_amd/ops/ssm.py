@@ -82,9 +82,53 @@ class _DwConvSiluPair(_DwConvSilu):
         return out, out.view_as(out)
 
 
-def dwconv_silu(x, weight, bias):
+# APERTIS_SSM_LEFT_PAD=1: a left-padded prefill of a selective_ssm model (eval, no autograd) gives every row what it gets alone -
+# the conv treats a row's pad prefix as "before the sequence" (dwconv_silu(start=...)), which keeps the scan's state at exactly
+# 0 up to the first real token.  Off by default: the reference runs the pads through conv and scan.
+SSM_LEFT_PAD = _os.environ.get("APERTIS_SSM_LEFT_PAD", "0") == "1"
+
+
+def left_pad_starts(attention_mask):
+    """First valid token of every row of a LEFT-PADDED mask [B, L] (each row 0...0 1...1 with at least one 1) as int32 [B] on
+    the mask's device, or None for any other mask (a hole, right padding, an empty row, not 2-D).  One host read per call."""
+    m = attention_mask
+    if m is None or m.dim() != 2 or m.shape[1] == 0:
+        return None
+    valid = m != 0
+    L = m.shape[1]
+    n = valid.sum(1)
+    # 0...0 1...1: the last token is valid and the valid tokens are the last n, i.e. nothing changes 1 -> 0 along the row
+    ok = (n > 0) & ~(valid[:, :-1] & ~valid[:, 1:]).any(1)
+    if not bool(ok.all()):
+        return None
+    return (L - n).to(torch.int32)
+
+
+def _dwconv_silu_start(x, w, b, start):
+    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad):
+        raise ApertisHipError("dwconv_silu(start=...) is forward only (a left-padded inference prefill): not under autograd")
+    _require_gpu(x, w, b, start)
+    lib = _lib.load()
+    B, L, Dn = x.shape
+    if start.dtype != torch.int32 or tuple(start.shape) != (B,):
+        raise ApertisHipError(f"start must be int32 [{B}], got {start.dtype} {tuple(start.shape)}")
+    x, x_rs = _rows(x, Dn)
+    w2 = _f32(w).reshape(Dn, -1)
+    b2 = _f32(b)
+    start = start.contiguous()
+    out = torch.empty(B, L, Dn, device=x.device, dtype=x.dtype)
+    check(lib.apertis_dwconv_silu_start_fwd(ptr(x), x_rs, ptr(w2), ptr(b2), ptr(start), ptr(out), Dn, B, L, Dn, w2.shape[1],
+                                            dtype_code(x), stream_ptr()), "apertis_dwconv_silu_start_fwd")
+    return out
+
+
+def dwconv_silu(x, weight, bias, start=None):
     """silu(causal depthwise conv1d(x)) on token-major x [B,L,Dn] (reference core.py:368-375).
-    weight [Dn,1,k] (nn.Conv1d layout), bias [Dn]."""
+    weight [Dn,1,k] (nn.Conv1d layout), bias [Dn].
+    start (int32 [B], left_pad_starts): row b's sequence begins at token start[b] - taps before it read as zero and the
+    outputs before it are exact zeros; forward only."""
+    if start is not None:
+        return _dwconv_silu_start(x, weight, bias, start)
     return _DwConvSilu.apply(x, weight, bias)
 
 

@@ -58,7 +58,8 @@ extern "C" {
  * earlier 4.12 header still calls every entry point it knows correctly; one that wants the RMSNorm family looks the symbols up.
  * The SwiGLU entry points (apertis_swiglu_fwd / _bwd) joined them the same way, for the same reason: still 4.12.
  * So did the bidirectional attention pair of the vision tower (apertis_attention_full_fwd / _bwd): still 4.12.
- * So did the document-masked causal pair of packed rows (apertis_attention_doc_fwd / _bwd): still 4.12, 117 entry points. */
+ * So did the document-masked causal pair of packed rows (apertis_attention_doc_fwd / _bwd): still 4.12, 117 entry points.
+ * So did the left-padded form of the conv forward (apertis_dwconv_silu_start_fwd): still 4.12, 118 entry points. */
 #define APERTIS_ABI_VERSION ((4 << 16) | 12)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
@@ -293,9 +294,18 @@ int apertis_dwconv_silu_bwd2(const void *x, int64_t x_rs, const float *w, const 
                              void *dx, int64_t dx_rs, float *dw_part, float *db_part, float *dw,
                              float *db, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
                              void *stream);
+/* apertis_dwconv_silu_fwd for LEFT-PADDED rows (inference prefill; forward only): batch row b's sequence begins at token
+ * start[b] (int32 [B] on the device, clamped to [0, L]).  A tap at token t - j < start[b] reads as 0, as t - j < 0 does in
+ * the plain forward, and output rows t < start[b] are written as exact zeros - whole pad rows are neither loaded nor
+ * convolved.  out[b, start[b]:] carries the bits the plain forward gives x[b, start[b]:] as a sequence of its own; with every
+ * start 0 it is the plain forward's output.  Same layouts, dtypes and widths (2 <= k <= 16, else APERTIS_ERR_UNSUPPORTED);
+ * x and out at addresses that are multiples of four elements. */
+int apertis_dwconv_silu_start_fwd(const void *x, int64_t x_rs, const float *w, const float *bias,
+                                  const int32_t *start /* [B] */, void *out, int64_t out_rs, int64_t B,
+                                  int64_t L, int64_t Dn, int64_t k, int dtype_io, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * MoE router gating  (replaces AdaptiveExpertSystem.forward core.py:491-492,529)
+ * MoE router gating (replaces AdaptiveExpertSystem.forward core.py:491-492,529)
  *   g = softmax(logits)              logits [S,E] fp32 (already noised if training)
  *   (p, idx) = topk(g, K) descending, ties -> lowest expert index first
  *   w = p / (sum(p) + 1e-6)
