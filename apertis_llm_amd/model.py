@@ -823,6 +823,10 @@ class ApertisAttention(nn.Module):
             return False
         return att_mask.fused_ok and (kv is None or tuple(kv.shape) == tuple(q.shape[:2]))
 
+    def _rope_tables(self):
+        """(cos, sin) of this layer's rotary table; (None, None) without rope."""
+        return (self.rope.cos_cached, self.rope.sin_cached) if self.rope is not None else (None, None)
+
     def _fused_attention(self, q, k, v, att_mask, pos_ids, use_c):
         key_valid, default_pos = (att_mask.key_valid, att_mask.default_pos) if att_mask is not None else (None, False)
         dead_rows = att_mask is not None and att_mask.dead_rows
@@ -830,16 +834,24 @@ class ApertisAttention(nn.Module):
         if self.rope is not None:
             # (the model's own positions 0..L-1 go in as None: explicit ones are range-checked on the host, a sync per call;
             #  a layout's positions lie in [0, L) by construction: L against the table is the whole check)
-            q, k = ops.rope_qk(q, k, None if default_pos else pos_ids, self.rope.cos_cached, self.rope.sin_cached,
+            q, k = ops.rope_qk(q, k, None if default_pos else pos_ids, *self._rope_tables(),
                                in_range=layout is not None and att_mask.layout_pos)
-        cache = (k, v) if use_c else None
+        heads, p = self.num_attention_heads, self.attention_dropout.p
         if layout is not None:
-            ctxv = ops.document_attention(q, k, v, self.num_attention_heads, layout, key_valid, self.attention_dropout.p,
-                                          self.training)
-            return self.out_proj(ctxv), cache
-        ctxv = ops.causal_attention(q, k, v, self.num_attention_heads, key_valid, self.attention_dropout.p, self.training,
-                                    dead_rows=dead_rows)
-        return self.out_proj(ctxv), cache
+            ctxv = ops.document_attention(q, k, v, heads, layout, key_valid, p, self.training)
+        else:
+            ctxv = ops.causal_attention(q, k, v, heads, key_valid, p, self.training, dead_rows=dead_rows)
+        return self.out_proj(ctxv), ((k, v) if use_c else None)
+
+    def _cache_step_ok(self, q, att_mask, past_kv, output_att, use_c):
+        """What _decode_ok and _chunk_ok share: the past is a layer of an ops.KVCache in the projections' dtype and batch, both
+        switches on, on the GPU, inference (use_cache, no attention weights, eval, no grad), the model's own mask saying that
+        every row has a valid key (_AttnMask.decode_ok), fp32 or bf16 with D 64 or 128."""
+        return (isinstance(past_kv, ops.KVLayer) and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and q.is_cuda and use_c
+                and not output_att and not self.training and not torch.is_grad_enabled()
+                and isinstance(att_mask, _AttnMask) and att_mask.decode_ok
+                and ops.attention_decode_supported(q, self.num_attention_heads)
+                and q.dtype == past_kv.cache.dtype and q.shape[0] == past_kv.cache.k[0].shape[0])
 
     def _decode_ok(self, q, att_mask, past_kv, output_att, use_c):
         """Whether this call is a single-token step the KV-cache decode kernels take: the past is a layer of an ops.KVCache
@@ -853,14 +865,10 @@ class ApertisAttention(nn.Module):
         rotary table is the kernel's check (ops.kv_append_rope_at).  Its host lengths are stale, so a call the kernels do not
         take cannot fall back on the views: it raises."""
         step = isinstance(past_kv, ops.KVLayer) and past_kv.cache.step_active
-        ok = (isinstance(past_kv, ops.KVLayer) and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and q.is_cuda
-              and q.shape[1] == 1 and use_c and not output_att and not self.training and not torch.is_grad_enabled()
-              and isinstance(att_mask, _AttnMask) and att_mask.decode_ok
-              and (att_mask.step_cache is past_kv.cache if step else att_mask.pos_host is not None)
-              and ops.attention_decode_supported(q, self.num_attention_heads))
+        ok = (self._cache_step_ok(q, att_mask, past_kv, output_att, use_c) and q.shape[1] == 1
+              and (att_mask.step_cache is past_kv.cache if step else att_mask.pos_host is not None))
         if step:
-            cache = past_kv.cache
-            if not (ok and q.dtype == cache.dtype and q.shape[0] == cache.k[0].shape[0]):
+            if not ok:
                 raise ops.ApertisHipError("a KVCache whose device step state is active takes single-token inference steps on the "
                                           "decode kernels only (its host lengths are stale): KVCache.step_state_end() first")
             return True
@@ -868,12 +876,11 @@ class ApertisAttention(nn.Module):
             return False
         cache, kv = past_kv.cache, att_mask.key_valid
         n = cache.lengths[past_kv.layer]
-        return (q.dtype == cache.dtype and n < cache.capacity and q.shape[0] == cache.k[0].shape[0]
-                and (kv is None or tuple(kv.shape) == (q.shape[0], n + 1)))
+        return n < cache.capacity and (kv is None or tuple(kv.shape) == (q.shape[0], n + 1))
 
     def _decode_attention(self, q, k, v, att_mask, past_kv):
         cache, layer = past_kv.cache, past_kv.layer
-        cos, sin = (self.rope.cos_cached, self.rope.sin_cached) if self.rope is not None else (None, None)
+        cos, sin = self._rope_tables()
         if cache.step_active:
             q = ops.kv_append_rope_at(q, k, v, cache, layer, cos, sin)
             ctxv = ops.attention_decode_at(q, cache, layer, self.num_attention_heads)
@@ -890,20 +897,17 @@ class ApertisAttention(nn.Module):
         every sequence valid, so that every row has a valid key, or with ops.ATTN_LEFT_PAD the rows without one filled in
         afterwards (`att_mask.dead_rows`); the mask None or [B, n + Lq].  Anything else runs the stock
         branch on the cache's views, as every multi-token forward against a cache without the flag does."""
-        if not (isinstance(past_kv, ops.KVLayer) and past_kv.cache.multi_token and not past_kv.cache.step_active
-                and ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED and q.is_cuda and q.shape[1] > 1 and use_c and not output_att
-                and not self.training and not torch.is_grad_enabled()
-                and isinstance(att_mask, _AttnMask) and att_mask.decode_ok and att_mask.pos_host is not None
-                and ops.attention_decode_supported(q, self.num_attention_heads)):
+        if not (self._cache_step_ok(q, att_mask, past_kv, output_att, use_c) and past_kv.cache.multi_token
+                and not past_kv.cache.step_active and q.shape[1] > 1 and att_mask.pos_host is not None):
             return False
         cache, kv = past_kv.cache, att_mask.key_valid
         n = cache.lengths[past_kv.layer]
-        return (q.dtype == cache.dtype and n + q.shape[1] <= cache.capacity and q.shape[0] == cache.k[0].shape[0]
-                and att_mask.pos_host == n and (kv is None or tuple(kv.shape) == (q.shape[0], n + q.shape[1])))
+        return (n + q.shape[1] <= cache.capacity and att_mask.pos_host == n
+                and (kv is None or tuple(kv.shape) == (q.shape[0], n + q.shape[1])))
 
     def _chunk_attention(self, q, k, v, att_mask, past_kv):
         cache, layer = past_kv.cache, past_kv.layer
-        cos, sin = (self.rope.cos_cached, self.rope.sin_cached) if self.rope is not None else (None, None)
+        cos, sin = self._rope_tables()
         q = ops.kv_append_rope_chunk(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
         ctxv = ops.attention_chunk(q, cache, layer, self.num_attention_heads, att_mask.key_valid, dead_rows=att_mask.dead_rows)
         return self.out_proj(ctxv), cache

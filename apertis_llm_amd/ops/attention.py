@@ -25,6 +25,83 @@ ATTN_FUSED = True
 ATTN_LEFT_PAD = os.environ.get("APERTIS_MHA_LEFT_PAD", "0") == "1"
 
 
+# ------------------------------------------------------------------------------------------------------ operand checks
+# (host arithmetic on shapes, strides and pointers; none of them reads a device value)
+def _aligned_rows(t, rs, W, bs=0):
+    """(t, row stride) as the kernels' 16-byte loads take them: a packed copy (row stride W) when the pointer, the row
+    stride or - where the caller passes one - the batch stride `bs` is off a 16-byte boundary."""
+    es = t.element_size()
+    if t.data_ptr() % 16 or (rs * es) % 16 or (bs * es) % 16:
+        return t.clone(memory_format=torch.contiguous_format), W
+    return t, rs
+
+
+def _row2d(t, W, what):
+    """[B, W] or [B, 1, W] -> ([B, W] view with unit inner stride, row stride)."""
+    if t.dim() == 3 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 2 or t.shape[-1] != W:
+        raise ApertisHipError(f"{what}: expected [B, {W}] or [B, 1, {W}], got {tuple(t.shape)}")
+    if t.stride(-1) != 1 or (t.shape[0] > 1 and t.stride(0) < W):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else W)
+
+
+def _chunk3d(t, B, W, what):
+    """[B, Lq, W] -> (tensor with unit inner stride, row stride, batch stride)."""
+    if t.dim() != 3 or t.shape[0] != B or t.shape[-1] != W:
+        raise ApertisHipError(f"{what}: expected [{B}, Lq, {W}], got {tuple(t.shape)}")
+    Lq = t.shape[1]
+    if t.stride(-1) != 1 or (Lq > 1 and t.stride(1) < W) or (B > 1 and t.stride(0) < Lq * t.stride(1)):
+        t = t.contiguous()
+    rs = t.stride(1) if Lq > 1 else W
+    return t, rs, (t.stride(0) if B > 1 else Lq * rs)
+
+
+def _key_valid_exact(what, key_valid, B, L):
+    """key_valid of exactly [B, L] (or None) as the training / prefill kernels read it: int64, contiguous."""
+    if key_valid is None:
+        return None
+    if tuple(key_valid.shape) != (B, L):
+        raise ApertisHipError(f"{what}: key_valid {tuple(key_valid.shape)}, expected ({B}, {L})")
+    if key_valid.dtype != torch.int64 or not key_valid.is_contiguous():
+        key_valid = key_valid.to(torch.int64).contiguous()
+    return key_valid
+
+
+def _mask_rows(what, key_valid, B, Lk):
+    """key_valid [B, >= Lk] as the cache kernels read it: (int64 tensor with unit inner stride, row stride); None: (None, 0)."""
+    if key_valid is None:
+        return None, 0
+    if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < Lk:
+        raise ApertisHipError(f"{what}: key_valid {tuple(key_valid.shape)}, expected ({B}, >= {Lk})")
+    if key_valid.dtype != torch.int64 or key_valid.stride(1) != 1:
+        key_valid = key_valid.to(torch.int64).contiguous()
+    return key_valid, (key_valid.stride(0) if B > 1 else key_valid.shape[1])
+
+
+def _dropout(what, dropout_p, training):
+    """(p, seed) of an attention call: p is 0 outside training, and the seed of the library's counter hash is ONE draw from
+    torch's CPU generator, made only when p > 0 (a checkpointed recompute restores that generator and draws the same one)."""
+    p = float(dropout_p) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ApertisHipError(f"{what}: dropout_p {dropout_p} outside [0, 1)")
+    return p, (int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0)
+
+
+def _rope_table(what, cos, sin, W, required=False):
+    """(cos, sin, max_pos): the module's fp32 cos_cached / sin_cached [max_pos, W/2], contiguous.  They come together; without
+    a table (the appends: no rotation) max_pos is 0."""
+    if (cos is None) != (sin is None):
+        raise ApertisHipError(f"{what}: cos and sin come together")
+    if cos is None and not required:
+        return None, None, 0
+    if (cos is None or cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape
+            or 2 * cos.shape[-1] != W):
+        raise ApertisHipError(f"{what}: cos/sin must be fp32 [max_pos, {W // 2}]")
+    return cos.contiguous(), sin.contiguous(), cos.shape[0]
+
+
 def _positions(position_ids, B, L, max_pos, in_range=False):
     """(int64 tensor or None, batch stride).  Explicit positions are range-checked here, on the host: the stock module's
     cos_cached[position_ids] raises IndexError for them, so this does too (one sync; the model passes None for its own
@@ -90,70 +167,125 @@ def rope_qk(q, k, position_ids, cos, sin, in_range=False):
     if q.shape != k.shape or q.dtype != k.dtype or q.dim() != 3:
         raise ApertisHipError(f"rope_qk: q {tuple(q.shape)} {q.dtype} and k {tuple(k.shape)} {k.dtype} must match, [B, L, W]")
     B, L, W = q.shape
-    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
-        raise ApertisHipError(f"rope_qk: cos/sin must be fp32 [max_pos, {W // 2}]")
-    pos, pos_bs = _positions(position_ids, B, L, cos.shape[0], in_range)
-    return _RopeQK.apply(q, k, pos, pos_bs, cos.contiguous(), sin.contiguous())
+    cos, sin, max_pos = _rope_table("rope_qk", cos, sin, W, required=True)
+    pos, pos_bs = _positions(position_ids, B, L, max_pos, in_range)
+    return _RopeQK.apply(q, k, pos, pos_bs, cos, sin)
 
 
-def _attn_flops(B, L, H, D):
-    """Causal forward: 4*B*H*D*L(L+1)/2 (two products over the lower triangle)."""
-    return 4.0 * B * H * D * L * (L + 1) / 2
+# ------------------------------------------------------------------------------- training / prefill attention: one node
+class DocumentLayout:
+    """What document_layout returns: `start` / `end` int32 [B, L] (first token / one past the last token of each token's
+    document, as the kernels read them), `positions` int64 [B, L] (index - start: the position within the document) and
+    `pairs`, a host integer: the number of (query, key) pairs the mask keeps in the whole batch, sum of len*(len+1)/2."""
+    __slots__ = ("start", "end", "positions", "pairs")
+
+    def __init__(self, start, end, positions, pairs):
+        self.start, self.end, self.positions, self.pairs = start, end, positions, pairs
 
 
-class _CausalAttention(torch.autograd.Function):
+# csrc/attention.hip has ONE kernel set templated on <CAUSAL, DOC> behind three pairs of entry points, and this is all that
+# differs between them on the host: form -> (forward launch, backward launch, forward work(B, L, H, D, layout) in flops -
+# two products over the pairs the mask keeps; the backward's is 2.5 times it - and whether layout.start / layout.end follow
+# key_valid in both argument lists)
+_FORMS = {
+    "causal": ("apertis_attention_fwd", "apertis_attention_bwd", lambda B, L, H, D, layout: 4.0 * B * H * D * L * (L + 1) / 2,
+               False),
+    "full": ("apertis_attention_full_fwd", "apertis_attention_full_bwd", lambda B, L, H, D, layout: 4.0 * B * H * D * L * L,
+             False),
+    "doc": ("apertis_attention_doc_fwd", "apertis_attention_doc_bwd", lambda B, L, H, D, layout: 4.0 * H * D * layout.pairs,
+            True),
+}
+
+
+def _attn_fwd(form, q, q_rs, k, k_rs, v, v_rs, key_valid, layout, B, L, W, heads, p, seed):
+    """One forward launch of `form`: (O [B, L, W] packed, LSE [B, heads, L] fp32)."""
+    name, _, work, doc = _FORMS[form]
+    bounds = (ptr(layout.start), ptr(layout.end)) if doc else ()
+    out = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
+    lse = torch.empty(B, heads, L, device=q.device, dtype=torch.float32)
+    _launch(name, getattr(_lib.load(), name),
+            (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(key_valid), *bounds, ptr(out), W, ptr(lse), B, L, heads, W // heads,
+             p, seed, dtype_code(q), stream_ptr()), work=work(B, L, heads, W // heads, layout))
+    return out, lse
+
+
+def _attn_bwd(form, q, q_rs, k, k_rs, v, v_rs, out, dout, lse, key_valid, layout, dq, dk, dv, d_rs, B, L, W, heads, p, seed):
+    """One backward launch of `form` into dq, dk, dv (one row stride d_rs).  The incoming gradient is whatever autograd hands
+    over: another dtype is cast, and rows the kernels cannot take as they are (_rows, _aligned_rows) are copied."""
+    _, name, work, doc = _FORMS[form]
+    bounds = (ptr(layout.start), ptr(layout.end)) if doc else ()
+    lib = _lib.load()
+    dout = dout.to(q.dtype)
+    dout, do_rs = _aligned_rows(*_rows(dout, W), W)
+    ws = torch.empty(lib.apertis_attention_bwd_workspace_bytes(B, L, heads) // 4, device=q.device, dtype=torch.float32)
+    _launch(name, getattr(lib, name),
+            (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(out), W, ptr(dout), do_rs, ptr(lse), ptr(key_valid), *bounds, ptr(ws),
+             ptr(dq), ptr(dk), ptr(dv), d_rs, B, L, heads, W // heads, p, seed, dtype_code(q), stream_ptr()),
+            work=2.5 * work(B, L, heads, W // heads, layout))
+
+
+class _Attention(torch.autograd.Function):
+    """causal_attention, full_attention and document_attention (`form`, a key of _FORMS; `layout`: the DocumentLayout of
+    "doc", else None)."""
+
     @staticmethod
-    def forward(ctx, q, k, v, heads, key_valid, p, seed):
-        lib = _lib.load()
+    def forward(ctx, form, q, k, v, heads, key_valid, p, seed, layout=None):
         B, L, W = q.shape
-        D = W // heads
         q, q_rs = _rows(q, W)
         k, k_rs = _rows(k, W)
         v, v_rs = _rows(v, W)
-        out = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
-        lse = torch.empty(B, heads, L, device=q.device, dtype=torch.float32)
-        _launch("apertis_attention_fwd", lib.apertis_attention_fwd,
-                (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(key_valid), ptr(out), W, ptr(lse), B, L, heads, D, p, seed,
-                 dtype_code(q), stream_ptr()), work=_attn_flops(B, L, heads, D))
-        ctx.save_for_backward(q, k, v, out, lse, key_valid)
+        out, lse = _attn_fwd(form, q, q_rs, k, k_rs, v, v_rs, key_valid, layout, B, L, W, heads, p, seed)
+        doc = (layout.start, layout.end) if form == "doc" else ()
+        ctx.save_for_backward(q, k, v, out, lse, key_valid, *doc)
+        ctx.cfg = (form, heads, p, seed, layout.pairs if doc else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, key_valid, *doc = ctx.saved_tensors
+        form, heads, p, seed, pairs = ctx.cfg
+        layout = DocumentLayout(*doc, None, pairs) if doc else None
+        B, L, W = q.shape
+        dq = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
+        dk = torch.empty_like(dq)
+        dv = torch.empty_like(dq)
+        _attn_bwd(form, q, q.stride(-2), k, k.stride(-2), v, v.stride(-2), out, dout, lse, key_valid, layout, dq, dk, dv, W,
+                  B, L, W, heads, p, seed)
+        return None, dq, dk, dv, None, None, None, None, None
+
+
+class _FullAttentionQKV(torch.autograd.Function):
+    """The "full" form on the column slices of ONE [B, L, 3W] tensor: nothing is copied on the way in (row stride 3W), and the
+    backward writes dq | dk | dv into the column slices of ONE [B, L, 3W] gradient - three slice backwards would each
+    materialise a zero-filled [B, L, 3W] and autograd would add them."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, p, seed):
+        B, L, W3 = qkv.shape
+        W = W3 // 3
+        qkv, rs = _aligned_rows(*_rows(qkv, W3), W3)
+        out, lse = _attn_fwd("full", qkv[..., :W], rs, qkv[..., W:2 * W], rs, qkv[..., 2 * W:], rs, None, None, B, L, W, heads,
+                             p, seed)
+        ctx.save_for_backward(qkv, out, lse)
         ctx.cfg = (heads, p, seed)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
-        q, k, v, out, lse, key_valid = ctx.saved_tensors
+        qkv, out, lse = ctx.saved_tensors
         heads, p, seed = ctx.cfg
-        B, L, W = q.shape
-        D = W // heads
-        dout = dout.to(q.dtype)
-        dout, do_rs = _rows(dout, W)
-        if dout.data_ptr() % 16:
-            dout = dout.clone()
-        ws = torch.empty(lib.apertis_attention_bwd_workspace_bytes(B, L, heads) // 4, device=q.device, dtype=torch.float32)
-        dq = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
-        dk = torch.empty_like(dq)
-        dv = torch.empty_like(dq)
-        _launch("apertis_attention_bwd", lib.apertis_attention_bwd,
-                (ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(v), v.stride(-2), ptr(out), W, ptr(dout), do_rs, ptr(lse),
-                 ptr(key_valid), ptr(ws), ptr(dq), ptr(dk), ptr(dv), W, B, L, heads, D, p, seed, dtype_code(q), stream_ptr()),
-                work=2.5 * _attn_flops(B, L, heads, D))
-        return dq, dk, dv, None, None, None, None
+        B, L, W3 = qkv.shape
+        W, rs = W3 // 3, qkv.stride(-2)
+        d = torch.empty(B, L, W3, device=qkv.device, dtype=qkv.dtype)
+        _attn_bwd("full", qkv[..., :W], rs, qkv[..., W:2 * W], rs, qkv[..., 2 * W:], rs, out, dout, lse, None, None,
+                  d[..., :W], d[..., W:2 * W], d[..., 2 * W:], W3, B, L, W, heads, p, seed)
+        return d, None, None, None
 
 
 def attention_supported(q, heads):
     """Whether causal_attention takes q [B, L, heads*D] of this dtype and head dim (D 64 or 128, fp32 or bf16)."""
     return (q.dim() == 3 and q.shape[-1] % heads == 0 and q.shape[-1] // heads in (64, 128)
             and q.dtype in (torch.float32, torch.bfloat16))
-
-
-def _mask_rows(what, key_valid, B, Lk):
-    """key_valid [B, >= Lk] as the kernels read it: (int64 tensor with unit inner stride, row stride)."""
-    if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < Lk:
-        raise ApertisHipError(f"{what}: key_valid {tuple(key_valid.shape)}, expected ({B}, >= {Lk})")
-    if key_valid.dtype != torch.int64 or key_valid.stride(1) != 1:
-        key_valid = key_valid.to(torch.int64).contiguous()
-    return key_valid, (key_valid.stride(0) if B > 1 else key_valid.shape[1])
 
 
 def attention_dead_rows(out, v, key_valid, n=0):
@@ -178,9 +310,8 @@ def attention_dead_rows(out, v, key_valid, n=0):
         raise ApertisHipError("attention_dead_rows: out is written in place: unit inner stride, rows and batches on 16-byte "
                               "boundaries")
     v, v_rs, v_bs = _chunk3d(v[:, :Lk], B, W, "attention_dead_rows v")
-    if v.data_ptr() % 16 or (v_rs * es) % 16 or (B > 1 and (v_bs * es) % 16):
-        v = v.clone(memory_format=torch.contiguous_format)
-        v_rs, v_bs = W, Lk * W
+    v, v_rs = _aligned_rows(v, v_rs, W, v_bs if B > 1 else 0)
+    v_bs = v.stride(0) if B > 1 else Lk * v_rs                      # (as _chunk3d gave it, or the packed copy's)
     key_valid, kv_rs = _mask_rows("attention_dead_rows", key_valid, B, Lk)
     _launch("apertis_attention_dead_rows", _lib.load().apertis_attention_dead_rows,
             (ptr(v), v_rs, v_bs, ptr(key_valid), kv_rs, ptr(out), o_rs, o_bs, B, Lq, int(n), W, dtype_code(out), stream_ptr()),
@@ -213,32 +344,15 @@ def causal_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=Fal
         raise ApertisHipError(f"causal_attention: q/k/v {tuple(q.shape)} {q.dtype} with {heads} heads (D 64 or 128, fp32 or bf16, "
                               "one shape and dtype)")
     B, L, _ = q.shape
-    if key_valid is not None:
-        if tuple(key_valid.shape) != (B, L):
-            raise ApertisHipError(f"causal_attention: key_valid {tuple(key_valid.shape)}, expected ({B}, {L})")
-        if key_valid.dtype != torch.int64 or not key_valid.is_contiguous():
-            key_valid = key_valid.to(torch.int64).contiguous()
-    p = float(dropout_p) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise ApertisHipError(f"causal_attention: dropout_p {dropout_p} outside [0, 1)")
-    seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0
-    out = _CausalAttention.apply(q, k, v, int(heads), key_valid, p, seed)
+    key_valid = _key_valid_exact("causal_attention", key_valid, B, L)
+    p, seed = _dropout("causal_attention", dropout_p, training)
+    out = _Attention.apply("causal", q, k, v, int(heads), key_valid, p, seed, None)
     if dead_rows and key_valid is not None and B:
         attention_dead_rows(out, v, key_valid)
     return out
 
 
 # --------------------------------------------------------------------------------- packed rows: document-masked attention
-class DocumentLayout:
-    """What document_layout returns: `start` / `end` int32 [B, L] (first token / one past the last token of each token's
-    document, as the kernels read them), `positions` int64 [B, L] (index - start: the position within the document) and
-    `pairs`, a host integer: the number of (query, key) pairs the mask keeps in the whole batch, sum of len*(len+1)/2."""
-    __slots__ = ("start", "end", "positions", "pairs")
-
-    def __init__(self, start, end, positions, pairs):
-        self.start, self.end, self.positions, self.pairs = start, end, positions, pairs
-
-
 def document_layout(document_ids):
     """The layout of packed rows from `document_ids` [B, L] (integers, non-decreasing along L in every row: a document is a
     run of equal ids).  Built with torch ops on the ids' device (a running maximum over the run starts and its mirror over
@@ -268,46 +382,6 @@ def document_layout(document_ids):
     return DocumentLayout(start.to(torch.int32).contiguous(), end.to(torch.int32).contiguous(), positions, int(pairs))
 
 
-class _DocumentAttention(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, heads, key_valid, start, end, pairs, p, seed):
-        lib = _lib.load()
-        B, L, W = q.shape
-        D = W // heads
-        q, q_rs = _rows(q, W)
-        k, k_rs = _rows(k, W)
-        v, v_rs = _rows(v, W)
-        out = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
-        lse = torch.empty(B, heads, L, device=q.device, dtype=torch.float32)
-        _launch("apertis_attention_doc_fwd", lib.apertis_attention_doc_fwd,
-                (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(key_valid), ptr(start), ptr(end), ptr(out), W, ptr(lse), B, L,
-                 heads, D, p, seed, dtype_code(q), stream_ptr()), work=4.0 * heads * D * pairs)
-        ctx.save_for_backward(q, k, v, out, lse, key_valid, start, end)
-        ctx.cfg = (heads, pairs, p, seed)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        lib = _lib.load()
-        q, k, v, out, lse, key_valid, start, end = ctx.saved_tensors
-        heads, pairs, p, seed = ctx.cfg
-        B, L, W = q.shape
-        D = W // heads
-        dout = dout.to(q.dtype)
-        dout, do_rs = _rows(dout, W)
-        if dout.data_ptr() % 16:
-            dout = dout.clone()
-        ws = torch.empty(lib.apertis_attention_bwd_workspace_bytes(B, L, heads) // 4, device=q.device, dtype=torch.float32)
-        dq = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
-        dk = torch.empty_like(dq)
-        dv = torch.empty_like(dq)
-        _launch("apertis_attention_doc_bwd", lib.apertis_attention_doc_bwd,
-                (ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(v), v.stride(-2), ptr(out), W, ptr(dout), do_rs, ptr(lse),
-                 ptr(key_valid), ptr(start), ptr(end), ptr(ws), ptr(dq), ptr(dk), ptr(dv), W, B, L, heads, D, p, seed,
-                 dtype_code(q), stream_ptr()), work=2.5 * 4.0 * heads * D * pairs)
-        return dq, dk, dv, None, None, None, None, None, None, None
-
-
 def document_attention(q, k, v, heads, layout, key_valid=None, dropout_p=0.0, training=False):
     """causal_attention on PACKED rows: query i of row b attends key j iff layout.start[b, i] <= j <= i (and key_valid),
     so the documents of a row - contiguous runs, document_layout - do not see each other.  The layout contract, the dropout
@@ -326,16 +400,9 @@ def document_attention(q, k, v, heads, layout, key_valid=None, dropout_p=0.0, tr
         if tuple(t.shape) != (B, L) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != q.device:
             raise ApertisHipError(f"document_attention: layout of {tuple(t.shape)} {t.dtype} on {t.device} for q of [{B}, {L}, ...] "
                                   f"on {q.device}")
-    if key_valid is not None:
-        if tuple(key_valid.shape) != (B, L):
-            raise ApertisHipError(f"document_attention: key_valid {tuple(key_valid.shape)}, expected ({B}, {L})")
-        if key_valid.dtype != torch.int64 or not key_valid.is_contiguous():
-            key_valid = key_valid.to(torch.int64).contiguous()
-    p = float(dropout_p) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise ApertisHipError(f"document_attention: dropout_p {dropout_p} outside [0, 1)")
-    seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0
-    return _DocumentAttention.apply(q, k, v, int(heads), key_valid, layout.start, layout.end, layout.pairs, p, seed)
+    key_valid = _key_valid_exact("document_attention", key_valid, B, L)
+    p, seed = _dropout("document_attention", dropout_p, training)
+    return _Attention.apply("doc", q, k, v, int(heads), key_valid, p, seed, layout)
 
 
 # ------------------------------------------------------------------------------------------- bidirectional attention
@@ -346,90 +413,6 @@ def document_attention(q, k, v, heads, layout, key_valid=None, dropout_p=0.0, tr
 VIT_FUSED = os.environ.get("APERTIS_VIT_FUSED", "0") == "1"
 
 
-def _full_attn_flops(B, L, H, D):
-    """Bidirectional forward: 4*B*H*D*L^2 (two products over the whole square)."""
-    return 4.0 * B * H * D * L * L
-
-
-def _full_fwd(q, q_rs, k, k_rs, v, v_rs, key_valid, B, L, W, heads, p, seed):
-    """One apertis_attention_full_fwd launch: (O [B, L, W] packed, LSE [B, heads, L] fp32)."""
-    lib = _lib.load()
-    out = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
-    lse = torch.empty(B, heads, L, device=q.device, dtype=torch.float32)
-    _launch("apertis_attention_full_fwd", lib.apertis_attention_full_fwd,
-            (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(key_valid), ptr(out), W, ptr(lse), B, L, heads, W // heads, p, seed,
-             dtype_code(q), stream_ptr()), work=_full_attn_flops(B, L, heads, W // heads))
-    return out, lse
-
-
-def _full_bwd(q, q_rs, k, k_rs, v, v_rs, out, dout, lse, key_valid, dq, dk, dv, d_rs, B, L, W, heads, p, seed):
-    """One apertis_attention_full_bwd launch into dq, dk, dv (one row stride d_rs)."""
-    lib = _lib.load()
-    dout = dout.to(q.dtype)
-    dout, do_rs = _rows(dout, W)
-    if dout.data_ptr() % 16 or (do_rs * dout.element_size()) % 16:
-        dout, do_rs = dout.clone(memory_format=torch.contiguous_format), W
-    ws = torch.empty(lib.apertis_attention_bwd_workspace_bytes(B, L, heads) // 4, device=q.device, dtype=torch.float32)
-    _launch("apertis_attention_full_bwd", lib.apertis_attention_full_bwd,
-            (ptr(q), q_rs, ptr(k), k_rs, ptr(v), v_rs, ptr(out), W, ptr(dout), do_rs, ptr(lse), ptr(key_valid), ptr(ws), ptr(dq),
-             ptr(dk), ptr(dv), d_rs, B, L, heads, W // heads, p, seed, dtype_code(q), stream_ptr()),
-            work=2.5 * _full_attn_flops(B, L, heads, W // heads))
-
-
-class _FullAttention(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, heads, key_valid, p, seed):
-        B, L, W = q.shape
-        q, q_rs = _rows(q, W)
-        k, k_rs = _rows(k, W)
-        v, v_rs = _rows(v, W)
-        out, lse = _full_fwd(q, q_rs, k, k_rs, v, v_rs, key_valid, B, L, W, heads, p, seed)
-        ctx.save_for_backward(q, k, v, out, lse, key_valid)
-        ctx.cfg = (heads, p, seed)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, out, lse, key_valid = ctx.saved_tensors
-        heads, p, seed = ctx.cfg
-        B, L, W = q.shape
-        dq = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
-        dk = torch.empty_like(dq)
-        dv = torch.empty_like(dq)
-        _full_bwd(q, q.stride(-2), k, k.stride(-2), v, v.stride(-2), out, dout, lse, key_valid, dq, dk, dv, W, B, L, W, heads,
-                  p, seed)
-        return dq, dk, dv, None, None, None, None
-
-
-class _FullAttentionQKV(torch.autograd.Function):
-    """_FullAttention on the column slices of ONE [B, L, 3W] tensor: nothing is copied on the way in (row stride 3W), and the
-    backward writes dq | dk | dv into the column slices of ONE [B, L, 3W] gradient - three slice backwards would each
-    materialise a zero-filled [B, L, 3W] and autograd would add them."""
-
-    @staticmethod
-    def forward(ctx, qkv, heads, p, seed):
-        B, L, W3 = qkv.shape
-        W = W3 // 3
-        qkv, rs = _rows(qkv, W3)
-        if qkv.data_ptr() % 16 or (rs * qkv.element_size()) % 16:
-            qkv, rs = qkv.clone(memory_format=torch.contiguous_format), W3
-        out, lse = _full_fwd(qkv[..., :W], rs, qkv[..., W:2 * W], rs, qkv[..., 2 * W:], rs, None, B, L, W, heads, p, seed)
-        ctx.save_for_backward(qkv, out, lse)
-        ctx.cfg = (heads, p, seed)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        heads, p, seed = ctx.cfg
-        B, L, W3 = qkv.shape
-        W, rs = W3 // 3, qkv.stride(-2)
-        d = torch.empty(B, L, W3, device=qkv.device, dtype=qkv.dtype)
-        _full_bwd(qkv[..., :W], rs, qkv[..., W:2 * W], rs, qkv[..., 2 * W:], rs, out, dout, lse, None, d[..., :W],
-                  d[..., W:2 * W], d[..., 2 * W:], W3, B, L, W, heads, p, seed)
-        return d, None, None, None
-
-
 def full_attention_supported(q, heads, packed=False):
     """Whether full_attention takes q [B, L, heads*D] - or, packed=True, full_attention_qkv takes qkv [B, L, 3*heads*D] - of
     this dtype, head dim and batch (D 64 or 128, fp32 or bf16, B*heads <= 65535: the grid's y dimension)."""
@@ -438,13 +421,6 @@ def full_attention_supported(q, heads, packed=False):
     W = q.shape[-1] // 3 if packed else q.shape[-1]
     return (W % heads == 0 and W // heads in (64, 128) and q.dtype in (torch.float32, torch.bfloat16)
             and q.shape[0] * heads <= 65535)
-
-
-def _full_p_seed(what, dropout_p, training):
-    p = float(dropout_p) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise ApertisHipError(f"{what}: dropout_p {dropout_p} outside [0, 1)")
-    return p, (int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0)
 
 
 def full_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=False):
@@ -461,13 +437,9 @@ def full_attention(q, k, v, heads, key_valid=None, dropout_p=0.0, training=False
         raise ApertisHipError(f"full_attention: q/k/v {tuple(q.shape)} {q.dtype} with {heads} heads (D 64 or 128, fp32 or bf16, "
                               "one shape and dtype, B*heads <= 65535)")
     B, L, _ = q.shape
-    if key_valid is not None:
-        if tuple(key_valid.shape) != (B, L):
-            raise ApertisHipError(f"full_attention: key_valid {tuple(key_valid.shape)}, expected ({B}, {L})")
-        if key_valid.dtype != torch.int64 or not key_valid.is_contiguous():
-            key_valid = key_valid.to(torch.int64).contiguous()
-    p, seed = _full_p_seed("full_attention", dropout_p, training)
-    return _FullAttention.apply(q, k, v, int(heads), key_valid, p, seed)
+    key_valid = _key_valid_exact("full_attention", key_valid, B, L)
+    p, seed = _dropout("full_attention", dropout_p, training)
+    return _Attention.apply("full", q, k, v, int(heads), key_valid, p, seed, None)
 
 
 def full_attention_qkv(qkv, heads, dropout_p=0.0, training=False):
@@ -481,7 +453,7 @@ def full_attention_qkv(qkv, heads, dropout_p=0.0, training=False):
                               "D 64 or 128, fp32 or bf16, B*heads <= 65535)")
     if (qkv.shape[-1] // 3 * qkv.element_size()) % 16:
         raise ApertisHipError(f"full_attention_qkv: the slices of width {qkv.shape[-1] // 3} are not 16-byte aligned")
-    p, seed = _full_p_seed("full_attention_qkv", dropout_p, training)
+    p, seed = _dropout("full_attention_qkv", dropout_p, training)
     return _FullAttentionQKV.apply(qkv, int(heads), p, seed)
 
 
@@ -643,17 +615,6 @@ class KVCache:
         return self._ws if nbytes else None
 
 
-def _row2d(t, W, what):
-    """[B, W] or [B, 1, W] -> ([B, W] view with unit inner stride, row stride)."""
-    if t.dim() == 3 and t.shape[1] == 1:
-        t = t[:, 0]
-    if t.dim() != 2 or t.shape[-1] != W:
-        raise ApertisHipError(f"{what}: expected [B, {W}] or [B, 1, {W}], got {tuple(t.shape)}")
-    if t.stride(-1) != 1 or (t.shape[0] > 1 and t.stride(0) < W):
-        t = t.contiguous()
-    return t, (t.stride(0) if t.shape[0] > 1 else W)
-
-
 def _append_operands(what, q, k, v, cache, layer, cos, sin):
     """What both appends hand to the library: q, k, v as rows with their strides, the rotary table and its length (0: no
     rotation) and the output for the rotated q."""
@@ -663,13 +624,7 @@ def _append_operands(what, q, k, v, cache, layer, cos, sin):
     v, v_rs = _row2d(v, W, f"{what} v")
     if not (q.shape[0] == k.shape[0] == v.shape[0] == B and q.dtype == k.dtype == v.dtype == cache.dtype):
         raise ApertisHipError(f"{what}: q/k/v {tuple(q.shape)} {q.dtype} against a cache of [{B}, {cap}, {W}] {cache.dtype}")
-    max_pos = 0
-    if (cos is None) != (sin is None):
-        raise ApertisHipError(f"{what}: cos and sin come together")
-    if cos is not None:
-        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
-            raise ApertisHipError(f"{what}: cos/sin must be fp32 [max_pos, {W // 2}]")
-        cos, sin, max_pos = cos.contiguous(), sin.contiguous(), cos.shape[0]
+    cos, sin, max_pos = _rope_table(what, cos, sin, W)
     qo = torch.empty(B, W, device=q.device, dtype=q.dtype)
     return (q, q_rs), (k, k_rs), (v, v_rs), cos, sin, max_pos, qo
 
@@ -683,8 +638,7 @@ def _decode_operands(what, lib, q, cache, layer, heads, splits):
     if not attention_decode_supported(q, heads) or q.shape[0] != B or q.dtype != cache.dtype:
         raise ApertisHipError(f"{what}: q {tuple(q.shape)} {q.dtype} with {heads} heads against a cache of "
                               f"[{B}, {cap}, {W}] {cache.dtype} (D 64 or 128, fp32 or bf16, one dtype)")
-    if q.data_ptr() % 16 or (q_rs * q.element_size()) % 16:
-        q, q_rs = q.clone(memory_format=torch.contiguous_format), W
+    q, q_rs = _aligned_rows(q, q_rs, W)
     D, ws = W // heads, None
     n = splits(D) if callable(splits) else splits
     if 1 <= n <= ATTN_DECODE_MAX_SPLITS:
@@ -743,13 +697,7 @@ def attention_decode(q, cache, layer, heads, key_valid=None, splits=0):
     Lk = cache.lengths[layer]
     n = int(splits) if splits else lambda D: int(lib.apertis_attention_decode_splits(B, heads, max(Lk, 1), D)) if B else 1
     q, q_rs, D, ws, out = _decode_operands("attention_decode", lib, q, cache, layer, heads, n)
-    kv_rs = 0
-    if key_valid is not None:
-        if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < Lk:
-            raise ApertisHipError(f"attention_decode: key_valid {tuple(key_valid.shape)}, expected ({B}, >= {Lk})")
-        if key_valid.dtype != torch.int64 or key_valid.stride(1) != 1:
-            key_valid = key_valid.to(torch.int64).contiguous()
-        kv_rs = key_valid.stride(0) if B > 1 else key_valid.shape[1]
+    key_valid, kv_rs = _mask_rows("attention_decode", key_valid, B, Lk)
     nbytes = 2.0 * B * Lk * W * q.element_size()
     _launch("apertis_attention_decode", lib.apertis_attention_decode,
             (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
@@ -759,17 +707,6 @@ def attention_decode(q, cache, layer, heads, key_valid=None, splits=0):
 
 
 # ------------------------------------------------------------------------------------------------- multi-token steps
-def _chunk3d(t, B, W, what):
-    """[B, Lq, W] -> (tensor with unit inner stride, row stride, batch stride)."""
-    if t.dim() != 3 or t.shape[0] != B or t.shape[-1] != W:
-        raise ApertisHipError(f"{what}: expected [{B}, Lq, {W}], got {tuple(t.shape)}")
-    Lq = t.shape[1]
-    if t.stride(-1) != 1 or (Lq > 1 and t.stride(1) < W) or (B > 1 and t.stride(0) < Lq * t.stride(1)):
-        t = t.contiguous()
-    rs = t.stride(1) if Lq > 1 else W
-    return t, rs, (t.stride(0) if B > 1 else Lq * rs)
-
-
 def kv_append_rope_chunk(q, k, v, cache, layer, t0=None, cos=None, sin=None):
     """A chunk of Lq tokens of every sequence into layer `layer` of `cache`, in ONE launch: rows l of q and k ([B, Lq, W]) are
     rotated at rotary position `t0 + l` (a host integer; default: the first row appended to) with the module's fp32
@@ -790,16 +727,10 @@ def kv_append_rope_chunk(q, k, v, cache, layer, t0=None, cos=None, sin=None):
                               f"a cache of [{B}, {cap}, {W}] {cache.dtype}")
     if row + Lq > cap:
         raise ApertisHipError(f"kv_append_rope_chunk: {Lq} rows do not fit ({row} of {cap} rows held)")
-    max_pos = 0
-    if (cos is None) != (sin is None):
-        raise ApertisHipError("kv_append_rope_chunk: cos and sin come together")
+    cos, sin, max_pos = _rope_table("kv_append_rope_chunk", cos, sin, W)
     t0 = row if t0 is None else int(t0)
-    if cos is not None:
-        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or 2 * cos.shape[-1] != W:
-            raise ApertisHipError(f"kv_append_rope_chunk: cos/sin must be fp32 [max_pos, {W // 2}]")
-        cos, sin, max_pos = cos.contiguous(), sin.contiguous(), cos.shape[0]
-        if Lq and not (-max_pos <= t0 and t0 + Lq <= max_pos):
-            raise IndexError(f"positions {t0}..{t0 + Lq - 1} outside the rotary table of {max_pos} positions")
+    if cos is not None and Lq and not (-max_pos <= t0 and t0 + Lq <= max_pos):
+        raise IndexError(f"positions {t0}..{t0 + Lq - 1} outside the rotary table of {max_pos} positions")
     qo = torch.empty(B, Lq, W, device=q.device, dtype=q.dtype)
     _launch("apertis_rope_kv_append_chunk", lib.apertis_rope_kv_append_chunk,
             (ptr(q), q_rs, q_bs, ptr(k), k_rs, k_bs, ptr(v), v_rs, v_bs, ptr(cos), ptr(sin), max_pos, t0, ptr(qo), ptr(kc),
@@ -841,21 +772,13 @@ def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0, dead_rows=
     Lq, Lk = q.shape[1], cache.lengths[layer]
     if Lq > Lk:
         raise ApertisHipError(f"attention_chunk: {Lq} query rows but the layer holds {Lk} (kv_append_rope_chunk first)")
-    q, q_rs = _rows(q, W)
-    if q.data_ptr() % 16 or (q_rs * q.element_size()) % 16:
-        q, q_rs = q.clone(memory_format=torch.contiguous_format), W
+    q, q_rs = _aligned_rows(*_rows(q, W), W)
     D, ns, ws = W // heads, int(splits), None              # ns: the split count the workspace is sized for AND the launch takes
     if ns == 0:
         ns = int(lib.apertis_attention_chunk_splits(B, heads, Lq, Lk, D)) if B else 1
     if 1 <= ns <= ATTN_DECODE_MAX_SPLITS:
         ws = cache._workspace(max(int(lib.apertis_attention_chunk_workspace_bytes(B, heads, Lq, D, ns)), 0))
-    kv_rs = 0
-    if key_valid is not None:
-        if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < Lk:
-            raise ApertisHipError(f"attention_chunk: key_valid {tuple(key_valid.shape)}, expected ({B}, >= {Lk})")
-        if key_valid.dtype != torch.int64 or key_valid.stride(1) != 1:
-            key_valid = key_valid.to(torch.int64).contiguous()
-        kv_rs = key_valid.stride(0) if B > 1 else key_valid.shape[1]
+    key_valid, kv_rs = _mask_rows("attention_chunk", key_valid, B, Lk)
     out = torch.empty(B, Lq, W, device=q.device, dtype=q.dtype)
     _launch("apertis_attention_chunk", lib.apertis_attention_chunk,
             (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,

@@ -223,16 +223,14 @@ def test_document_attention_dropout_mask_matches_numpy_hash(dev):
     layout, allow = ops.document_layout(ids), _allow(ids)
     q, k, v, do = _inputs(dev, B, L, H, D, torch.float32, 6)
     keep = _keep_mask(seed, B, H, L, p)
-    fn = lambda a, b, c: ops.attention._DocumentAttention.apply(a, b, c, H, None, layout.start, layout.end,     # noqa: E731
-                                                                layout.pairs, p, seed)
+    fn = lambda a, b, c: ops.attention._Attention.apply("doc", a, b, c, H, None, p, seed, layout)     # noqa: E731
     got = _fwd_bwd(fn, q, k, v, do)
     ref = _fwd_bwd(lambda a, b, c: _ref_attention(a, b, c, H, allow, keep, p), q.double(), k.double(), v.double(), do.double())
     for n, g_, r in zip(NAMES, got, ref):
         rel_error_report(f"document attention dropout fp32 {n}", g_, r, rtol=1e-4)
     again = _fwd_bwd(fn, q, k, v, do)
     assert all(torch.equal(a, b) for a, b in zip(got, again))
-    other = _fwd_bwd(lambda a, b, c: ops.attention._DocumentAttention.apply(a, b, c, H, None, layout.start, layout.end,
-                                                                            layout.pairs, p, seed + 1), q, k, v, do)
+    other = _fwd_bwd(lambda a, b, c: ops.attention._Attention.apply("doc", a, b, c, H, None, p, seed + 1, layout), q, k, v, do)
     assert not torch.equal(got[0], other[0])
     # through the op: the seed comes from torch's RNG, training only
     torch.manual_seed(7)
@@ -242,6 +240,72 @@ def test_document_attention_dropout_mask_matches_numpy_hash(dev):
     assert torch.equal(a, b)
     assert torch.equal(ops.document_attention(q, k, v, H, layout, None, 0.3, training=False),
                        ops.document_attention(q, k, v, H, layout))
+
+
+# ------------------------------------------------------------------------------------------------ every form of the node
+# (causal, full and doc run through ONE autograd node and one table of what differs, ops.attention._FORMS: these hold every
+#  row of that table, here because the document ids live here)
+LAUNCHES = {"causal": ("apertis_attention_fwd", "apertis_attention_bwd"),
+            "full": ("apertis_attention_full_fwd", "apertis_attention_full_bwd"),
+            "doc": ("apertis_attention_doc_fwd", "apertis_attention_doc_bwd")}
+
+
+def _form_fn(ops, form, H, layout):
+    if form == "qkv":                                        # one [B, L, 3W] input: q | k | v stacked along the width
+        return lambda a, b, c: ops.full_attention_qkv(torch.cat((a, b, c), dim=-1), H)
+    return {"causal": lambda a, b, c: ops.causal_attention(a, b, c, H),
+            "full": lambda a, b, c: ops.full_attention(a, b, c, H),
+            "doc": lambda a, b, c: ops.document_attention(a, b, c, H, layout)}[form]
+
+
+@pytest.mark.parametrize("form", ["causal", "full", "doc"])
+def test_every_form_launches_its_own_pair_and_counts_its_own_work(dev, form):
+    """One forward + backward of each form under a timer on all six launch names: exactly one launch of the form's own two
+    and none of the other four, with the form's flops (L = 97: no multiple of the 64-row work-group or the 32-key tile)."""
+    from apertis_llm_amd import ops
+    B, H, D, L = 2, 2, 64, 97
+    layout = ops.document_layout(_doc_ids(L, dev)[:B])
+    pairs = sum(n * (n + 1) // 2 for lens in LAYOUTS[L][:B] for n in lens)
+    assert layout.pairs == pairs
+    fwd_work = {"causal": 4.0 * B * H * D * L * (L + 1) / 2, "full": 4.0 * B * H * D * L * L, "doc": 4.0 * H * D * pairs}[form]
+    q, k, v, do = _inputs(dev, B, L, H, D, torch.float32, 3)
+    timer = ops.KernelTimer([n for pair in LAUNCHES.values() for n in pair])
+    ops.set_kernel_timer(timer)
+    try:
+        _fwd_bwd(_form_fn(ops, form, H, layout), q, k, v, do)
+    finally:
+        ops.set_kernel_timer(None)
+    s = timer.summary()
+    fwd, bwd = LAUNCHES[form]
+    assert {n: r["launches"] for n, r in s.items()} == {fwd: 1, bwd: 1}
+    assert s[fwd]["work"] == fwd_work and s[bwd]["work"] == 2.5 * fwd_work
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("form", ["causal", "full", "doc", "qkv"])
+def test_misaligned_gradient_is_copied_and_gives_the_same_bits(dev, form, dtype):
+    """A gradient whose rows (a [B, L, W + 1] buffer's first W columns: 516- and 258-byte rows) or whose pointer (one element
+    into a flat buffer) is off a 16-byte boundary is not what the kernels' 16-byte loads take: every form copies it, and dQ,
+    dK, dV have the bits a packed copy of the same gradient gives."""
+    from apertis_llm_amd import ops
+    B, L, H, D = 2, 33, 2, 64
+    W = H * D
+    q, k, v, _ = _inputs(dev, B, L, H, D, dtype, 13)
+    ids = torch.stack([torch.repeat_interleave(torch.arange(2), torch.tensor(lens)) for lens in ([5, 28], [32, 1])]).to(dev)
+    fn = _form_fn(ops, form, H, ops.document_layout(ids))
+    gen = torch.Generator(device=dev).manual_seed(14)
+    rows = torch.randn(B, L, W + 1, device=dev, generator=gen).to(dtype)[..., :W]
+    shifted = torch.randn(B * L * W + 1, device=dev, generator=gen).to(dtype)[1:].view(B, L, W)
+    assert (rows.stride(1) * rows.element_size()) % 16 and shifted.data_ptr() % 16
+    q, k, v = (t.requires_grad_() for t in (q, k, v))
+    o = fn(q, k, v)
+    for what, g in (("row stride", rows), ("pointer", shifted)):
+        packed = g.clone(memory_format=torch.contiguous_format)     # (a fresh allocation: .contiguous() keeps the shifted view)
+        assert packed.is_contiguous() and packed.data_ptr() % 16 == 0
+        got = torch.autograd.grad(o, (q, k, v), g, retain_graph=True)
+        want = torch.autograd.grad(o, (q, k, v), packed, retain_graph=True)
+        for n, g_, w in zip(NAMES[1:], got, want):
+            assert torch.equal(g_, w) and bool(g_.any()), (what, n)
 
 
 # ------------------------------------------------------------------------------------------------ refusals

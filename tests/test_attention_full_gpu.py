@@ -108,7 +108,7 @@ def test_full_attention_dropout_mask_matches_numpy_hash(dev, dtype):
     q, k, v, do = _inputs(dev, B, L, H, D, dtype, 5)
     kv = _mask("holes", B, L, dev)
     keep = _keep_mask(seed, B, H, L, p)
-    fn = lambda a, b, c: ops.attention._FullAttention.apply(a, b, c, H, kv, p, seed)     # noqa: E731
+    fn = lambda a, b, c: ops.attention._Attention.apply("full", a, b, c, H, kv, p, seed)     # noqa: E731
     got = _fwd_bwd(fn, q, k, v, do)
     ref = _ref64(q, k, v, do, H, kv, keep, p)
     if dtype == torch.float32:
@@ -123,7 +123,7 @@ def test_full_attention_dropout_mask_matches_numpy_hash(dev, dtype):
     # same seed: the same bits; another seed: another mask
     again = _fwd_bwd(fn, q, k, v, do)
     assert all(torch.equal(a, b) for a, b in zip(got, again))
-    other = _fwd_bwd(lambda a, b, c: ops.attention._FullAttention.apply(a, b, c, H, kv, p, seed + 1), q, k, v, do)
+    other = _fwd_bwd(lambda a, b, c: ops.attention._Attention.apply("full", a, b, c, H, kv, p, seed + 1), q, k, v, do)
     assert not torch.equal(got[0], other[0])
     # the public op draws its seed from torch's RNG, and only in training
     torch.manual_seed(7)
@@ -141,7 +141,7 @@ def test_full_attention_backward_is_deterministic(dev, dtype):
     B, L, H, D = 2, 257, 2, 64
     q, k, v, do = _inputs(dev, B, L, H, D, dtype, 9)
     kv = _mask("holes", B, L, dev)
-    fn = lambda a, b, c: ops.attention._FullAttention.apply(a, b, c, H, kv, 0.1, 99)     # noqa: E731
+    fn = lambda a, b, c: ops.attention._Attention.apply("full", a, b, c, H, kv, 0.1, 99)     # noqa: E731
     runs = [_fwd_bwd(fn, q, k, v, do) for _ in range(3)]
     assert all(torch.equal(a, b) for r in runs[1:] for a, b in zip(runs[0], r))
 

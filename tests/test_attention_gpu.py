@@ -234,7 +234,7 @@ def test_attention_dropout_mask_matches_numpy_hash(dev, dtype):
     # the keep fraction over all L x L elements: binomial, 6 sigma
     n, pk = keep.size, 1.0 - int(p * 65536) / 65536
     assert abs(keep.mean() - pk) <= 6 * np.sqrt(pk * (1 - pk) / n), keep.mean()
-    fn = lambda a, b, c: ops.attention._CausalAttention.apply(a, b, c, H, kv, p, seed)     # noqa: E731
+    fn = lambda a, b, c: ops.attention._Attention.apply("causal", a, b, c, H, kv, p, seed)     # noqa: E731
     got = _fwd_bwd(fn, q, k, v, do)
     ref = _fwd_bwd(lambda a, b, c: _ref_attention(a, b, c, H, kv, keep, p), q.double(), k.double(), v.double(), do.double())
     if dtype == torch.float32:
@@ -249,7 +249,7 @@ def test_attention_dropout_mask_matches_numpy_hash(dev, dtype):
     # same seed: the same bits; another seed: another mask
     again = _fwd_bwd(fn, q, k, v, do)
     assert all(torch.equal(a, b) for a, b in zip(got, again))
-    other = _fwd_bwd(lambda a, b, c: ops.attention._CausalAttention.apply(a, b, c, H, kv, p, seed + 1), q, k, v, do)
+    other = _fwd_bwd(lambda a, b, c: ops.attention._Attention.apply("causal", a, b, c, H, kv, p, seed + 1), q, k, v, do)
     assert not torch.equal(got[0], other[0])
 
 
@@ -296,7 +296,7 @@ def test_checkpointed_layer_sees_the_same_dropout_mask(dev):
 def test_attention_backward_is_deterministic(dev, dtype):
     from apertis_llm_amd import ops
     q, k, v, do, kv = _inputs(dev, 2, 2048, 2, 64, dtype, 9, True)
-    fn = lambda a, b, c: ops.attention._CausalAttention.apply(a, b, c, 2, kv, 0.1, 99)     # noqa: E731
+    fn = lambda a, b, c: ops.attention._Attention.apply("causal", a, b, c, 2, kv, 0.1, 99)     # noqa: E731
     r1, r2 = _fwd_bwd(fn, q, k, v, do), _fwd_bwd(fn, q, k, v, do)
     assert all(torch.equal(a, b) for a, b in zip(r1, r2))
 
