@@ -191,14 +191,33 @@ class _LazyCombine:
         return ops.moe_combine(self.yr, self.w, self.plan, out_dtype=self.dtype).reshape(self.shape)
 
 
+class _SsmLayerPast:
+    """One SSM layer's cache as the layer receives it: it reads like the (conv window, SSM state) pair and carries the step's
+    state.  `pre`: the layer's row of ApertisModel._decode_prepass (C s + D xc of this token step, the state already advanced)
+    or None; `inplace`: the single-token step may update the buffers it is handed (generate()'s graph tail)."""
+    __slots__ = ("conv", "state", "pre", "inplace")
+
+    def __init__(self, conv, state, pre=None, inplace=False):
+        self.conv, self.state, self.pre, self.inplace = conv, state, pre, inplace
+
+    def __len__(self):
+        return 2
+
+    def __getitem__(self, j):
+        return (self.conv, self.state)[j]
+
+    def __iter__(self):
+        return iter((self.conv, self.state))
+
+
 class _StackedPast(list):
     """generate()'s static cache of an all-SSM model as ONE tensor per kind - conv windows [NL,B,Dn,k-1], states [NL,B,Dn] fp32 -
-    with the usual per-layer (conv_state, ssm_state) tuples as views into them: the model then runs the cache-only half of a
-    token step for every layer at once (ApertisModel._decode_prepass)."""
+    with the usual per-layer (conv_state, ssm_state) pairs as views into them (_SsmLayerPast): the model then runs the
+    cache-only half of a token step for every layer at once (ApertisModel._decode_prepass)."""
 
-    def __init__(self, conv_all, state_all, heads, d_state):
+    def __init__(self, conv_all, state_all, heads, d_state, inplace=False):
         NL, B = conv_all.shape[0], conv_all.shape[1]
-        super().__init__((conv_all[l], state_all[l].view(B, heads, d_state)) for l in range(NL))
+        super().__init__(_SsmLayerPast(conv_all[l], state_all[l].view(B, heads, d_state), inplace=inplace) for l in range(NL))
         self.conv_all, self.state_all = conv_all, state_all
         self._offs = None
 
@@ -377,10 +396,7 @@ class SelectiveLinearAttention(nn.Module):
         self.A_log = nn.Parameter(torch.empty(self.num_heads, self.d_state).uniform_(math.log(0.5), math.log(0.99)))
         self.D = nn.Parameter(torch.ones(self.d_inner))
         self.out_proj = nn.Linear(self.d_inner, self.hidden_size, bias=False)
-        self.use_cache = False
         self._pad_idx = None
-        self._inplace_cache = False     # generate()'s graph replay: the single-token step updates the SSM state it is handed
-        self._decode_pre = None         # this layer's  C s + D xc  of the current token step, when the model ran it ahead
 
     def _pad_index(self, device):
         """Destination row of every row of x_param_proj.weight ([dt | Bt | C]) in the padded layout [Bt | 0 | C | 0 | dt | 0]."""
@@ -418,82 +434,94 @@ class SelectiveLinearAttention(nn.Module):
         return torch.cat([w[R:R + Dn], zb, w[R + Dn:], zb, w[:R], zr], dim=0), Wb, Wr
 
     def _stacked_in_proj(self):
-        """in_proj_x | in_proj_z as one [2 Dn, H] weight (core.py:366-367 share their input): prepared per step / per generate()."""
+        """in_proj_x | in_proj_z as one [2 Dn, H] weight (core.py:366-367 share their input: one GEMM, the outputs are column views).
+        Under no_grad - generate() - it is prepared once, not per token; inside a training step it comes prepared (ops.TrainPrep:
+        one launch per step for the whole model) and is a placeholder that carries shape and gradient route only."""
         w_xz = ops.prepared_weight(("in_proj_xz", id(self)), (self.in_proj_x.weight, self.in_proj_z.weight))
         if w_xz is None:
             w_xz = ops.cached_prep("in_proj_xz", (self.in_proj_x.weight, self.in_proj_z.weight),
                                    lambda: torch.cat([self.in_proj_x.weight, self.in_proj_z.weight], dim=0))
         return w_xz
 
+    def _param_weight(self):
+        """(_padded_param_weight's weight, Wb, Wr), prepared per step / per generate() like the stacked in_proj."""
+        wp = ops.prepared_weight(("x_param_padded", id(self)), (self.x_param_proj.weight,))
+        if wp is not None:
+            return wp, -(-self.d_inner // 64) * 64, -(-self.dt_rank // 64) * 64
+        return ops.cached_prep("x_param_padded", (self.x_param_proj.weight,), self._padded_param_weight)
+
+    def _have_window(self, conv_prev, use_cache):
+        return conv_prev is not None and use_cache and conv_prev.shape[1] == self.d_inner and conv_prev.shape[2] == self.conv_kernel_size - 1
+
+    def _token_step_ok(self, h, conv_prev, ssm_prev, use_cache, output_attentions):
+        """Whether this call is a single-token step on the caches (generate(), core.py:1578-1603): inference on the GPU."""
+        return (h.shape[1] == 1 and self._have_window(conv_prev, use_cache) and ssm_prev is not None and not output_attentions
+                and not torch.is_grad_enabled() and h.is_cuda and self.conv_kernel_size > 1)
+
     def decode_finish(self, gated, past_key_value):
-        """out_proj of a single-token step whose gate already ran (ops.decode_inproj's epilogue; `_decode_pre` is consumed)."""
-        self._decode_pre = None
-        B = gated.shape[0]
+        """out_proj of a single-token step whose gate already ran (ops.decode_inproj's epilogue)."""
         out = ops.decode_dense_gemv(gated, self.out_proj.weight, self.out_proj.bias)
         if out is None:
-            out = _mfma_linear(gated.reshape(B, 1, self.d_inner), self.out_proj.weight, self.out_proj.bias)
-        return out.reshape(B, 1, -1), None, tuple(past_key_value)
+            out = _mfma_linear(gated.reshape(-1, 1, self.d_inner), self.out_proj.weight, self.out_proj.bias)
+        return out.reshape(gated.shape[0], 1, -1), None, tuple(past_key_value)
 
     @_on_input_device
     def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None,
                 output_attentions: bool = False, use_cache: bool = False):
-        self.use_cache = use_cache
-        B, L, _ = hidden_states.shape
-        Dn, R, kw = self.d_inner, self.dt_rank, self.conv_kernel_size
-        conv_prev = ssm_prev = None
-        if past_key_value is not None:
-            conv_prev, ssm_prev = past_key_value
-        have_window = (conv_prev is not None and use_cache and conv_prev.shape[1] == Dn and conv_prev.shape[2] == kw - 1)
-        # in_proj_x and in_proj_z share their input: one GEMM with the stacked weight, outputs are
-        # column views (core.py:366-367)
-        # (under no_grad - generate() - the stacked and the padded weight are prepared once, not per token)
-        # (inside a training step the stacked and the padded weight come prepared - ops.TrainPrep: one launch per step for the
-        # whole model - and these are placeholders that carry shape and gradient route only)
-        if (self._decode_pre is not None and L == 1 and have_window and hidden_states.is_cuda and hidden_states.dtype == torch.bfloat16
-                and not torch.is_grad_enabled() and not output_attentions):
-            # single-token step whose cache-only half ran ahead (ApertisModel._decode_prepass): in_proj with the gate and the window
-            # push in its epilogue - xz is never written
-            gated = ops.decode_inproj(self._stacked_in_proj(), self._decode_pre, conv_prev, xn=hidden_states)
-            if gated is not None:
-                return self.decode_finish(gated, past_key_value)
-        xz = _mfma_linear(hidden_states, self._stacked_in_proj())
-        if self._decode_pre is not None and not (L == 1 and have_window and ssm_prev is not None and not output_attentions
-                                                  and not torch.is_grad_enabled() and hidden_states.is_cuda and kw > 1):
-            self._decode_pre = None
+        conv_prev, ssm_prev = past_key_value if past_key_value is not None else (None, None)
+        pre = getattr(past_key_value, "pre", None)
+        if self._token_step_ok(hidden_states, conv_prev, ssm_prev, use_cache, output_attentions):
+            return (self._token_step if pre is None else self._prepass_step)(hidden_states, past_key_value)
+        if pre is not None:
             raise ops.ApertisHipError("SelectiveLinearAttention: the model ran this step's cache-only half ahead (_decode_prepass: the "
                                       "SSM state is already updated) but the layer is not on its single-token path")
-        Wb, Wr = -(-Dn // 64) * 64, -(-R // 64) * 64
-        wp = ops.prepared_weight(("x_param_padded", id(self)), (self.x_param_proj.weight,))
-        if wp is None:
-            wp, Wb, Wr = ops.cached_prep("x_param_padded", (self.x_param_proj.weight,), self._padded_param_weight)
-        if (L == 1 and have_window and ssm_prev is not None and not output_attentions and not torch.is_grad_enabled()
-                and hidden_states.is_cuda and kw > 1):
-            # single-token decode step (generate(), core.py:1578-1603): two small kernels around the projections
-            # instead of the chunk machinery
-            xz2 = xz.reshape(B, 2 * Dn)
-            pre, self._decode_pre = self._decode_pre, None
-            if pre is not None:
-                # the step's first half - conv, x_param_proj, dt, state update: functions of the caches alone - ran for every
-                # layer at the start of the token step (ApertisModel._decode_prepass); the gate and the window push are left
-                gated = ops.decode_post(pre, xz2, conv_prev)
-                out = _mfma_linear(gated.reshape(B, 1, Dn), self.out_proj.weight, self.out_proj.bias)
-                return out, None, (conv_prev, ssm_prev)
-            xc, conv_state = ops.ssm_decode_step(xz2[:, :Dn], conv_prev, self.conv1d.weight, self.conv1d.bias,
-                                                 inplace=self._inplace_cache)
-            p = _mfma_linear(xc, wp)                                                   # [B, 2*Wb + Wr]
-            dt_in = p[:, 2 * Wb:2 * Wb + R]
-            state = ssm_prev.reshape(B, Dn).float()
-            if not (self._inplace_cache and state.data_ptr() == ssm_prev.data_ptr()):
-                state = state.clone()            # (the captured decode graph owns its cache buffers and updates them in place)
-            if ops.tiny_linear_supported(dt_in, R, self.num_heads):
-                # dt_proj_head inside the state kernel (one launch less per layer of a token step; the same bits)
-                gated = ops.ssm_decode_state_dt(dt_in, self.dt_proj_head.weight, self.dt_proj_head.bias, self.A_log, p[:, :Dn],
-                                                p[:, Wb:Wb + Dn], xc, xz2[:, Dn:], self.D, state)
-            else:
-                dt_logits = self.dt_proj_head(dt_in).float()
-                gated = ops.ssm_decode_state(dt_logits, self.A_log, p[:, :Dn], p[:, Wb:Wb + Dn], xc, xz2[:, Dn:], self.D, state)
-            out = _mfma_linear(gated.reshape(B, 1, Dn), self.out_proj.weight)
-            return out, None, (conv_state, state.reshape(B, self.num_heads, self.d_state))
+        return self._sequence(hidden_states, attention_mask, conv_prev, ssm_prev, output_attentions, use_cache)
+
+    def _prepass_step(self, hidden_states, past):
+        """Single-token step whose first half - conv, x_param_proj, dt, state update: functions of the caches alone - ran for every
+        layer at the start of the token step (ApertisModel._decode_prepass; `past.pre`): the gate and the window push are left."""
+        B, Dn = hidden_states.shape[0], self.d_inner
+        if hidden_states.dtype == torch.bfloat16:
+            # in_proj with the gate and the window push in its epilogue - xz is never written
+            gated = ops.decode_inproj(self._stacked_in_proj(), past.pre, past.conv, xn=hidden_states)
+            if gated is not None:
+                return self.decode_finish(gated, past)
+        xz = _mfma_linear(hidden_states, self._stacked_in_proj())
+        self._param_weight()    # (not read here: prepared at the same point of the step as in _token_step, so a cold cache fills alike)
+        gated = ops.decode_post(past.pre, xz.reshape(B, 2 * Dn), past.conv)
+        out = _mfma_linear(gated.reshape(B, 1, Dn), self.out_proj.weight, self.out_proj.bias)
+        return out, None, tuple(past)
+
+    def _token_step(self, hidden_states, past):
+        """Single-token decode step (generate(), core.py:1578-1603): two small kernels around the projections instead of the
+        chunk machinery.  A _SsmLayerPast says whether the buffers it holds may be updated in place; a plain tuple's may not."""
+        B, Dn, R = hidden_states.shape[0], self.d_inner, self.dt_rank
+        conv_prev, ssm_prev = past
+        inplace = getattr(past, "inplace", False)
+        xz2 = _mfma_linear(hidden_states, self._stacked_in_proj()).reshape(B, 2 * Dn)
+        wp, Wb, Wr = self._param_weight()
+        xc, conv_state = ops.ssm_decode_step(xz2[:, :Dn], conv_prev, self.conv1d.weight, self.conv1d.bias, inplace=inplace)
+        p = _mfma_linear(xc, wp)                                                   # [B, 2*Wb + Wr]
+        dt_in = p[:, 2 * Wb:2 * Wb + R]
+        state = ssm_prev.reshape(B, Dn).float()
+        if not (inplace and state.data_ptr() == ssm_prev.data_ptr()):
+            state = state.clone()            # (the captured decode graph owns its cache buffers and updates them in place)
+        if ops.tiny_linear_supported(dt_in, R, self.num_heads):
+            # dt_proj_head inside the state kernel (one launch less per layer of a token step; the same bits)
+            gated = ops.ssm_decode_state_dt(dt_in, self.dt_proj_head.weight, self.dt_proj_head.bias, self.A_log, p[:, :Dn],
+                                            p[:, Wb:Wb + Dn], xc, xz2[:, Dn:], self.D, state)
+        else:
+            gated = ops.ssm_decode_state(self.dt_proj_head(dt_in).float(), self.A_log, p[:, :Dn], p[:, Wb:Wb + Dn], xc, xz2[:, Dn:], self.D, state)
+        out = _mfma_linear(gated.reshape(B, 1, Dn), self.out_proj.weight)
+        return out, None, (conv_state, state.reshape(B, self.num_heads, self.d_state))
+
+    def _sequence(self, hidden_states, attention_mask, conv_prev, ssm_prev, output_attentions, use_cache):
+        """Training, prefill and multi-token steps on a cache: the conv over the whole sequence and the chunked scan."""
+        B, L, _ = hidden_states.shape
+        Dn, R, kw = self.d_inner, self.dt_rank, self.conv_kernel_size
+        have_window = self._have_window(conv_prev, use_cache)
+        xz = _mfma_linear(hidden_states, self._stacked_in_proj())
+        wp, Wb, Wr = self._param_weight()
         xp, z = ops.split_cols(xz, (Dn, Dn))
         conv_in = xp
         if have_window:
@@ -778,17 +806,16 @@ class ApertisAttention(nn.Module):
             self.rope = RotaryEmbedding(config.hidden_size, config.max_position_embeddings, config.rope_theta)
 
     def _decode_entry(self, h, past_kv, use_c, output_att):
-        """A single-token step whose cache-only half ran ahead (the SSM module's `_decode_pre` is set): the block boundary as the
+        """A single-token step whose cache-only half ran ahead (`past_kv.pre` of a _SsmLayerPast is set): the block boundary as the
         prologue of the in_proj product (ops.decode_inproj with `boundary`), whose epilogue gates and pushes the window.  None: the general path."""
-        impl = self.attention_mechanism_impl
-        if (impl._decode_pre is None or not isinstance(h, _Pending) or past_kv is None or not use_c or output_att
+        impl, pre = self.attention_mechanism_impl, getattr(past_kv, "pre", None)
+        if (pre is None or not isinstance(h, _Pending) or not use_c or output_att
                 or not isinstance(self.pre_norm, HipLayerNorm) or torch.is_grad_enabled() or self.training):
             return None
         out, res = h.out, h.res
-        if res.shape[1] != 1 or not res.is_cuda:
+        if res.shape[1] != 1 or not res.is_cuda or res.shape[0] > 4 or past_kv.conv.dim() != 3:
             return None
         lazy = out if isinstance(out, _LazyCombine) else None
-        conv_prev = past_kv[0]
         if lazy is not None:
             if not (lazy.yr.dtype == torch.bfloat16 == lazy.dtype):
                 return None
@@ -797,13 +824,8 @@ class ApertisAttention(nn.Module):
             bnd = (out, res, self.pre_norm.weight, self.pre_norm.bias, self.pre_norm.eps, None)
         else:
             return None
-        if res.shape[0] > 4 or conv_prev.dim() != 3:
-            return None
-        r = ops.decode_inproj(impl._stacked_in_proj(), impl._decode_pre, conv_prev, boundary=bnd)
-        if r is None:
-            return None
-        y, gated = r
-        return y, impl.decode_finish(gated, past_kv)
+        r = ops.decode_inproj(impl._stacked_in_proj(), pre, past_kv.conv, boundary=bnd)          # (y, gated), or None
+        return None if r is None else (r[0], impl.decode_finish(r[1], past_kv))
 
     def _fused_ok(self, q, att_mask, past_kv, output_att):
         """Whether this call takes the HIP RoPE + causal attention kernels: on the GPU, fp32 or bf16, D 64 or 128, no KV cache
@@ -919,13 +941,11 @@ class ApertisAttention(nn.Module):
     def forward(self, hidden_s, att_mask=None, pos_ids=None, past_kv=None, output_att=False, use_c=False, defer=False):
         """hidden_s: the residual stream, or the previous sub-block's _Pending output (its residual add is then
         folded into this block's pre-norm).  defer=True returns this block's output as a _Pending too."""
-        fused = self._decode_entry(hidden_s, past_kv, use_c, output_att) if self._ssm else None
-        if fused is not None:
-            hidden_s, (out, proxy, cache) = fused
-        else:
+        entry = self._decode_entry(hidden_s, past_kv, use_c, output_att) if self._ssm else None
+        if entry is None:
             x, hidden_s = _enter_block(self.pre_norm, hidden_s)
-        if fused is not None:
-            pass
+        if entry is not None:
+            hidden_s, (out, proxy, cache) = entry
         elif self._ssm:
             out, proxy, cache = self.attention_mechanism_impl(x, attention_mask=att_mask, position_ids=pos_ids,
                                                               past_key_value=past_kv, output_attentions=output_att,
@@ -1052,54 +1072,46 @@ class ApertisFeedForward(nn.Module):
                 return out.reshape(*x.shape[:-1], lin2.weight.shape[0])
         return self.ffn(x)
 
+    def _small_entry(self, h, defer):
+        """A handful of rows under no_grad (the single-token decode step, core.py:1578-1603): the block boundary, the router, the
+        gate, the dispatch plan and the per-expert LayerNorm as ONE launch (ops.moe_enter_small), then the two expert GEMMs.
+        Returns (output or its _LazyCombine, residual stream); None when that kernel does not take the shapes / modes (general path)."""
+        f = self.ffn
+        if not (isinstance(h, _Pending) and not isinstance(h.out, _LazyCombine) and not self.training and not f.training
+                and isinstance(self.pre_norm, HipLayerNorm) and isinstance(f.router_norm, nn.LayerNorm)
+                and h.res.is_cuda and _compute_dtype(h.res) == h.out.dtype
+                and ops.moe_enter_small_supported(h.out, h.res, f.num_experts, f.experts_per_token)):
+            return None
+        y, _logits, w, plan, xg = ops.moe_enter_small(h.out, h.res, self.pre_norm.weight, self.pre_norm.bias, self.pre_norm.eps,
+                                                      f.router_norm.weight, f.router_norm.bias, f.router_norm.eps, f.router.weight,
+                                                      f.router.bias, f.expert_ln_weight, f.expert_ln_bias, f.config.layer_norm_eps,
+                                                      f.experts_per_token)
+        yr = ops.expert_mlp(xg, f.expert_w1, f.expert_b1, f.expert_w2, f.expert_b2, plan.offsets, plan.max_rows, act=f.activation,
+                            drop_p=0.0, seed=0, compute_dtype=h.out.dtype)
+        out = _LazyCombine(yr, w, plan, tuple(h.res.shape), h.out.dtype)
+        if not defer or os.environ.get("APERTIS_NO_LAZY_COMBINE"):
+            out = out.materialise()
+        return out, y
+
     def forward(self, hidden_s, defer=False):
-        router = None
+        router = small = None
         if self.is_expert_system and self.ffn.router is not None and self.ffn.num_experts > 0:
             router = (self.ffn.router_norm, self.ffn.router)
             small = self._small_entry(hidden_s, defer)
-            if small is not None:
-                return small
-        x, hidden_s = _enter_block(self.pre_norm, hidden_s, router=router)
-        if self.is_expert_system:
-            out, lb, rz = self.ffn(x, lazy_combine=defer and not os.environ.get("APERTIS_NO_LAZY_COMBINE"),
-                                   aux_dtype=hidden_s.dtype)
-        else:
-            out = self._dense_ffn(x)
+        if small is not None:
+            out, hidden_s = small
             lb = rz = _zero_scalar(hidden_s.device, hidden_s.dtype)
+        else:
+            x, hidden_s = _enter_block(self.pre_norm, hidden_s, router=router)
+            if self.is_expert_system:
+                out, lb, rz = self.ffn(x, lazy_combine=defer and not os.environ.get("APERTIS_NO_LAZY_COMBINE"),
+                                       aux_dtype=hidden_s.dtype)
+            else:
+                out = self._dense_ffn(x)
+                lb = rz = _zero_scalar(hidden_s.device, hidden_s.dtype)
         if defer:
             return _Pending(out, hidden_s, self.output_dropout), lb, rz
         return _dropout_add(self.output_dropout, out, hidden_s), lb, rz
-
-
-def _ffn_small_entry(self, h, defer):
-    """A handful of rows under no_grad (the single-token decode step, core.py:1578-1603): the block boundary, the router, the
-    gate, the dispatch plan and the per-expert LayerNorm as ONE launch (ops.moe_enter_small), then the two expert GEMMs.
-    None when the shapes / modes are not the ones that kernel takes (the general path runs then)."""
-    f = self.ffn
-    if not (isinstance(h, _Pending) and not isinstance(h.out, _LazyCombine) and not self.training and not f.training
-            and isinstance(self.pre_norm, HipLayerNorm) and isinstance(f.router_norm, nn.LayerNorm)
-            and h.res.is_cuda and _compute_dtype(h.res) == h.out.dtype
-            and ops.moe_enter_small_supported(h.out, h.res, f.num_experts, f.experts_per_token)):
-        return None
-    B, L, H = h.res.shape
-    cd = h.out.dtype
-    y, _logits, w, plan, xg = ops.moe_enter_small(h.out, h.res, self.pre_norm.weight, self.pre_norm.bias, self.pre_norm.eps,
-                                                  f.router_norm.weight, f.router_norm.bias, f.router_norm.eps, f.router.weight,
-                                                  f.router.bias, f.expert_ln_weight, f.expert_ln_bias, f.config.layer_norm_eps,
-                                                  f.experts_per_token)
-    yr = ops.expert_mlp(xg, f.expert_w1, f.expert_b1, f.expert_w2, f.expert_b2, plan.offsets, plan.max_rows, act=f.activation,
-                        drop_p=0.0, seed=0, compute_dtype=cd)
-    out = _LazyCombine(yr, w, plan, (B, L, H), cd)
-    zero = _zero_scalar(y.device, y.dtype)
-    if defer and not os.environ.get("APERTIS_NO_LAZY_COMBINE"):
-        return _Pending(out, y, self.output_dropout), zero, zero
-    out = out.materialise()
-    if defer:
-        return _Pending(out, y, self.output_dropout), zero, zero
-    return _dropout_add(self.output_dropout, out, y), zero, zero
-
-
-ApertisFeedForward._small_entry = _ffn_small_entry
 
 
 class _AttnMask:
@@ -1398,36 +1410,28 @@ class ApertisModel(nn.Module):
 
         all_hs, all_att, all_cache = [], [], []
         lbs, rzs = [], []
-        pre_all = None
-        if isinstance(past_key_values, _StackedPast) and x.shape[1] == 1 and use_c and not out_att and not torch.is_grad_enabled():
-            pre_all = self._decode_prepass(past_key_values)
-        try:
-            for i, layer in enumerate(self.layers):
-                if out_hs:
-                    all_hs.append(x)
-                past = past_key_values[i] if past_key_values and i < len(past_key_values) else None
-                if pre_all is not None:
-                    layer.attention.attention_mechanism_impl._decode_pre = pre_all[i]
-                if self.gradient_checkpointing and self.training and not use_c:             # core.py:1258
-                    x, att_w, cache, lb, rz = torch.utils.checkpoint.checkpoint(layer, x, mask, pos_layers, past, out_att,
-                                                                                use_c, use_reentrant=False)
-                else:
-                    # hidden states are only materialised at layer boundaries when somebody asked for them
-                    x, att_w, cache, lb, rz = layer(x, mask, pos_layers, past, out_att, use_c, defer=not out_hs)
-                if out_att:
-                    all_att.append(att_w)
-                if use_c:
-                    all_cache.append(cache)
-                if cfg.use_expert_system:
-                    lbs.append(lb)
-                    rzs.append(rz)
-        finally:
-            #  the pre-pass has advanced every layer's SSM state in place; its per-layer results travel through the
-            # module attribute _decode_pre.  A layer that raised or left its single-token path must not leave a stale tensor
-            # behind for the next, unrelated forward on that module: whatever happened above, nothing stays pending.
+        prepass = isinstance(past_key_values, _StackedPast) and x.shape[1] == 1 and use_c and not out_att and not torch.is_grad_enabled()
+        pre_all = self._decode_prepass(past_key_values) if prepass else None
+        for i, layer in enumerate(self.layers):
+            if out_hs:
+                all_hs.append(x)
+            past = past_key_values[i] if past_key_values and i < len(past_key_values) else None
             if pre_all is not None:
-                for layer in self.layers:
-                    layer.attention.attention_mechanism_impl._decode_pre = None
+                # (the pre-pass has advanced every state in place: its row rides on a view made for this call, so none can go stale)
+                past = _SsmLayerPast(past.conv, past.state, pre_all[i], past.inplace)
+            if self.gradient_checkpointing and self.training and not use_c:             # core.py:1258
+                x, att_w, cache, lb, rz = torch.utils.checkpoint.checkpoint(layer, x, mask, pos_layers, past, out_att,
+                                                                            use_c, use_reentrant=False)
+            else:
+                # hidden states are only materialised at layer boundaries when somebody asked for them
+                x, att_w, cache, lb, rz = layer(x, mask, pos_layers, past, out_att, use_c, defer=not out_hs)
+            if out_att:
+                all_att.append(att_w)
+            if use_c:
+                all_cache.append(cache)
+            if cfg.use_expert_system:
+                lbs.append(lb)
+                rzs.append(rz)
         x, _ = _enter_block(self.final_post_norm, x)
         if out_hs:
             all_hs.append(x)
@@ -1889,22 +1893,20 @@ class ApertisForCausalLM(nn.Module):
         off = tokens.shape[1] - prompt_len                      # (steps already decoded: the draw counter goes on from there)
         if sampler is not None:
             state += [t for t in (sampler.counts, sampler.err) if t is not None]
-        ssm_blocks, start, cap, err_word = [], 0, 0, None
+        start, cap, err_word = 0, 0, None
         if cache is None:
             # (contiguous copies: the prefill hands the conv window over as a transposed view, and a cache that is not contiguous
-            #  is copied in and out of every token step instead of being updated in place - two launches per layer)
-            s_past = [(c.clone(memory_format=torch.contiguous_format), st.clone(memory_format=torch.contiguous_format)) for (c, st) in past]
+            #  is copied in and out of every token step instead of being updated in place - two launches per layer: `inplace`)
+            s_past = [_SsmLayerPast(c.clone(memory_format=torch.contiguous_format), st.clone(memory_format=torch.contiguous_format),
+                                    inplace=True) for (c, st) in past]
             if (DECODE_PREPASS and len(s_past) > 0 and all(c.dim() == 3 and st.dim() == 3 and st.dtype == torch.float32 and
                                                            c.shape == s_past[0][0].shape and st.shape == s_past[0][1].shape
                                                            and c.dtype == s_past[0][0].dtype for c, st in s_past)):
                 # one tensor per kind, the per-layer caches as views: the cache-only half of every layer's step runs at once
                 conv_all = torch.stack([c for c, _ in s_past]).contiguous()
                 state_all = torch.stack([st.reshape(st.shape[0], -1) for _, st in s_past]).contiguous()
-                s_past = _StackedPast(conv_all, state_all, s_past[0][1].shape[1], s_past[0][1].shape[2])
+                s_past = _StackedPast(conv_all, state_all, s_past[0][1].shape[1], s_past[0][1].shape[2], inplace=True)
             state += [t for pair in s_past for t in pair]
-            ssm_blocks = [m for m in self.modules() if isinstance(m, SelectiveLinearAttention)]
-            for m in ssm_blocks:
-                m._inplace_cache = True
         else:
             s_past, start, cap = cache, cache.length, cache.capacity
             # one split count for the whole tail, from the length it ends at (which end to size for)
@@ -1932,7 +1934,7 @@ class ApertisForCausalLM(nn.Module):
                 cache.dev_len.add_(1)
             else:
                 for (sc, ss), (nc, ns) in zip(s_past, out[4]):
-                    if nc.data_ptr() != sc.data_ptr():     # (both updated in place by the step: _inplace_cache)
+                    if nc.data_ptr() != sc.data_ptr():     # (both updated in place by the step: the views say `inplace`)
                         sc.copy_(nc)
                     if ns.data_ptr() != ss.data_ptr():
                         ss.copy_(ns)
@@ -1944,8 +1946,6 @@ class ApertisForCausalLM(nn.Module):
             kept = out.shape[1] - tokens.shape[1]
             return out
         finally:
-            for m in ssm_blocks:
-                m._inplace_cache = False
             if cache is not None:
                 cache.step_state_end(start + kept)       # (the replay may have run up to 15 steps past the last token kept)
 

@@ -948,3 +948,131 @@ def test_decode_prepass_runs_the_cache_only_half_of_every_layer_at_once(dev, exp
         assert torch.equal(a, b), float((a - b).abs().max())
     for (c0, s0), (c1, s1) in zip(cache0, cache1):
         assert torch.equal(c0.reshape(c1.shape), c1) and torch.equal(s0.reshape(s1.shape), s1)
+
+
+# ---- the token step's state rides with the cache (model._SsmLayerPast), not with the modules --------------------------------
+def _step_model(dev, experts=0, hidden=128, heads=4):
+    """Two selective_ssm layers, vocabulary 131, eval: the smallest model that has a layer behind a block boundary."""
+    import apertis_llm_amd as A
+    torch.manual_seed(17)
+    cfg = A.ApertisConfig(vocab_size=131, hidden_size=hidden, num_hidden_layers=2, num_attention_heads=heads, intermediate_size=2 * hidden,
+                          attention_type="selective_ssm", use_expert_system=experts > 0, num_experts=max(experts, 1),
+                          experts_per_token=2 if experts else 1, pad_token_id=0)
+    return A.ApertisForCausalLM(cfg).to(dev).eval()
+
+
+def _step_prefill(model, batch, dev, stacked=False):
+    """(caches, next token) after a 6-token prompt: contiguous plain (conv, state) tuples, or the same in a _StackedPast."""
+    from apertis_llm_amd import model as M
+    torch.manual_seed(23)
+    o = model(input_ids=torch.randint(4, 131, (batch, 6), device=dev), use_cache=True)
+    past = [(c.clone(memory_format=torch.contiguous_format), st.clone()) for c, st in o[4]]
+    if stacked:
+        past = M._StackedPast(torch.stack([c for c, _ in past]).contiguous(),
+                              torch.stack([st.reshape(batch, -1) for _, st in past]).contiguous(), past[0][1].shape[1], past[0][1].shape[2])
+    return past, o[1][:, -1].argmax(-1, keepdim=True)
+
+
+class _EntryRecorder:
+    """Stands in front of the loaded library (_lib._lib): every entry point called goes into `names`, in order."""
+
+    def __init__(self, real, names):
+        self._real, self._names = real, names
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+
+        def call(*args):
+            self._names.append(name)
+            return fn(*args)
+        return call
+
+
+_STEP_ENTRIES = {
+    "plain": ["apertis_layernorm_fwd", "apertis_grouped_gemm_nt", "apertis_ssm_decode_conv", "apertis_grouped_gemm_nt",
+              "apertis_ssm_decode_state_dt", "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd", "apertis_grouped_gemm_nt",
+              "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd", "apertis_grouped_gemm_nt", "apertis_ssm_decode_conv",
+              "apertis_grouped_gemm_nt", "apertis_ssm_decode_state_dt", "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd",
+              "apertis_grouped_gemm_nt", "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd"],
+    "stacked": ["apertis_decode_pre_conv", "apertis_grouped_gemm_nt", "apertis_decode_pre_state", "apertis_layernorm_fwd",
+                "apertis_grouped_gemm_nt", "apertis_decode_post", "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd",
+                "apertis_grouped_gemm_nt", "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd", "apertis_grouped_gemm_nt",
+                "apertis_decode_post", "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd", "apertis_grouped_gemm_nt",
+                "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd"],
+    "moe_bf16": ["apertis_decode_pre_conv", "apertis_grouped_gemm_nt", "apertis_decode_pre_state", "apertis_layernorm_fwd",
+                 "apertis_decode_inproj", "apertis_decode_dense_gemv", "apertis_moe_enter_small", "apertis_grouped_gemm_nt",
+                 "apertis_grouped_gemm_nt", "apertis_decode_inproj", "apertis_decode_dense_gemv", "apertis_moe_enter_small",
+                 "apertis_grouped_gemm_nt", "apertis_grouped_gemm_nt", "apertis_dropout_add_layernorm_fwd"],
+}
+
+
+@pytest.mark.parametrize("case,experts,bf16,batch,hidden,heads,stacked", [("plain", 0, False, 3, 128, 4, False), ("stacked", 0, False, 3, 128, 4, True),
+                                                                         ("moe_bf16", 8, True, 1, 704, 11, True)])
+def test_token_step_calls_the_library_entries_of_the_parent_in_order(dev, monkeypatch, case, experts, bf16, batch, hidden, heads, stacked):
+    """Every library entry point one single-token forward calls, in order (the second step after the prefill: prepared weights
+    are cached by then).  plain: the stand-alone step with dt inside the state kernel; stacked: the pre-pass and decode_post
+    (fp32 keeps it off decode_inproj); moe_bf16: decode_inproj on the normalised input (layer 0) and behind the boundary with a
+    lazy combine (layer 1), decode_finish and moe_enter_small.  The expected lists were not written from this code: they are what
+    this recorder printed, with the same seeds, on commit 147cf3a - the tree before the step state moved from attributes of
+    SelectiveLinearAttention into the cache views."""
+    import contextlib
+    from apertis_llm_amd import _lib, ops
+    model = _step_model(dev, experts, hidden, heads)
+    ac = (lambda: torch.autocast("cuda", dtype=torch.bfloat16)) if bf16 else contextlib.nullcontext
+    names = []
+    with torch.no_grad(), ac(), ops.prep_cache_scope():
+        past, tok = _step_prefill(model, batch, dev, stacked)
+        o = model(input_ids=tok, past_key_values=past, use_cache=True)
+        past, tok = (past if stacked else o[4]), o[1][:, -1].argmax(-1, keepdim=True)
+        with monkeypatch.context() as mp:
+            mp.setattr(_lib, "_lib", _EntryRecorder(_lib.load(), names))
+            model(input_ids=tok, past_key_values=past, use_cache=True)
+    torch.cuda.synchronize()
+    print(case, json.dumps(names))
+    assert names == _STEP_ENTRIES[case]
+
+
+def test_a_prepass_result_off_the_token_path_raises_and_keeps_nothing(dev):
+    """A layer that is handed a pre-pass result (the state is already advanced) but is not on its single-token path - here: two
+    positions - must refuse instead of applying the step twice, and nothing of the refused call stays behind: the next ordinary
+    token step gives the bits it gave before."""
+    from apertis_llm_amd import model as M, ops
+    model = _step_model(dev)
+    with torch.no_grad():
+        past, tok = _step_prefill(model, 3, dev)
+
+        def step():
+            o = model(input_ids=tok, past_key_values=[(c.clone(), st.clone()) for c, st in past], use_cache=True)
+            return [o[1]] + [t for pair in o[4] for t in pair]
+
+        before = step()
+        impl = model.model.layers[0].attention.attention_mechanism_impl
+        view = M._SsmLayerPast(past[0][0].clone(), past[0][1].clone(), pre=torch.zeros(3, impl.d_inner, device=dev))
+        with pytest.raises(ops.ApertisHipError, match="cache-only half"):
+            impl(torch.randn(3, 2, 128, device=dev), past_key_value=view, use_cache=True)
+        after = step()
+    assert len(before) == len(after) == 5 and all(torch.equal(a, b) for a, b in zip(before, after))
+
+
+def test_an_exception_in_the_layer_loop_of_a_prepass_step_leaves_no_trace(dev, monkeypatch):
+    """Layer 1 raises in a token step whose pre-pass has run for both layers: the exception propagates, and the model is as a
+    copy made before the call - an ordinary token step on fresh caches gives the same bits on both.  (The stacked buffers the
+    failed step advanced are the caller's; they are not used again.)"""
+    import copy
+    model = _step_model(dev)
+    twin = copy.deepcopy(model)
+    with torch.no_grad():
+        stacked, tok = _step_prefill(model, 3, dev, stacked=True)
+
+        def once(*a, **k):
+            raise RuntimeError("stop")
+        with monkeypatch.context() as mp:
+            mp.setitem(model.model.layers[1].__dict__, "forward", once)
+            with pytest.raises(RuntimeError, match="^stop$"):
+                model(input_ids=tok, past_key_values=stacked, use_cache=True)
+        past, tok = _step_prefill(model, 3, dev)
+        outs = []
+        for m in (model, twin):
+            o = m(input_ids=tok, past_key_values=[(c.clone(), st.clone()) for c, st in past], use_cache=True)
+            outs.append([o[1]] + [t for pair in o[4] for t in pair])
+    assert len(outs[0]) == 5 and all(torch.equal(a, b) for a, b in zip(*outs))
