@@ -234,6 +234,50 @@ tiny_linear_fwd_small_k(const TX *__restrict__ x, int64_t ldx, const float *__re
   y[i] = a;
 }
 
+// The dt logits of PACKED rows (ops.ssm.SSM_PACKED; rows are the tokens of [B, L], start = ops.document_layout's int32
+// [B, L]): tiny_linear_fwd_k, except that the row of a document's first token at t >= 1 (start[b, t] == t) receives `reset`
+// in every column instead of the projection - the scan then forms a = exp2(softplus(reset) * A2) = 0 there, which is the
+// state reset.  Such a row is not loaded.  Every other row: the chain above, the same bits.
+template <typename TX, bool VEC>
+__global__ void __launch_bounds__(TL_ROWS)
+tiny_linear_doc_fwd_k(const TX *__restrict__ x, int64_t ldx, const float *__restrict__ W, const float *__restrict__ b,
+                      const int32_t *__restrict__ start, float reset, float *__restrict__ y, int64_t T, int64_t L, int K, int N) {
+  __shared__ __attribute__((aligned(16))) float sW[TL_MAXN * TL_MAXK + TL_MAXN];
+  tl_stage_w(sW, W, K, N);
+  for (int i = threadIdx.x; i < N; i += TL_ROWS) sW[TL_MAXN * TL_MAXK + i] = b ? b[i] : 0.f;
+  __syncthreads();
+  const float4 *sW4 = reinterpret_cast<const float4 *>(sW);
+  for (int64_t t = (int64_t)blockIdx.x * TL_ROWS + threadIdx.x; t < T; t += (int64_t)gridDim.x * TL_ROWS) {
+    const int64_t tl = t % L;
+    if (tl > 0 && (int64_t)start[t] == tl) {
+      for (int j = 0; j < N; ++j) y[t * N + j] = reset;
+      continue;
+    }
+    float xr[TL_MAXK];
+    tl_load_row<TX, VEC>(x + t * ldx, K, xr);
+    for (int j = 0; j < N; ++j) {
+      float a = sW[TL_MAXN * TL_MAXK + j];
+#pragma unroll
+      for (int r4 = 0; r4 < TL_MAXK / 4; ++r4)
+        if (r4 * 4 < K) {    // the pad entries of the last chunk are zeros on both sides
+          const float4 w = sW4[j * (TL_MAXK / 4) + r4];
+          a = fmaf(xr[4 * r4], w.x, a); a = fmaf(xr[4 * r4 + 1], w.y, a);
+          a = fmaf(xr[4 * r4 + 2], w.z, a); a = fmaf(xr[4 * r4 + 3], w.w, a);
+        }
+      y[t * N + j] = a;
+    }
+  }
+}
+
+// ... and for logits that something else has formed (a dt projection the kernel above does not take): only the overwrite
+__global__ void __launch_bounds__(256)
+doc_reset_rows_k(const int32_t *__restrict__ start, float reset, float *__restrict__ y, int64_t T, int64_t L, int N) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < T * N; i += (int64_t)gridDim.x * 256) {
+    const int64_t t = i / N, tl = t % L;
+    if (tl > 0 && (int64_t)start[t] == tl) y[i] = reset;
+  }
+}
+
 // Backward.  dx per row (W four at a time from LDS, as above).  dW/db as per-block partial sums over the row tile
 // staged in LDS: thread p owns the 2 x 4 block dW[2*(p/16) + {0,1}][4*(p%16) + {0..3}] (and db of its two rows when
 // p%16 == 0) and reads one 8-byte dy pair and one 16-byte x chunk per row for eight FMAs; rows are walked in order and
@@ -402,6 +446,31 @@ extern "C" int apertis_tiny_linear_fwd(const void *x, int64_t ldx, const float *
   const int64_t esz = dtype_x == APERTIS_BF16 ? 2 : 4, epc = 16 / esz;
   const bool vec = (((uintptr_t)x) & 15) == 0 && (ldx * esz) % 16 == 0 && ceil_div64(K, epc) * epc <= ldx;
 #define GO(TX, V) hipLaunchKernelGGL((tiny_linear_fwd_k<TX, V>), grid, block, 0, st, (const TX *)x, ldx, W, b, y, T, (int)K, (int)N)
+  if (dtype_x == APERTIS_BF16) { if (vec) GO(bf16_t, true); else GO(bf16_t, false); }
+  else { if (vec) GO(float, true); else GO(float, false); }
+#undef GO
+  return apertis_check_launch();
+}
+
+extern "C" int apertis_tiny_linear_doc_fwd(const void *x, int64_t ldx, const float *W, const float *b, const int32_t *start,
+                                           float reset, float *y, int64_t T, int64_t L, int64_t K, int64_t N, int dtype_x,
+                                           void *stream) {
+  if (!start || !y || T < 0 || L < 1 || T % L || !(reset == reset) || N < 1) return APERTIS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (!x) {    // y holds the logits already: overwrite the rows of the document starts, nothing else
+    if (T == 0) return APERTIS_OK;
+    hipLaunchKernelGGL(doc_reset_rows_k, dim3((unsigned)std::min<int64_t>(ceil_div64(T * N, 256), 4096)), dim3(256), 0, st, start,
+                       reset, y, T, L, (int)std::min<int64_t>(N, 0x7fffffff));
+    return apertis_check_launch();
+  }
+  if (!W || ldx < K) return APERTIS_ERR_ARG;
+  if (K < 1 || K > TL_MAXK || N > TL_MAXN) return APERTIS_ERR_UNSUPPORTED;
+  if (dtype_x != APERTIS_BF16 && dtype_x != APERTIS_F32) return APERTIS_ERR_ARG;
+  if (T == 0) return APERTIS_OK;
+  dim3 grid((unsigned)std::min<int64_t>(ceil_div64(T, TL_ROWS), 4096)), block(TL_ROWS);
+  const int64_t esz = dtype_x == APERTIS_BF16 ? 2 : 4, epc = 16 / esz;
+  const bool vec = (((uintptr_t)x) & 15) == 0 && (ldx * esz) % 16 == 0 && ceil_div64(K, epc) * epc <= ldx;
+#define GO(TX, V) hipLaunchKernelGGL((tiny_linear_doc_fwd_k<TX, V>), grid, block, 0, st, (const TX *)x, ldx, W, b, start, reset, y, T, L, (int)K, (int)N)
   if (dtype_x == APERTIS_BF16) { if (vec) GO(bf16_t, true); else GO(bf16_t, false); }
   else { if (vec) GO(float, true); else GO(float, false); }
 #undef GO

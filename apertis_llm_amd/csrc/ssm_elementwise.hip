@@ -648,6 +648,244 @@ dwconv_silu_bwd_kn(const T *__restrict__ x, int64_t x_rs, const float *__restric
   }
 }
 
+// ---- PACKED rows (training under ops.ssm.SSM_PACKED): a batch row holds several documents, contiguous runs of tokens, and
+// token t of row b belongs to the document [start[b, t], end[b, t]) (int32 [B, L], ops.document_layout).  The conv stops at a
+// document's first token: a tap at t - j < start[b, t] reads as zero - what t - j < 0 is to the kernels above - so every
+// document gets what it gets in a row of its own.
+// Forward: dwconv_silu_start_k's geometry - a work-group takes (batch, 64 tokens, CB <= 64 four-channel chunks), thread (rg, p)
+// owns chunk p of rows rg, rg + RG, ..., the taps sit in LDS transposed to [k][CB], one form for every width 2..16 and every
+// Dn % 4 == 0 - with two differences.  The boundary is per token ROW, not a prefix of the batch row: the 64 starts of the tile
+// come into LDS and a row masks its own taps with a select in front of the multiply (the product with the zero is still
+// added, as the kernels above add the zeros they load in front of a sequence: bias + sum_q w[q] * x[t - (k-1) + q], q
+// ascending, rounded to the io dtype before SiLU, term for term - a document's outputs carry the bits the plain forward gives
+// it alone, and with one document per row they are the plain forward's).  And the tile holds the rows as stored (8 bytes per
+// chunk in bf16, not 16): this kernel runs in every layer of every training step, and at Dn = 176, k = 4 the fp32 tile's
+// 47 KiB would leave three work-groups per CU where the stored form's 24 KiB leaves six.
+template <typename T> struct Raw4;
+template <> struct Raw4<float> {
+  typedef float4 R;
+  __device__ static __forceinline__ R zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+  __device__ static __forceinline__ R load(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+  __device__ static __forceinline__ float4 f4(R v) { return v; }
+};
+template <> struct Raw4<bf16_t> {
+  typedef uint2 R;
+  __device__ static __forceinline__ R zero() { return make_uint2(0u, 0u); }
+  __device__ static __forceinline__ R load(const bf16_t *p) { return *reinterpret_cast<const uint2 *>(p); }
+  __device__ static __forceinline__ float4 f4(R u) {
+    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                       __uint_as_float(u.y & 0xffff0000u));
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+dwconv_silu_doc_fwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
+                      const int32_t *__restrict__ start, T *__restrict__ out, int64_t out_rs, int64_t L, int CPR, int k, int CB,
+                      int nchunks, int ncb) {
+  constexpr int TT = CONV_TILE_T;
+  typedef Raw4<T> RW;
+  typedef typename RW::R R;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float4 *taps = reinterpret_cast<float4 *>(smem);              // [k][CB]
+  R *tile = reinterpret_cast<R *>(taps + k * CB);               // [TT + k - 1][CB]; tile row j = token t0 - (k - 1) + j
+  int32_t *st = reinterpret_cast<int32_t *>(tile + (TT + k - 1) * CB);   // [TT]: taps of tile row r + q with q < st[r] are masked
+  const int tid = threadIdx.x;
+  const int cb = (int)(blockIdx.x % ncb);
+  const int64_t bt = blockIdx.x / ncb, b = bt / nchunks;
+  const int64_t t0 = (bt - b * nchunks) * TT;
+  const int rows = (int)min((int64_t)TT, L - t0);
+  const int c_lo = cb * CB, nc = min(CB, CPR - c_lo);
+  const T *xb = x + b * L * x_rs + c_lo * 4;
+  T *ob = out + (b * L + t0) * out_rs + c_lo * 4;
+  const int nrow = rows + k - 1;
+  for (int i = tid; i < nrow * nc; i += 256) {
+    const int r = i / nc, c = i - r * nc;
+    const int64_t t = t0 - (k - 1) + r;
+    tile[r * CB + c] = t >= 0 ? RW::load(xb + t * x_rs + c * 4) : RW::zero();
+  }
+  for (int i = tid; i < k * nc; i += 256) {
+    const int q = i / nc, c = i - q * nc;
+    const float *wc = w + (int64_t)(c_lo + c) * 4 * k + q;
+    taps[q * CB + c] = make_float4(wc[0], wc[k], wc[2 * k], wc[3 * k]);
+  }
+  // token t - (k-1) + q lies before the document iff q < start[b, t] - t + (k-1)   (<= k-1: a token is in its own document)
+  if (tid < rows) st[tid] = (int32_t)min((int64_t)start[b * L + t0 + tid] - (t0 + tid) + (k - 1), (int64_t)k);
+  __syncthreads();
+  const int rg = tid / CB, p = tid - rg * CB, RG = 256 / CB;
+  if (rg >= RG || p >= nc) return;
+  const float *bp = bias + (c_lo + p) * 4;
+  const float4 bv = make_float4(bp[0], bp[1], bp[2], bp[3]);
+  for (int r = rg; r < rows; r += RG) {
+    const int lim = st[r];
+    float acc[4] = {bv.x, bv.y, bv.z, bv.w};
+    for (int q = 0; q < k; ++q) {
+      float4 f = RW::f4(tile[(r + q) * CB + p]);
+      const float4 wq = taps[q * CB + p];
+      if (q < lim) f = make_float4(0.f, 0.f, 0.f, 0.f);
+      acc[0] += wq.x * f.x; acc[1] += wq.y * f.y; acc[2] += wq.z * f.z; acc[3] += wq.w * f.w;
+    }
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float sj = to_f32(from_f32<T>(acc[j]));  // conv output is stored in the activation dtype before SiLU
+      o[j] = siluf_(sj);
+    }
+    st4<T>(ob + (int64_t)r * out_rs + p * 4, make_float4(o[0], o[1], o[2], o[3]));
+  }
+}
+
+// Backward of the same: dwconv_silu_bwd_kn's walk (a thread owns four channels of a 16-token run, x window and dpre history in
+// registers, right-aligned KM-long arrays with the tap count k a runtime value; same grid, partial layout and order of every
+// sum) in two capacities, KM = 4 for the widths 2..4 and KM = 16 for 5..16.  pre is recomputed under the forward's predicate:
+// where the walk reaches a document's first token (start[b, t] == t) the window in front of it is zeroed - the tokens of one
+// document share their start, so the zeros hold until they leave the window - and the window a run begins with is masked by
+// the start of its first token.  Hence dw[c, q] sums pairs of one document only.  dx[t] = sum_q w[q] * dpre[t + (k-1) - q]
+// takes a dpre at t' >= end[b, t] as zero - the select sits in front of the multiply, as above - and db is what it was.
+// With one document per row every select passes exactly where the plain kernels read a value they loaded, so dx carries
+// their bits.  No atomics: per-block partials, folded in a fixed order by colsum_rows_k.
+template <typename T, int KM>
+__global__ void __launch_bounds__(256, KM == 4 ? 3 : 1)   // (KM = 4: the plain k = 4 kernel's three waves per SIMD - 168 VGPRs)
+dwconv_silu_doc_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
+                      const T *__restrict__ dout, int64_t dout_rs, const T *__restrict__ dout2, int64_t dout2_rs,
+                      const int32_t *__restrict__ start, const int32_t *__restrict__ end, T *__restrict__ dx, int64_t dx_rs,
+                      float *__restrict__ dw_part, float *__restrict__ db_part, int64_t B, int64_t L, int Dn, int k) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float *red = reinterpret_cast<float *>(smem);  // [RP][CPR][4*(k+2)]: per channel k tap sums, then the bias sum as (hi, lo)
+  const int off = KM - k, NA = 4 * (k + 2);
+  const Geo g = make_geo(Dn);
+  const int rr = threadIdx.x / g.CPR;
+  const bool on = rr < g.RP;
+  const int64_t runs_per_seq = ceil_div64(L, CONV_TT);
+  for (int c0 = 0; c0 < g.CPR; c0 += 256) {
+    const int c = c0 + (on ? threadIdx.x - rr * g.CPR : 0);
+    float accw[4][KM];
+    double accb[4];      // (fp64: db is one chain over every token of the batch, the longest sum of the kernel - see the fold below)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { accb[j] = 0.0;
+#pragma unroll
+      for (int m = 0; m < KM; ++m) accw[j][m] = 0.f; }
+    if (on && c < g.CPR) {
+      float wv[4][KM], bv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        bv[j] = bias[c * 4 + j];
+#pragma unroll
+        for (int m = 0; m < KM; ++m) wv[j][m] = m >= off ? w[(c * 4 + j) * k + (m - off)] : 0.f;
+      }
+      for (int64_t run = (int64_t)blockIdx.x * g.RP + rr; run < B * runs_per_seq; run += (int64_t)gridDim.x * g.RP) {
+        const int64_t b = run / runs_per_seq, t0 = (run - b * runs_per_seq) * CONV_TT;
+        const T *xb = x + b * L * x_rs + c * 4;
+        const T *gb = dout + b * L * dout_rs + c * 4;
+        const T *gb2 = dout2 ? dout2 + b * L * dout2_rs + c * 4 : nullptr;
+        const int32_t *sb = start + b * L, *eb = end + b * L;
+        T *dxb = dx + b * L * dx_rs + c * 4;
+        const int64_t t1 = min(t0 + CONV_TT, L), te = min(t1 + (k - 1), L);
+        // win[m] = x[t-(KM-1)+m] (zero in front of t's document), dp[m] = dpre[t-(KM-1)+m]; dpre is formed on [t0, te) - the
+        // next run's first k-1 tokens feed our dx - and taken as zero outside it
+        float win[KM][4], dp[KM][4];
+#pragma unroll
+        for (int m = 0; m < KM; ++m)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { win[m][j] = 0.f; dp[m][j] = 0.f; }
+        const int64_t s0 = max((int64_t)sb[t0], (int64_t)0);
+#pragma unroll
+        for (int m = 0; m < KM - 1; ++m) {
+          const int64_t tt = t0 - (KM - 1) + m;
+          if (m >= off && tt >= s0) { float4 v = ld4<T>(xb + tt * x_rs); win[m + 1][0] = v.x; win[m + 1][1] = v.y; win[m + 1][2] = v.z; win[m + 1][3] = v.w; }
+        }
+        for (int64_t t = t0; t < t1 + (KM - 1); ++t) {
+#pragma unroll
+          for (int m = 0; m < KM - 1; ++m)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { win[m][j] = win[m + 1][j]; dp[m][j] = dp[m + 1][j]; }
+          if (t < te) {
+            float4 v = ld4<T>(xb + t * x_rs), gv = ld4<T>(gb + t * dout_rs);
+            const bool first = (int64_t)sb[t] == t;       // a document begins here: nothing in front of it is its own
+            if (gb2) {
+              const float4 g2 = ld4<T>(gb2 + t * dout2_rs);
+              gv = make_float4(to_f32(from_f32<T>(gv.x + g2.x)), to_f32(from_f32<T>(gv.y + g2.y)), to_f32(from_f32<T>(gv.z + g2.z)),
+                               to_f32(from_f32<T>(gv.w + g2.w)));
+            }
+#pragma unroll
+            for (int m = 0; m < KM - 1; ++m)
+#pragma unroll
+              for (int j = 0; j < 4; ++j) win[m][j] = first ? 0.f : win[m][j];
+            win[KM - 1][0] = v.x; win[KM - 1][1] = v.y; win[KM - 1][2] = v.z; win[KM - 1][3] = v.w;
+            const float g_[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              float s = bv[j];
+#pragma unroll
+              for (int m = 0; m < KM; ++m)
+                if (m >= off) s += wv[j][m] * win[m][j];
+              s = to_f32(from_f32<T>(s));
+              float d = g_[j] * silu_grad(s);
+              dp[KM - 1][j] = d;
+              if (t < t1) {  // own tokens only: parameter gradients are not double counted
+                accb[j] += (double)d;
+#pragma unroll
+                for (int m = 0; m < KM; ++m)
+                  if (m >= off) accw[j][m] += d * win[m][j];
+              }
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { win[KM - 1][j] = 0.f; dp[KM - 1][j] = 0.f; }
+          }
+          const int64_t tp = t - (KM - 1);
+          if (tp >= t0) {  // (tp < t1 by the loop bound)
+            const int64_t lim = (int64_t)eb[tp] - tp;       // dp[m] is dpre[tp + m]: inside tp's document iff m < lim
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              float s = 0.f;
+#pragma unroll
+              for (int m = KM - 1; m >= 0; --m)  // q = k-1-m ascending, as in the plain kernels
+                if (m < k) s += wv[j][KM - 1 - m] * (m < lim ? dp[m][j] : 0.f);
+              o[j] = s;
+            }
+            st4<T>(dxb + tp * dx_rs, make_float4(o[0], o[1], o[2], o[3]));
+          }
+        }
+      }
+    }
+    const int cw = min(g.CPR, 256);
+    __syncthreads();
+    if (on && c < g.CPR) {
+      float *r = red + ((int64_t)rr * cw + (c - c0)) * NA;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float hi = (float)accb[j];
+        r[j * (k + 2) + k] = hi;
+        r[j * (k + 2) + k + 1] = (float)(accb[j] - (double)hi);
+#pragma unroll
+        for (int m = 0; m < KM; ++m)
+          if (m >= off) r[j * (k + 2) + (m - off)] = accw[j][m];
+      }
+    }
+    __syncthreads();
+    if (on && rr == 0 && c < g.CPR) {
+      for (int j = 0; j < 4; ++j) {
+        for (int q = 0; q <= k; ++q) {
+          // (the rows' partials meet in fp64, off the token walk, and db - whose chains were fp64 already - comes over as a
+          //  (hi, lo) pair: a packed row's dw then carries the rounding of the threads' own 16-token chains and one more, its
+          //  db one rounding, as the short documents' do when each is run alone and summed outside.  Measured against the
+          //  fp64 restatement at Dn = 4, L = 64, fp32: all-fp32 sums left db at 3.0e-6, the alone runs at 7.4e-7)
+          double s = 0.0;
+          for (int r = 0; r < g.RP; ++r) {
+            const float *e = red + ((int64_t)r * cw + (c - c0)) * NA + j * (k + 2);
+            s += q < k ? (double)e[q] : (double)e[k] + (double)e[k + 1];
+          }
+          if (q < k) dw_part[((int64_t)blockIdx.x * Dn + c * 4 + j) * k + q] = (float)s;
+          else db_part[(int64_t)blockIdx.x * Dn + c * 4 + j] = (float)s;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // out[c] = sum_r in[r][c], fixed order (16 row groups, four independent loads in flight)
 __global__ void __launch_bounds__(1024)
 colsum_rows_k(const float *__restrict__ in, float *__restrict__ out, int64_t rows, int64_t cols) {
@@ -978,6 +1216,50 @@ extern "C" int apertis_dwconv_silu_bwd(const void *x, int64_t x_rs, const float 
                                        void *stream) {
   return apertis_dwconv_silu_bwd2(x, x_rs, w, bias, dout, dout_rs, nullptr, 0, dx, dx_rs, dw_part, db_part, dw, db, B, L, Dn, k,
                                   dtype_io, stream);
+}
+
+extern "C" int apertis_dwconv_silu_doc_fwd(const void *x, int64_t x_rs, const float *w, const float *bias, const int32_t *start,
+                                           void *out, int64_t out_rs, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
+                                           void *stream) {
+  if (!x || !w || !bias || !start || !out || B < 0 || L < 0) return APERTIS_ERR_ARG;
+  if (dtype_io != APERTIS_F32 && dtype_io != APERTIS_BF16) return APERTIS_ERR_ARG;
+  if (!rows_ok(Dn) || (x_rs | out_rs) % 4 || x_rs < Dn || out_rs < Dn || k < 2 || k > CONV_KMAX || L >= 0x7fffffffLL)
+    return APERTIS_ERR_UNSUPPORTED;
+  const uintptr_t piece = dtype_io == APERTIS_BF16 ? 8 : 16;        // a thread moves four channels at a time
+  if ((uintptr_t)x % piece || (uintptr_t)out % piece) return APERTIS_ERR_UNSUPPORTED;
+  if (B == 0 || L == 0) return APERTIS_OK;
+  const int CPR = (int)(Dn / 4), CB = std::min(CPR, 64);
+  const int64_t nchunks = ceil_div64(L, CONV_TILE_T), ncb = ceil_div64(CPR, CB);
+  if (B * nchunks * ncb >= 0x7fffffffLL) return APERTIS_ERR_UNSUPPORTED;
+  // taps + tile as stored + the tile's starts: at most 16 + 79 KiB at k = 16, fp32; 27 KiB at k = 4, Dn = 176, bf16
+  const size_t lds = (size_t)k * CB * sizeof(float4) + (size_t)(CONV_TILE_T + k - 1) * CB * piece + CONV_TILE_T * sizeof(int32_t);
+  CONV_TYPES(dtype_io, launch_lds(dwconv_silu_doc_fwd_k<T>, dim3((unsigned)(B * nchunks * ncb)), dim3(256), lds, (hipStream_t)stream,
+                                  (const T *)x, x_rs, w, bias, start, (T *)out, out_rs, L, CPR, (int)k, CB, (int)nchunks, (int)ncb));
+  return apertis_check_launch();
+}
+
+extern "C" int apertis_dwconv_silu_doc_bwd(const void *x, int64_t x_rs, const float *w, const float *bias, const void *dout,
+                                           int64_t dout_rs, const void *dout2, int64_t dout2_rs, const int32_t *start,
+                                           const int32_t *end, void *dx, int64_t dx_rs, float *dw_part, float *db_part, float *dw,
+                                           float *db, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io, void *stream) {
+  if (!x || !w || !bias || !dout || !start || !end || !dx || !dw_part || !db_part || !dw || !db || B < 0 || L < 0) return APERTIS_ERR_ARG;
+  if (dtype_io != APERTIS_F32 && dtype_io != APERTIS_BF16) return APERTIS_ERR_ARG;
+  if (!dout2) dout2_rs = 0;
+  if (!rows_ok(Dn) || (x_rs | dout_rs | dout2_rs | dx_rs) % 4 || k < 2 || k > CONV_KMAX || L >= 0x7fffffffLL) return APERTIS_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = conv_blocks(B, L, Dn);
+  Geo g = make_geo(Dn);
+  const size_t lds = (size_t)g.RP * std::min(g.CPR, 256) * 4 * (k + 2) * sizeof(float);   // (up to 72 KiB at k = 16)
+  dim3 grid(nblk), block(256);
+#define DOC_BWD(KM_)                                                                                                          \
+  CONV_TYPES(dtype_io, launch_lds(dwconv_silu_doc_bwd_k<T, KM_>, grid, block, lds, st, (const T *)x, x_rs, w, bias, (const T *)dout, \
+                                  dout_rs, (const T *)dout2, dout2_rs, start, end, (T *)dx, dx_rs, dw_part, db_part, B, L, (int)Dn, (int)k))
+  if (k > 4) DOC_BWD(CONV_KMAX); else DOC_BWD(4);
+#undef DOC_BWD
+  hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn * k, 64)), dim3(1024), 0, st, dw_part, dw, (int64_t)nblk,
+                     Dn * k);
+  hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn, 64)), dim3(1024), 0, st, db_part, db, (int64_t)nblk, Dn);
+  return apertis_check_launch();
 }
 
 extern "C" int apertis_cast_transpose(const float *src, void *dst, void *dstT, int64_t E, int64_t R, int64_t C,

@@ -368,6 +368,15 @@ class _SsmStarts:
         self.start = start
 
 
+class _SsmDocs:
+    """What ApertisModel.forward hands the SSM layers in the mask slot for PACKED rows under ops.SSM_PACKED: `layout`, the
+    ops.DocumentLayout of the forward (computed once; a checkpointed layer is recomputed with the same object)."""
+    __slots__ = ("layout",)
+
+    def __init__(self, layout):
+        self.layout = layout
+
+
 class SelectiveLinearAttention(nn.Module):
     """in_proj_x/z -> depthwise causal conv + SiLU -> x_param_proj -> (dt feats, Bt, C) ->
     softplus(dt_proj_head) -> selective scan -> +D*x -> *SiLU(z) -> out_proj.
@@ -529,7 +538,18 @@ class SelectiveLinearAttention(nn.Module):
             # (core.py:369-373); reproduced as is so cached decode matches `apertis chat`
             conv_in = torch.cat([conv_prev.transpose(1, 2).to(xp.dtype), xp], dim=1)
         conv_state = conv_in[:, -(kw - 1):].transpose(1, 2).detach() if use_cache else None
-        if isinstance(attention_mask, _SsmStarts):
+        layout = attention_mask.layout if isinstance(attention_mask, _SsmDocs) else None
+        if layout is not None:
+            # packed rows under ops.SSM_PACKED (ApertisModel._packed_layout has the conditions): conv and scan - the two
+            # operations of this block that look across tokens - stop at the document boundaries; everything else is per token
+            if have_window or use_cache or ssm_prev is not None or output_attentions or not hidden_states.is_cuda:
+                raise ValueError("document_ids: a packed selective_ssm forward takes no cache, keeps none and returns no "
+                                 "attention weights (output_attentions), on a ROCm device")
+            if ops.DWCONV_PAIR:
+                xc_p, xc = ops.dwconv_silu_pair(conv_in, self.conv1d.weight, self.conv1d.bias, layout=layout)
+            else:
+                xc_p = xc = ops.dwconv_silu(conv_in, self.conv1d.weight, self.conv1d.bias, layout=layout)
+        elif isinstance(attention_mask, _SsmStarts):
             # left-padded prefill under ops.SSM_LEFT_PAD (ApertisModel._ssm_left_pad has the conditions: inference, no incoming
             # cache): a row's pads count as "before the sequence" - the conv output is exactly 0 there, x_param_proj has no
             # bias, so Bt = C = dt_in = 0 and the state every scan form carries stays at 0 up to the first real token
@@ -552,7 +572,7 @@ class SelectiveLinearAttention(nn.Module):
             # dt_proj_head, softplus, recurrence, skip and gate as ONE op (core.py:382-396): the logits come from the
             # stand-alone kernel or - APERTIS_SCAN_DT_FUSED=1 - from inside the scan's state pass (the same bits)
             res = ops.scan_gate_dt(dt_in, self.dt_proj_head.weight, self.dt_proj_head.bias, self.A_log, Btp, Cp, xc, z, self.D,
-                                   h0=h0, delta_softplus=True, return_last=use_cache)
+                                   h0=h0, delta_softplus=True, return_last=use_cache, layout=layout)
             (gated, h_last), y = (res if use_cache else (res, None)), None
             out = _mfma_linear(gated, self.out_proj.weight)                 # core.py:397
             cache = (conv_state, h_last.reshape(B, self.num_heads, self.d_state)) if use_cache else None
@@ -571,7 +591,7 @@ class SelectiveLinearAttention(nn.Module):
         else:
             # recurrence + skip + gate in one kernel per direction; y is never written (core.py:388-396)
             res = ops.scan_gate(dt_logits, self.A_log, Btp, Cp, xc, z, self.D, h0=h0, delta_softplus=True,
-                                return_last=use_cache)
+                                return_last=use_cache, layout=layout)
             (gated, h_last), y = (res if use_cache else (res, None)), None
         out = _mfma_linear(gated, self.out_proj.weight)                     # core.py:397
         cache = (conv_state, h_last.reshape(B, self.num_heads, self.d_state)) if use_cache else None
@@ -1252,14 +1272,17 @@ class ApertisModel(nn.Module):
             return None
         return (1.0 - allow.to(inputs_embeds.dtype)) * torch.finfo(inputs_embeds.dtype).min
 
-    def _packed_layout(self, document_ids, input_shape, attention_mask, past_key_values, use_c, pixel_values):
+    def _packed_layout(self, document_ids, input_shape, attention_mask, past_key_values, use_c, pixel_values, device=None):
         """The ops.DocumentLayout of a packed forward, after the checks that keep such a forward well defined: standard_mha
-        (an SSM state would run across documents), no cache in or out, no image tokens in front of the rows, and no key
-        masking - the pad tail of a packed row is a document of its own, so every query keeps a key and attention_mask is
-        None or all ones (one host read, and only when a mask is given).  Every violation raises ValueError."""
-        if self.config.attention_type != "standard_mha":
-            raise ValueError(f"document_ids: packed rows need attention_type 'standard_mha', not "
-                             f"{self.config.attention_type!r} (the recurrent state would run across documents)")
+        (an SSM state would run across documents) - or, with ops.SSM_PACKED, selective_ssm on a ROCm device (`device`: the
+        inputs'), whose conv and scan then stop at the document boundaries - no cache in or out, no image tokens in front of
+        the rows, and no key masking - the pad tail of a packed row is a document of its own, so every query keeps a key and
+        attention_mask is None or all ones (one host read, and only when a mask is given).  Every violation raises ValueError."""
+        kind = self.config.attention_type
+        if kind != "standard_mha" and not (ops.SSM_PACKED and device is not None and device.type == "cuda"):
+            why = "ops.SSM_PACKED / APERTIS_SSM_PACKED=1 is off" if not ops.SSM_PACKED else f"the inputs are on {device}, not a ROCm device"
+            raise ValueError(f"document_ids: packed rows need attention_type 'standard_mha', not {kind!r} (the recurrent state "
+                             f"would run across documents; the packed selective_ssm path is not taken: {why})")
         if past_key_values is not None or use_c:
             raise ValueError("document_ids: packed rows take no past_key_values and no use_cache=True")
         if pixel_values is not None:
@@ -1334,9 +1357,10 @@ class ApertisModel(nn.Module):
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, pixel_values=None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, document_ids=None):
-        """document_ids: int64 [B, L], non-decreasing along L - PACKED rows (standard_mha, no cache): a run of equal ids is
-        one document, a token attends within its document only and, with position_ids = None, is positioned within it (the
-        pad tail of a row is a document of its own, so no attention_mask goes with it); _packed_layout has the rules.
+        """document_ids: int64 [B, L], non-decreasing along L - PACKED rows (standard_mha, or selective_ssm on a ROCm device
+        under ops.SSM_PACKED; no cache): a run of equal ids is one document, a token attends within its document only (an SSM
+        layer's conv and state stop at its start) and, with position_ids = None, is positioned within it (the pad tail of a
+        row is a document of its own, so no attention_mask goes with it); _packed_layout has the rules.
         past_key_values: a prefill's tuple of per-layer pairs (plain tensors in, plain tensors out), or for standard_mha an
         ops.KVCache: a single-token step then appends to it IN PLACE on the decode kernels and hands the same object back
         (position_ids = None: the step's position is the cache's length); a cache with `multi_token` set takes a forward of
@@ -1369,7 +1393,8 @@ class ApertisModel(nn.Module):
         pos = position_ids
         layout = None
         if document_ids is not None:
-            layout = self._packed_layout(document_ids, (B, Lq), attention_mask, past_key_values, use_c, pixel_values)
+            layout = self._packed_layout(document_ids, (B, Lq), attention_mask, past_key_values, use_c, pixel_values,
+                                         inputs_embeds.device)
             attention_mask = None
             if pos is None:
                 pos = layout.positions
@@ -1396,7 +1421,11 @@ class ApertisModel(nn.Module):
             logger.warning("pixel_values provided with past_key_values: image ignored for this step")
         x = self.embed_dropout(x)
         own_pos = position_ids is None and pos_layers is pos
-        if layout is not None:
+        if layout is not None and ssm:
+            if out_att:
+                raise ValueError("document_ids: a packed selective_ssm forward returns no attention weights (output_attentions)")
+            mask = _SsmDocs(layout)
+        elif layout is not None:
             mask = _AttnMask(None, True, False, lambda: self._document_additive_mask(layout, x.dtype), layout=layout,
                              layout_pos=own_pos)
         elif ssm:

@@ -31,7 +31,7 @@ _MODULES = (_base, prep, gemm, norm, ssm, scan, decode, moe, swiglu, loss, atten
 _FORWARDED = {
     "SCAN_SINGLE_PASS": scan, "SCAN_LEAN": scan, "SCAN_LEAN_BWD": scan, "SCAN_LOOKBACK": scan, "SCAN_DT_FUSED": scan,
     "SCAN_LOOKBACK_MIN_WGS": scan,
-    "DWCONV_PAIR": ssm, "SSM_LEFT_PAD": ssm,
+    "DWCONV_PAIR": ssm, "SSM_LEFT_PAD": ssm, "SSM_PACKED": ssm,
     "FUSE_ACT_BWD": moe, "SAVE_ACT_GRAD": moe, "ROWS_GRADIENT": moe,
     "FUSE_ROUTER_BOUNDARY_BWD": norm, "FUSED_ROUTER_BWD_CALLS": norm, "FUSE_COMBINE_BWD": norm, "RMSNORM_FUSED": norm,
     "GEMM_DYNAMIC_QUEUE": gemm, "TN_DYNAMIC_QUEUE": gemm, "DENSE_WGRAD_WIDE": gemm, "_splitk_depth": gemm,

@@ -11,6 +11,7 @@ import torch
 from .. import _lib
 from .._lib import ApertisHipError, check, dtype_code, ptr, stream_ptr
 from ._base import _apply, _f32, _grad_out, _grad_wanted, _indexed, _launch, _require_gpu, _rows, _slot_of, _try_launch
+from .ssm import doc_layout_check
 
 
 class _SelectiveScan(torch.autograd.Function):
@@ -187,17 +188,63 @@ def scan_gate_clear_error(device=None):
 SCAN_DT_FUSED = _os.environ.get("APERTIS_SCAN_DT_FUSED", "0") == "1"
 
 
+# PACKED rows (ops.ssm.SSM_PACKED): the state reset at a document's first token rides on delta.  The recurrence is
+# s_t = exp(delta_t * A) * s_{t-1} + Bt_t with Bt NOT scaled by delta, so a sequence's first token has s_0 = Bt_0 whatever its
+# delta: a reset IS a_t = 0.  Every scan form computes a_t = exp2(softplus(logit_t) * A2), A2 = -exp(A_log) * log2(e) < 0; with
+# the logit SSM_DOC_RESET at the document starts (t >= 1) softplus returns the logit itself, a_t = exp2(-huge) = 0 exactly,
+# s_t = fma(0, s_{t-1}, Bt_t) = Bt_t, and in the backward mu = a * lambda = 0 (nothing crosses the boundary), q = lambda *
+# h_prev * a * A = 0, so d delta = 0 and dA_log += q * delta = 0 - the scan kernels are not changed.
+# The value must be FINITE (0 * inf in the dA_log term is NaN) and stay finite where the kernels sum delta over a range of
+# tokens: 2^40 leaves 2^40 * L < 2^67 for L < 2^27 and, times |A2|, far below FLT_MAX.  exp2(RESET * A2) is exactly 0 as
+# long as RESET * exp(A_log) * log2(e) >= 150 (below the smallest fp32 denormal's exponent, whether or not the hardware exp2
+# flushes denormals): A_log >= SSM_DOC_A_LOG_FLOOR = -23, i.e. exp(A_log) >= 1.0e-10 (the initialisation is in [ln 0.5, ln 0.99]
+# and A = -exp(A_log) of a trained model stays within a few orders of magnitude of 1).  doc_reset_check reads the
+# parameters against that floor where the host syncs anyway: at trainer construction and at checkpoint save.
+SSM_DOC_RESET = float(2 ** 40)
+SSM_DOC_A_LOG_FLOOR = -23.0
+
+
+def doc_reset_check(model):
+    """Raise ApertisHipError if an A_log of `model`'s SSM layers lies below SSM_DOC_A_LOG_FLOOR (or is not finite): the state
+    reset of packed rows would then leave a non-zero decay at a document start.  One host read per SSM layer."""
+    for name, p in model.named_parameters():
+        if name.endswith("A_log"):
+            lo = float(p.detach().float().min())
+            if not lo >= SSM_DOC_A_LOG_FLOOR:
+                raise ApertisHipError(f"{name}: min {lo:.3g} is below {SSM_DOC_A_LOG_FLOOR} - packed selective_ssm rows reset the "
+                                      f"state through a delta logit of {SSM_DOC_RESET:g}, which needs exp2(-{SSM_DOC_RESET:g} * "
+                                      "exp(A_log) * log2 e) == 0")
+
+
+def _doc_args(what, layout, dlt_shape, device, h0, return_last):
+    """The `start` tensor of a scan op under a layout, after the refusals: no incoming state, no outgoing state."""
+    if h0 is not None or return_last:
+        raise ApertisHipError(f"{what}: packed rows (layout) take no h0 and no return_last - a row's documents have no one state")
+    B, L = dlt_shape[0], dlt_shape[1]
+    return doc_layout_check(what, layout, B, L, device)[0]
+
+
 class _ScanGate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last):
+    def forward(ctx, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last, layout=None):
+        if layout is not None:
+            _require_gpu(dlt)
+            if not delta_softplus:
+                raise ApertisHipError("scan_gate: packed rows (layout) reset the state through the delta LOGITS: delta_softplus=True")
+            start = _doc_args("scan_gate", layout, dlt.shape, dlt.device, h0, return_last)
+            # a copy of the caller's logits with SSM_DOC_RESET at the document starts: what the kernels read and the node saves
+            dlt = dlt.float().contiguous().clone()
+            T, h = dlt.numel() // dlt.shape[-1], dlt.shape[-1]
+            check(_lib.load().apertis_tiny_linear_doc_fwd(None, 0, None, None, ptr(start), SSM_DOC_RESET, ptr(dlt), T, dlt.shape[1],
+                                                          0, h, 0, stream_ptr()), "apertis_tiny_linear_doc_fwd")
         return _scan_gate_forward(ctx, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last,
                                   _grad_wanted(ctx, 7), None)
 
     @staticmethod
     def backward(ctx, dout, *_unused):
         if dout is None:
-            return (None,) * 10
-        return _scan_gate_backward(ctx, dout) + (None, None, None)
+            return (None,) * 11
+        return _scan_gate_backward(ctx, dout) + (None, None, None, None)
 
 
 class _ScanGateDt(torch.autograd.Function):
@@ -205,9 +252,21 @@ class _ScanGateDt(torch.autograd.Function):
     forward's state pass where that kernel takes the shape, by the stand-alone kernel otherwise - the same bits either way."""
 
     @staticmethod
-    def forward(ctx, dt_in, W_dt, b_dt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last):
+    def forward(ctx, dt_in, W_dt, b_dt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last, layout=None):
         _require_gpu(dt_in, W_dt, b_dt)
         R, h = dt_in.shape[-1], W_dt.shape[0]
+        start = None
+        if layout is not None:
+            # the logits of the document starts (t >= 1) are SSM_DOC_RESET, written by the dt kernel itself: the node saves them
+            # so, and the backward's d_dlt is exactly 0 there (nothing reaches dt_in, W_dt, b_dt from those rows)
+            if not delta_softplus:
+                raise ApertisHipError("scan_gate_dt: packed rows (layout) reset the state through the delta LOGITS: delta_softplus=True")
+            if SCAN_DT_FUSED:
+                raise ApertisHipError("scan_gate_dt: APERTIS_SCAN_DT_FUSED forms the logits inside the scan's state pass - not with "
+                                      "packed rows (layout)")
+            if dt_in.dim() != 3:
+                raise ApertisHipError(f"scan_gate_dt: dt_in [B, L, R] under a layout, got {tuple(dt_in.shape)}")
+            start = _doc_args("scan_gate_dt", layout, dt_in.shape, dt_in.device, h0, return_last)
         ctx.dt_slot = _slot_of(dt_in)
         xr, ldx = _rows(dt_in, R)
         w = _f32(W_dt)
@@ -215,7 +274,7 @@ class _ScanGateDt(torch.autograd.Function):
         ctx.dt_cfg = (ldx, tuple(dt_in.shape), W_dt.dtype, None if b_dt is None else b_dt.dtype)
         dlt = torch.empty(*dt_in.shape[:-1], h, device=dt_in.device, dtype=torch.float32)
         res = _scan_gate_forward(ctx, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last,
-                                 _grad_wanted(ctx, 9), (xr, ldx, w, b, R))
+                                 _grad_wanted(ctx, 9), (xr, ldx, w, b, R, start))
         ctx.dt_saved = (xr, w)     # (kept on ctx beside the tensors _scan_gate_forward saved: xr is a view of the projection output that the
         return res                 #  scan's own saved Bt / C slices keep alive and version-checked; w is an fp32 copy or the parameter itself)
 
@@ -223,7 +282,7 @@ class _ScanGateDt(torch.autograd.Function):
     def backward(ctx, dout, *_unused):
         lib = _lib.load()
         if dout is None:
-            return (None,) * 12
+            return (None,) * 13
         d_dlt, dA, dBt, dC, dxc, dz, dD = _scan_gate_backward(ctx, dout)
         xr, w = ctx.dt_saved
         ldx, xshape, wdt, bdt = ctx.dt_cfg
@@ -245,12 +304,13 @@ class _ScanGateDt(torch.autograd.Function):
         check(lib.apertis_tiny_linear_bwd_pad(ptr(xr), ldx, ptr(w), ptr(d_dlt), ptr(dxp), Kp, ptr(part), ptr(out), T, K, N, zero_to,
                                               dtype_code(xr), stream_ptr()), "apertis_tiny_linear_bwd")
         return (dx, out[:N * K].reshape(N, K).to(wdt), (out[N * K:].to(bdt) if bdt is not None else None),
-                dA, dBt, dC, dxc, dz, dD, None, None, None)
+                dA, dBt, dC, dxc, dz, dD, None, None, None, None)
 
 
 def _scan_gate_forward(ctx, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last, need_grad, dtp):
-    """Body of the two Functions above.  dtp = (dt rows, row stride, W fp32, b fp32 | None, R): `dlt` is an empty buffer
-    that the launch (or, where the fused kernel does not take the shape, apertis_tiny_linear_fwd) fills."""
+    """Body of the two Functions above.  dtp = (dt rows, row stride, W fp32, b fp32 | None, R, start | None): `dlt` is an empty
+    buffer that the launch (or, where the fused kernel does not take the shape, apertis_tiny_linear_fwd) fills; `start`
+    (packed rows): the doc form of that kernel, which writes SSM_DOC_RESET at the document starts."""
     _require_gpu(dlt, A_log, Bt, C, xc, z, D, h0)
     lib = _lib.load()
     B, L, h = dlt.shape
@@ -310,7 +370,7 @@ def _scan_gate_forward(ctx, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, ret
         tail = (ptr(A_log), ptr(Bt), bt_rs, ptr(C), c_rs, ptr(xc), xc_rs, ptr(z), z_rs, ptr(Df), ptr(h0), ptr(out),
                 out.stride(-2), ptr(h_last), ptr(agg), ptr(h_in), ptr(ckpt), B, L, h, N, int(delta_softplus), stream_ptr())
         if dtp is not None and SCAN_DT_FUSED and dtp[0].dtype == torch.bfloat16:
-            xr, ldx, w, b, R = dtp
+            xr, ldx, w, b, R, _ = dtp          # (never under a layout: _ScanGateDt.forward refuses the pair)
             _launch("apertis_scan_gate_fwd", lambda *a: rc.append(lib.apertis_scan_lean_fwd_dt(*a)) or (0 if rc[-1] == -2 else rc[-1]),
                     (ptr(xr), ldx, ptr(w), ptr(b), R, ptr(dlt)) + tail, work + B * L * (2 * R + 4 * h))
             dt_done = lean = rc[-1] == 0
@@ -345,7 +405,12 @@ def _scan_gate_forward(ctx, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, ret
 
 
 def _tiny_linear_into(lib, dtp, dlt):
-    xr, ldx, w, b, R = dtp
+    xr, ldx, w, b, R, start = dtp
+    if start is not None:
+        check(lib.apertis_tiny_linear_doc_fwd(ptr(xr), ldx, ptr(w), ptr(b), ptr(start), SSM_DOC_RESET, ptr(dlt),
+                                              dlt.numel() // dlt.shape[-1], dlt.shape[1], R, dlt.shape[-1], dtype_code(xr),
+                                              stream_ptr()), "apertis_tiny_linear_doc_fwd")
+        return
     check(lib.apertis_tiny_linear_fwd(ptr(xr), ldx, ptr(w), ptr(b), ptr(dlt), dlt.numel() // dlt.shape[-1], R, dlt.shape[-1],
                                       dtype_code(xr), stream_ptr()), "apertis_tiny_linear_fwd")
 
@@ -403,21 +468,26 @@ def _scan_gate_backward(ctx, dout):
     return d_dlt, dA_dD[0].reshape(h, N), dBt, dC, dxc, dz, dA_dD[1].to(Ddt)
 
 
-def scan_gate(dlt, A_log, Bt, C, xc, z, D, h0=None, delta_softplus=False, return_last=False):
+def scan_gate(dlt, A_log, Bt, C, xc, z, D, h0=None, delta_softplus=False, return_last=False, layout=None):
     """(C*s + D*xc) * silu(z) with s_t = exp(delta_t*A)*s_{t-1} + Bt_t: the recurrence (reference core.py:337-353) and
     the skip + gate (core.py:395-396) in ONE kernel per direction; y is never written (the backward recomputes it).
 
     dlt [B,L,h] fp32 (pre-softplus logits when delta_softplus), A_log [h,N], xc / z [B,L,h*N], D [h*N];
     Bt / C [B,L,w] with h*N <= w <= ceil(h*N/64)*64: the (possibly zero-padded) column slices of the projection output,
     of which the first h*N columns are used; their gradients come back [B,L,w] with zeros in the pad.
-    Returns out [B,L,h*N] in the activations' dtype (and the final state [B,h*N] fp32 when return_last)."""
-    return _apply(_ScanGate, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last)
+    Returns out [B,L,h*N] in the activations' dtype (and the final state [B,h*N] fp32 when return_last).
+    layout (ops.document_layout, packed rows; needs delta_softplus, no h0, no return_last): the state is reset at every
+    document's first token - the kernels read a copy of dlt with SSM_DOC_RESET at those rows (t >= 1) - so each document gets
+    the outputs and gradients it gets in a row of its own, and d dlt is exactly 0 at those rows."""
+    return _apply(_ScanGate, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last, layout)
 
 
-def scan_gate_dt(dt_in, W_dt, b_dt, A_log, Bt, C, xc, z, D, h0=None, delta_softplus=True, return_last=False):
+def scan_gate_dt(dt_in, W_dt, b_dt, A_log, Bt, C, xc, z, D, h0=None, delta_softplus=True, return_last=False, layout=None):
     """scan_gate(tiny_linear(dt_in, W_dt, b_dt), ...) as ONE op (reference core.py:382-396).  With APERTIS_SCAN_DT_FUSED=1
     dt_proj_head runs inside the lean forward's state pass where that kernel takes the shape (N4's pre-scan prologue; off by
     default - measured slower than the launch it replaces, see SCAN_DT_FUSED); otherwise the stand-alone kernel fills the
     logits.  The logits, outputs and gradients are the two-op form's bit for bit either way.  dt_in [B, L, R] (a column slice
-    of the projection output is read in place), W_dt [h, R], b_dt [h] or None."""
-    return _apply(_ScanGateDt, dt_in, W_dt, b_dt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last)
+    of the projection output is read in place), W_dt [h, R], b_dt [h] or None.
+    layout: packed rows as in scan_gate - the dt kernel writes SSM_DOC_RESET into the rows of the document starts itself (no
+    extra launch); not with APERTIS_SCAN_DT_FUSED."""
+    return _apply(_ScanGateDt, dt_in, W_dt, b_dt, A_log, Bt, C, xc, z, D, h0, delta_softplus, return_last, layout)

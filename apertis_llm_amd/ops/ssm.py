@@ -122,21 +122,103 @@ def _dwconv_silu_start(x, w, b, start):
     return out
 
 
-def dwconv_silu(x, weight, bias, start=None):
+# APERTIS_SSM_PACKED=1: a selective_ssm model takes PACKED rows (document_ids; ApertisTrainer(pack_sequences=True)), in training
+# and in eval forwards, and every document of a row gets what it gets in a row of its own: the conv stops at a document's first
+# token (dwconv_silu(layout=...)) and the scan's state is reset there (ops.scan_gate_dt(layout=...)).  Off by default: the
+# reference has no packed rows, and with it off such a model refuses them as before.
+SSM_PACKED = _os.environ.get("APERTIS_SSM_PACKED", "0") == "1"
+
+
+def doc_layout_check(what, layout, B, L, device):
+    """(start, end) of an ops.DocumentLayout, checked against rows [B, L] on `device` as the kernels read them."""
+    start, end = getattr(layout, "start", None), getattr(layout, "end", None)
+    for t in (start, end):
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, L) or t.dtype != torch.int32 or not t.is_contiguous()
+                or t.device != device):
+            raise ApertisHipError(f"{what}: layout is what ops.document_layout returns for rows [{B}, {L}] on {device}")
+    return start, end
+
+
+class _DwConvSiluDoc(torch.autograd.Function):
+    """_DwConvSilu on packed rows: both directions stop at the document boundaries of `layout`."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, layout):
+        _require_gpu(x, w, b)
+        lib = _lib.load()
+        B, L, Dn = x.shape
+        start, end = doc_layout_check("dwconv_silu", layout, B, L, x.device)
+        ctx.slot = _slot_of(x)
+        x, x_rs = _rows(x, Dn)
+        w2 = _f32(w).reshape(Dn, -1)
+        b2 = _f32(b)
+        out = torch.empty(B, L, Dn, device=x.device, dtype=x.dtype)
+        check(lib.apertis_dwconv_silu_doc_fwd(ptr(x), x_rs, ptr(w2), ptr(b2), ptr(start), ptr(out), Dn, B, L, Dn, w2.shape[1],
+                                              dtype_code(x), stream_ptr()), "apertis_dwconv_silu_doc_fwd")
+        ctx.save_for_backward(x, w2, b2, start, end)
+        ctx.wshape = w.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout, dout2=None):
+        lib = _lib.load()
+        x, w2, b2, start, end = ctx.saved_tensors
+        B, L, Dn = x.shape
+        k = w2.shape[1]
+        if dout is None:
+            dout, dout2 = dout2, None
+        if dout is None:
+            return None, None, None, None
+        dout = dout.to(x.dtype).contiguous()            # (as _DwConvSilu.backward: both gradients in the io dtype)
+        if dout2 is not None:
+            dout2 = dout2.to(x.dtype).contiguous()
+        nblk = lib.apertis_dwconv_bwd_blocks(B, L, Dn)
+        dev = x.device
+        dx, dx_rs = _grad_out(ctx.slot, (B, L), Dn, x.dtype, dev)
+        dw_part = torch.empty(nblk, Dn, k, device=dev, dtype=torch.float32)
+        db_part = torch.empty(nblk, Dn, device=dev, dtype=torch.float32)
+        dw = torch.empty(Dn, k, device=dev, dtype=torch.float32)
+        db = torch.empty(Dn, device=dev, dtype=torch.float32)
+        check(lib.apertis_dwconv_silu_doc_bwd(ptr(x), x.stride(-2), ptr(w2), ptr(b2), ptr(dout), Dn, ptr(dout2), Dn, ptr(start),
+                                              ptr(end), ptr(dx), dx_rs, ptr(dw_part), ptr(db_part), ptr(dw), ptr(db), B, L, Dn, k,
+                                              dtype_code(x), stream_ptr()), "apertis_dwconv_silu_doc_bwd")
+        return dx, dw.reshape(ctx.wshape), db, None
+
+
+class _DwConvSiluDocPair(_DwConvSiluDoc):
+    """_DwConvSiluPair on packed rows: the output as two views, one per consumer; same contract."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, layout):
+        out = _DwConvSiluDoc.forward(ctx, x, w, b, layout)
+        ctx.set_materialize_grads(False)
+        return out, out.view_as(out)
+
+
+def dwconv_silu(x, weight, bias, start=None, layout=None):
     """silu(causal depthwise conv1d(x)) on token-major x [B,L,Dn] (reference core.py:368-375).
     weight [Dn,1,k] (nn.Conv1d layout), bias [Dn].
     start (int32 [B], left_pad_starts): row b's sequence begins at token start[b] - taps before it read as zero and the
-    outputs before it are exact zeros; forward only."""
+    outputs before it are exact zeros; forward only.
+    layout (ops.document_layout, packed rows): a tap in front of its token's document reads as zero, and the backward stops at
+    the same boundaries - every document gets the outputs (their bits) and the gradients it gets in a row of its own."""
+    if start is not None and layout is not None:
+        raise ApertisHipError("dwconv_silu: start (a left-padded prefill) and layout (packed rows) do not go together")
     if start is not None:
         return _dwconv_silu_start(x, weight, bias, start)
+    if layout is not None:
+        return _DwConvSiluDoc.apply(x, weight, bias, layout)
     return _DwConvSilu.apply(x, weight, bias)
 
 
-def dwconv_silu_pair(x, weight, bias):
-    """dwconv_silu as two views of the one output, one per consumer: see _DwConvSiluPair (under no_grad: one tensor, twice)."""
+def dwconv_silu_pair(x, weight, bias, layout=None):
+    """dwconv_silu as two views of the one output, one per consumer: see _DwConvSiluPair (under no_grad: one tensor, twice).
+    layout: packed rows, as in dwconv_silu."""
     if not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or bias.requires_grad)):
-        out = _DwConvSilu.apply(x, weight, bias)
+        out = dwconv_silu(x, weight, bias, layout=layout)
         return out, out
+    if layout is not None:
+        return _DwConvSiluDocPair.apply(x, weight, bias, layout)
     return _DwConvSiluPair.apply(x, weight, bias)
 
 

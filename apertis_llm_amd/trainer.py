@@ -74,8 +74,11 @@ class ApertisTrainer:
         self.pack_sequences = pack_sequences
         if pack_sequences:
             # several items per row (data.PackedDataset): no pad tokens through the model, attention within each document
-            if getattr(getattr(model, "config", None), "attention_type", None) != "standard_mha":
-                raise ValueError("pack_sequences=True needs a standard_mha model (packed rows carry document_ids)")
+            # (a selective_ssm model takes them under ops.SSM_PACKED, on a ROCm device: checked below, once the device is known)
+            kind = getattr(getattr(model, "config", None), "attention_type", None)
+            if kind != "standard_mha" and not (kind == "selective_ssm" and ops.SSM_PACKED):
+                raise ValueError("pack_sequences=True needs a standard_mha model (packed rows carry document_ids), or a "
+                                 "selective_ssm model with ops.SSM_PACKED / APERTIS_SSM_PACKED=1 on a ROCm device")
             self.train_dataset = self._packed(train_dataset)
             self.val_dataset = self._packed(val_dataset) if val_dataset else val_dataset
         if use_wandb:
@@ -97,6 +100,10 @@ class ApertisTrainer:
             # the HIP kernels launch on the CURRENT device and stream (stock torch ops guard themselves, which is why
             # the reference's trainer gets away without this call, pipeline.py:447-460)
             torch.cuda.set_device(self.device)
+        self._packed_ssm = pack_sequences and getattr(getattr(model, "config", None), "attention_type", None) != "standard_mha"
+        if self._packed_ssm and self.device.type != "cuda":
+            raise ValueError(f"pack_sequences=True with a selective_ssm model (ops.SSM_PACKED) needs a ROCm device, not {self.device}: "
+                             "the conv and the scan that stop at document boundaries are HIP kernels")
         if distributed_training:
             if not dist.is_initialized():
                 if self.device.type == "cuda":
@@ -123,6 +130,8 @@ class ApertisTrainer:
                                                              pct_start=0.1, anneal_strategy="cos", div_factor=25.0,
                                                              final_div_factor=10000.0)
         self._params = [p for p in model.parameters() if p.requires_grad]
+        if self._packed_ssm:
+            ops.doc_reset_check(model)       # (the state reset of packed rows holds for A_log above a floor: ops.SSM_DOC_RESET)
         self.history: Dict[str, list] = {"loss": [], "lr": [], "val_loss": [], "checkpoints": []}
 
     # --------------------------------------------------------------------------------------------------------
@@ -267,6 +276,8 @@ class ApertisTrainer:
     def save_checkpoint(self, name: str):
         ckpt = os.path.join(self.output_dir, name)
         os.makedirs(ckpt, exist_ok=True)
+        if self._packed_ssm:
+            ops.doc_reset_check(self.model)  # (the host reads the parameters here anyway)
         torch.save(self.model.state_dict(), os.path.join(ckpt, "pytorch_model.bin"))
         if hasattr(self.model, "config") and hasattr(self.model.config, "save_pretrained"):
             self.model.config.save_pretrained(ckpt)

@@ -59,7 +59,9 @@ extern "C" {
  * The SwiGLU entry points (apertis_swiglu_fwd / _bwd) joined them the same way, for the same reason: still 4.12.
  * So did the bidirectional attention pair of the vision tower (apertis_attention_full_fwd / _bwd): still 4.12.
  * So did the document-masked causal pair of packed rows (apertis_attention_doc_fwd / _bwd): still 4.12, 117 entry points.
- * So did the left-padded form of the conv forward (apertis_dwconv_silu_start_fwd): still 4.12, 118 entry points. */
+ * So did the left-padded form of the conv forward (apertis_dwconv_silu_start_fwd): still 4.12, 118 entry points.
+ * So did the packed-row forms of the SSM block (apertis_dwconv_silu_doc_fwd / _bwd, apertis_tiny_linear_doc_fwd): still 4.12,
+ * 121 entry points. */
 #define APERTIS_ABI_VERSION ((4 << 16) | 12)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
@@ -303,6 +305,26 @@ int apertis_dwconv_silu_bwd2(const void *x, int64_t x_rs, const float *w, const 
 int apertis_dwconv_silu_start_fwd(const void *x, int64_t x_rs, const float *w, const float *bias,
                                   const int32_t *start /* [B] */, void *out, int64_t out_rs, int64_t B,
                                   int64_t L, int64_t Dn, int64_t k, int dtype_io, void *stream);
+/* The conv of PACKED rows (training and eval; several documents per batch row): token t of row b belongs to the document
+ * [start[b, t], end[b, t]) - int32 [B, L] on the device, contiguous, as the attention_doc pair takes them.
+ *   forward: a tap at token t - j < start[b, t] reads as 0, as t - j < 0 does in the plain forward; the sum is the plain
+ *     forward's term for term, so out at a document's tokens carries the bits apertis_dwconv_silu_fwd gives that document as a
+ *     sequence of its own, and with one document per row the plain forward's bits.  2 <= k <= 16, any Dn % 4 == 0, x and out at
+ *     addresses that are multiples of four elements, row strides >= Dn and % 4 == 0; APERTIS_ERR_UNSUPPORTED otherwise.
+ *   backward: apertis_dwconv_silu_bwd2 (dout2 may be NULL; the sum of the two rounded to the io dtype where the rows are read)
+ *     with pre recomputed under the same predicate; dx[t] sums the outputs t' >= t with t' < end[b, t] only, dw the (tap,
+ *     output) pairs inside one document, db as before.  Same scratch (dw_part [nblk, Dn, k], db_part [nblk, Dn], nblk =
+ *     apertis_dwconv_bwd_blocks), fixed-order folds, no atomics: the same bits on every run; with one document per row dx
+ *     carries apertis_dwconv_silu_bwd2's bits. */
+int apertis_dwconv_silu_doc_fwd(const void *x, int64_t x_rs, const float *w, const float *bias,
+                                const int32_t *start /* [B, L] */, void *out, int64_t out_rs, int64_t B,
+                                int64_t L, int64_t Dn, int64_t k, int dtype_io, void *stream);
+int apertis_dwconv_silu_doc_bwd(const void *x, int64_t x_rs, const float *w, const float *bias,
+                                const void *dout, int64_t dout_rs, const void *dout2, int64_t dout2_rs,
+                                const int32_t *start /* [B, L] */, const int32_t *end /* [B, L] */,
+                                void *dx, int64_t dx_rs, float *dw_part, float *db_part, float *dw,
+                                float *db, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
+                                void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * MoE router gating (replaces AdaptiveExpertSystem.forward core.py:491-492,529)
@@ -411,6 +433,14 @@ int apertis_tiny_linear_fwd(const void *x, int64_t ldx, const float *W, const fl
 int apertis_tiny_linear_bwd(const void *x, int64_t ldx, const float *W, const float *dy, void *dx,
                             int64_t lddx, float *part, float *dW_db, int64_t T, int64_t K,
                             int64_t N, int dtype_x, void *stream);
+/* apertis_tiny_linear_fwd for the dt logits of PACKED rows: the T = B*L rows are the tokens of [B, L] and start is the int32
+ * [B, L] document layout.  The row of a document's first token at t >= 1 (start[b, t] == t) receives the finite value `reset`
+ * in all N columns instead of the projection (the scan kernels then form a decay of exactly 0 there: the state reset); every
+ * other row carries apertis_tiny_linear_fwd's bits.  With x == NULL (W, b, K unused, any N) y already holds logits and only
+ * those rows are overwritten. */
+int apertis_tiny_linear_doc_fwd(const void *x, int64_t ldx, const float *W, const float *b,
+                                const int32_t *start /* [B, L] */, float reset, float *y, int64_t T,
+                                int64_t L, int64_t K, int64_t N, int dtype_x, void *stream);
 /* ... and with the columns [K, zero_to) of every dx row set to zero (zero_to <= lddx): the pad behind the dt columns in the
  * padded projection output's gradient, which otherwise costs a strided fill of its own. */
 int apertis_tiny_linear_bwd_pad(const void *x, int64_t ldx, const float *W, const float *dy, void *dx,
