@@ -179,6 +179,10 @@ SIGNATURES = {
                                          _u64, _i32, _vp]),
     "apertis_attention_doc_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _i64, _i64, _i64, _i64, _i64, _f32, _u64, _i32, _vp]),
+    "apertis_attention_window_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32,
+                                            _u64, _i32, _vp]),
+    "apertis_attention_window_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
+                                            _vp, _i64, _i64, _i64, _i64, _i64, _f32, _u64, _i32, _vp]),
     "apertis_rope_kv_append": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64,
                                       _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
     "apertis_attention_decode_splits": (_i64, [_i64, _i64, _i64, _i64]),

@@ -23,13 +23,19 @@
 // output row - is shared.  A sequence with no valid key at all gets O = 0, LSE = +inf and zero gradients, which is what the
 // causal form gives a row without a valid key.
 //
-// DOC = true (with CAUSAL) is the document-masked form of packed rows (apertis_attention_doc_fwd / _bwd): query i sees key j iff
+// MASK_DOC (with CAUSAL) is the document-masked form of packed rows (apertis_attention_doc_fwd / _bwd): query i sees key j iff
 // doc_start[b, i] <= j <= i, which for a key reads j <= i < doc_end[b, j] (documents are contiguous runs; start inclusive, end
 // exclusive).  A wave's loop begins at the tile of the smallest start among its 16 queries (forward, dQ) and ends at the largest
 // end among its 16 keys (dK/dV): both bounds are reduced over the 16 rows and broadcast, so they are wave-uniform.  A skipped
 // tile is one in which no key counts for any query of the wave: attn_fwd_tile leaves (m, lsum, acc) as they were on such a tile
 // while m = -inf, and the backward adds exact zeros, so skipping is bit-identical to walking.  The bounds are clamped to what the
 // causal loops walk, so whatever the two arrays hold only masks: no address depends on them.
+//
+// MASK_WINDOW (with CAUSAL) is the sliding-window form (apertis_attention_window_fwd / _bwd): the same mask with bounds that are
+// a function of the index and ONE scalar W - query i sees key j iff i - W < j <= i, which for a key reads j <= i < j + W.  Nothing
+// is loaded and nothing reduced: a wave's first key tile is that of max(0, q0 - W + 1) (q0 its first query: the smallest start),
+// its last query tile the one holding min(L, k0 + 15 + W) - 1.  The skip-equals-walk argument and the clamp are the document
+// form's, so the bits are those of the document form fed start = max(0, i - W + 1), end = min(L, j + W).  Compared in 64 bits.
 #include "attn_tile.h"
 #include "rope_common.h"
 
@@ -47,11 +53,17 @@ struct AttnArgs {
   uint64_t seed;
   uint32_t thresh16;
 };
-// what the DOC = true kernels take: AttnArgs and, per token, the first key / one past the last query of its document ([B, L])
+// what the MASK_DOC kernels take: AttnArgs and, per token, the first key / one past the last query of its document ([B, L])
 struct DocArgs : AttnArgs {
   const int32_t *doc_start, *doc_end;
 };
-template <bool DOC> using Args = std::conditional_t<DOC, DocArgs, AttnArgs>;
+// the window kernels: AttnArgs and the number of keys a query sees, its own included (>= 1)
+struct WindowArgs : AttnArgs {
+  int64_t window;
+};
+// the mask on top of CAUSAL: none, the two arrays of packed rows, or the one scalar of a sliding window
+enum Mask { MASK_NONE, MASK_DOC, MASK_WINDOW };
+template <Mask M> using Args = std::conditional_t<M == MASK_DOC, DocArgs, std::conditional_t<M == MASK_WINDOW, WindowArgs, AttnArgs>>;
 
 // smallest / largest value among the wave's 16 rows (lane & 15; the four lane groups hold copies), as a wave-uniform scalar
 __device__ __forceinline__ int rows16_min(int v) {
@@ -65,9 +77,17 @@ __device__ __forceinline__ int rows16_max(int v) {
   return __builtin_amdgcn_readfirstlane(v);
 }
 
+// WINDOW: the first key of the wave's first tile, max(0, q0 - W + 1) rounded down to a tile (q0 >= 0 and W >= 1: the difference
+// cannot wrap).  q0 comes from threadIdx.x >> 6, which the compiler cannot see is wave-uniform; read through lane 0 (as a tile
+// index: the entry points refuse L > INT32_MAX, as the document pair does) the loop counter and the tile addresses built from it stay scalar
+__device__ __forceinline__ int64_t window_first_tile(int64_t q0, int64_t window) {
+  const int64_t first = max(q0 - window + 1, (int64_t)0) / TILE;
+  return (int64_t)__builtin_amdgcn_readfirstlane((int)first) * TILE;
+}
+
 // ---------------------------------------------------------------------------------------------------------- forward
-template <typename T, int D, bool DROP, bool CAUSAL, bool DOC>
-__global__ __launch_bounds__(256) void attn_fwd_k(Args<DOC> a) {
+template <typename T, int D, bool DROP, bool CAUSAL, Mask M>
+__global__ __launch_bounds__(256) void attn_fwd_k(Args<M> a) {
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t L = a.L;
   const int bh = blockIdx.y, H = a.H, b = bh / H, h = bh - b * H;
@@ -90,10 +110,13 @@ __global__ __launch_bounds__(256) void attn_fwd_k(Args<DOC> a) {
   const int64_t last = CAUSAL ? min(q0 + ROWS - 1, L - 1) : L - 1;
   const uint64_t drow = (uint64_t)bh * (uint64_t)L + (uint64_t)qi;
   int64_t qs = 0, kb0 = 0;                                 // DOC: this query's first key; the wave's first tile
-  if constexpr (DOC) {
+  if constexpr (M == MASK_DOC) {
     qs = qi < L ? a.doc_start[(int64_t)b * L + qi] : INT32_MAX;
     kb0 = min((int64_t)max(rows16_min((int)qs), 0), q0) & ~(int64_t)(TILE - 1);
   }
+  // WINDOW: q0 >= 0 and W >= 1, so the difference cannot wrap; the per-lane predicate needs no bound of its own - the
+  // diagonal and the window are ONE unsigned compare of the distance qi - key against the scalar W
+  if constexpr (M == MASK_WINDOW) kb0 = window_first_tile(q0, a.window);
   for (int64_t kb = kb0; kb <= last; kb += TILE) {
     const int64_t nrows = L - kb;
     attn_fwd_tile<T, D>(
@@ -101,9 +124,10 @@ __global__ __launch_bounds__(256) void attn_fwd_k(Args<DOC> a) {
         [=](int t) {
           const int64_t key = kb + tile_row(g, t);
           bool ok;
-          if constexpr (CAUSAL) ok = key <= qi && key < L;
+          if constexpr (M == MASK_WINDOW) ok = (uint64_t)(qi - key) < (uint64_t)a.window && key < L;
+          else if constexpr (CAUSAL) ok = key <= qi && key < L;
           else ok = key < L;
-          if constexpr (DOC) ok = ok && key >= qs;
+          if constexpr (M == MASK_DOC) ok = ok && key >= qs;
           if (kv && ok) ok = kv[key] != 0;
           return ok;
         },
@@ -138,8 +162,8 @@ __global__ __launch_bounds__(256) void attn_dsum_k(AttnArgs a, int64_t rows) {
 }
 
 // dK, dV for the 16 keys of a wave: loop over the query tiles at or below the diagonal (bidirectional: over all of them)
-template <typename T, int D, bool DROP, bool CAUSAL, bool DOC>
-__global__ __launch_bounds__(256) void attn_bwd_dkv_k(Args<DOC> a) {
+template <typename T, int D, bool DROP, bool CAUSAL, Mask M>
+__global__ __launch_bounds__(256) void attn_bwd_dkv_k(Args<M> a) {
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t L = a.L;
   const int bh = blockIdx.y, H = a.H, b = bh / H, h = bh - b * H;
@@ -162,10 +186,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(Args<DOC> a) {
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt) dk[dt] = dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   int64_t ke = L, qend = L;                                // DOC: one past this key's last query; the wave's last query + 1
-  if constexpr (DOC) {
+  if constexpr (M == MASK_DOC) {
     ke = kj < L ? a.doc_end[bo + kj] : 0;
     qend = min((int64_t)rows16_max((int)ke), L);
   }
+  // WINDOW: W >= L is every query at or below the diagonal; else the sum is < 2 L + 15 and cannot wrap
+  if constexpr (M == MASK_WINDOW) qend = a.window >= L ? L : min(k0 + ROWS - 1 + a.window, L);
   for (int64_t qb = CAUSAL ? k0 & ~(int64_t)(TILE - 1) : 0; qb < qend; qb += TILE) {
     f32x4 pd[2], ds[2];
 #pragma unroll
@@ -181,9 +207,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(Args<DOC> a) {
       for (int r = 0; r < 4; ++r) {
         const int64_t qi = qb + 16 * s + 4 * g + r;
         bool ok;
-        if constexpr (CAUSAL) ok = kok && qi < L && kj <= qi;
+        if constexpr (M == MASK_WINDOW) ok = kok && qi < L && (uint64_t)(qi - kj) < (uint64_t)a.window;
+        else if constexpr (CAUSAL) ok = kok && qi < L && kj <= qi;
         else ok = kok && qi < L;
-        if constexpr (DOC) ok = ok && qi < ke;
+        if constexpr (M == MASK_DOC) ok = ok && qi < ke;
         const float p = ok ? exp2f(sv[r] * sl2 - lse[qi] * LOG2E_F) : 0.f;
         float dpr = dp[r], pdr = p;
         if constexpr (DROP) {
@@ -206,8 +233,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_k(Args<DOC> a) {
 }
 
 // dQ for the 16 queries of a wave: loop over the key tiles at or below the diagonal (bidirectional: over all of them)
-template <typename T, int D, bool DROP, bool CAUSAL, bool DOC>
-__global__ __launch_bounds__(256) void attn_bwd_dq_k(Args<DOC> a) {
+template <typename T, int D, bool DROP, bool CAUSAL, Mask M>
+__global__ __launch_bounds__(256) void attn_bwd_dq_k(Args<M> a) {
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t L = a.L;
   const int bh = blockIdx.y, H = a.H, b = bh / H, h = bh - b * H;
@@ -234,10 +261,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(Args<DOC> a) {
   for (int dt = 0; dt < D / 16; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int64_t last = CAUSAL ? min(q0 + ROWS - 1, L - 1) : L - 1;
   int64_t qs = 0, kb0 = 0;                                 // DOC: as in the forward
-  if constexpr (DOC) {
+  if constexpr (M == MASK_DOC) {
     qs = qok ? a.doc_start[bo + qi] : INT32_MAX;
     kb0 = min((int64_t)max(rows16_min((int)qs), 0), q0) & ~(int64_t)(TILE - 1);
   }
+  if constexpr (M == MASK_WINDOW) kb0 = window_first_tile(q0, a.window);
   for (int64_t kb = kb0; kb <= last; kb += TILE) {
     f32x4 ds[2];
 #pragma unroll
@@ -253,9 +281,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(Args<DOC> a) {
       for (int r = 0; r < 4; ++r) {
         const int64_t key = kb + 16 * s + 4 * g + r;
         bool ok;
-        if constexpr (CAUSAL) ok = qok && key <= qi;
+        if constexpr (M == MASK_WINDOW) ok = qok && (uint64_t)(qi - key) < (uint64_t)a.window;
+        else if constexpr (CAUSAL) ok = qok && key <= qi;
         else ok = qok && key < L;
-        if constexpr (DOC) ok = ok && key >= qs;
+        if constexpr (M == MASK_DOC) ok = ok && key >= qs;
         if (kv && ok) ok = kv[key] != 0;
         const float p = ok ? exp2f(sv[r] * sl2 - lse2) : 0.f;
         float dpr = dp[r];
@@ -270,25 +299,25 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_k(Args<DOC> a) {
   store_cols<T, D>(static_cast<T *>(a.dq) + (bo + qi) * a.d_rs + h * D, dq, a.scale, lane);
 }
 
-template <typename T, int D, bool DROP, bool CAUSAL, bool DOC> int launch_fwd(const Args<DOC> &a, int64_t B, hipStream_t st) {
+template <typename T, int D, bool DROP, bool CAUSAL, Mask M> int launch_fwd(const Args<M> &a, int64_t B, hipStream_t st) {
   const dim3 grid((unsigned)ceil_div64(a.L, WG_ROWS), (unsigned)(B * a.H));
-  hipLaunchKernelGGL((attn_fwd_k<T, D, DROP, CAUSAL, DOC>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((attn_fwd_k<T, D, DROP, CAUSAL, M>), grid, dim3(256), 0, st, a);
   return apertis_check_launch();
 }
-template <typename T, int D, bool DROP, bool CAUSAL, bool DOC> int launch_bwd(const Args<DOC> &a, int64_t B, hipStream_t st) {
+template <typename T, int D, bool DROP, bool CAUSAL, Mask M> int launch_bwd(const Args<M> &a, int64_t B, hipStream_t st) {
   const int64_t rows = B * a.L;
   hipLaunchKernelGGL((attn_dsum_k<T, D>), dim3((unsigned)ceil_div64(rows * a.H, 256)), dim3(256), 0, st, (const AttnArgs &)a, rows);
   const dim3 grid((unsigned)ceil_div64(a.L, WG_ROWS), (unsigned)(B * a.H));
-  hipLaunchKernelGGL((attn_bwd_dkv_k<T, D, DROP, CAUSAL, DOC>), grid, dim3(256), 0, st, a);
-  hipLaunchKernelGGL((attn_bwd_dq_k<T, D, DROP, CAUSAL, DOC>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((attn_bwd_dkv_k<T, D, DROP, CAUSAL, M>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((attn_bwd_dq_k<T, D, DROP, CAUSAL, M>), grid, dim3(256), 0, st, a);
   return apertis_check_launch();
 }
 
-template <bool BWD, bool CAUSAL, bool DOC> int dispatch(const Args<DOC> &a, int64_t B, int64_t D, int dtype, bool drop, hipStream_t st) {
+template <bool BWD, bool CAUSAL, Mask M> int dispatch(const Args<M> &a, int64_t B, int64_t D, int dtype, bool drop, hipStream_t st) {
 #define APERTIS_ATTN_CASE(T, DD)                                                                                                \
   if (D == DD) {                                                                                                                \
-    if constexpr (BWD) return drop ? launch_bwd<T, DD, true, CAUSAL, DOC>(a, B, st) : launch_bwd<T, DD, false, CAUSAL, DOC>(a, B, st); \
-    else return drop ? launch_fwd<T, DD, true, CAUSAL, DOC>(a, B, st) : launch_fwd<T, DD, false, CAUSAL, DOC>(a, B, st);      \
+    if constexpr (BWD) return drop ? launch_bwd<T, DD, true, CAUSAL, M>(a, B, st) : launch_bwd<T, DD, false, CAUSAL, M>(a, B, st); \
+    else return drop ? launch_fwd<T, DD, true, CAUSAL, M>(a, B, st) : launch_fwd<T, DD, false, CAUSAL, M>(a, B, st);      \
   }
   if (dtype == APERTIS_F32) {
     APERTIS_ATTN_CASE(float, 64)
@@ -374,42 +403,47 @@ int rope_entry(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const i
   return apertis_check_launch();
 }
 
-// DOC: doc_start / doc_end are checked with the other pointers (null: APERTIS_ERR_ARG); else they are not looked at
-template <bool CAUSAL, bool DOC = false>
+// MASK_DOC: doc_start / doc_end are checked with the other pointers (null: APERTIS_ERR_ARG); else they are not looked at.
+// MASK_WINDOW: window < 1 is APERTIS_ERR_ARG, and so is L > INT32_MAX as for MASK_DOC; else it is not looked at
+template <bool CAUSAL, Mask M = MASK_NONE>
 int attention_fwd_entry(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs, const int64_t *key_valid,
                         void *out, int64_t out_rs, float *lse, int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p,
                         uint64_t seed, int dtype, void *stream, const int32_t *doc_start = nullptr,
-                        const int32_t *doc_end = nullptr) {
-  if (DOC && (!doc_start || !doc_end || L > INT32_MAX)) return APERTIS_ERR_ARG;
+                        const int32_t *doc_end = nullptr, int64_t window = 0) {
+  if (M == MASK_DOC && (!doc_start || !doc_end || L > INT32_MAX)) return APERTIS_ERR_ARG;
+  if (M == MASK_WINDOW && (window < 1 || L > INT32_MAX)) return APERTIS_ERR_ARG;
   const int rc = attn_check({q, k, v, out, lse}, {q_rs, k_rs, v_rs, out_rs}, B, L, H, D, dropout_p, dtype);
   if (rc) return rc;
   if (B == 0 || L == 0) return APERTIS_OK;
-  Args<DOC> a{};
+  Args<M> a{};
   static_cast<AttnArgs &>(a) = make_args(L, H, D, dropout_p, seed);
   a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.key_valid = key_valid;
   a.q_rs = q_rs; a.k_rs = k_rs; a.v_rs = v_rs; a.o_rs = out_rs;
-  if constexpr (DOC) { a.doc_start = doc_start; a.doc_end = doc_end; }
-  return dispatch<false, CAUSAL, DOC>(a, B, D, dtype, dropout_p > 0.f, (hipStream_t)stream);
+  if constexpr (M == MASK_DOC) { a.doc_start = doc_start; a.doc_end = doc_end; }
+  if constexpr (M == MASK_WINDOW) a.window = window;
+  return dispatch<false, CAUSAL, M>(a, B, D, dtype, dropout_p > 0.f, (hipStream_t)stream);
 }
 
-template <bool CAUSAL, bool DOC = false>
+template <bool CAUSAL, Mask M = MASK_NONE>
 int attention_bwd_entry(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs, const void *out,
                         int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse, const int64_t *key_valid,
                         float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B, int64_t L, int64_t H, int64_t D,
                         float dropout_p, uint64_t seed, int dtype, void *stream, const int32_t *doc_start = nullptr,
-                        const int32_t *doc_end = nullptr) {
-  if (DOC && (!doc_start || !doc_end || L > INT32_MAX)) return APERTIS_ERR_ARG;
+                        const int32_t *doc_end = nullptr, int64_t window = 0) {
+  if (M == MASK_DOC && (!doc_start || !doc_end || L > INT32_MAX)) return APERTIS_ERR_ARG;
+  if (M == MASK_WINDOW && (window < 1 || L > INT32_MAX)) return APERTIS_ERR_ARG;
   const int rc = attn_check({q, k, v, out, dout, lse, workspace, dq, dk, dv}, {q_rs, k_rs, v_rs, out_rs, dout_rs, d_rs}, B, L,
                             H, D, dropout_p, dtype);
   if (rc) return rc;
   if (B == 0 || L == 0) return APERTIS_OK;
-  Args<DOC> a{};
+  Args<M> a{};
   static_cast<AttnArgs &>(a) = make_args(L, H, D, dropout_p, seed);
   a.q = q; a.k = k; a.v = v; a.o = out; a.dout = dout; a.lse = (float *)lse; a.key_valid = key_valid; a.dsum = workspace;
   a.dq = dq; a.dk = dk; a.dv = dv;
   a.q_rs = q_rs; a.k_rs = k_rs; a.v_rs = v_rs; a.o_rs = out_rs; a.do_rs = dout_rs; a.d_rs = d_rs;
-  if constexpr (DOC) { a.doc_start = doc_start; a.doc_end = doc_end; }
-  return dispatch<true, CAUSAL, DOC>(a, B, D, dtype, dropout_p > 0.f, (hipStream_t)stream);
+  if constexpr (M == MASK_DOC) { a.doc_start = doc_start; a.doc_end = doc_end; }
+  if constexpr (M == MASK_WINDOW) a.window = window;
+  return dispatch<true, CAUSAL, M>(a, B, D, dtype, dropout_p > 0.f, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -465,12 +499,12 @@ extern "C" int apertis_attention_full_bwd(const void *q, int64_t q_rs, const voi
                                     B, L, H, D, dropout_p, seed, dtype, stream);
 }
 
-// the document-masked causal pair (packed rows): the same checks, null doc_start / doc_end refused, the DOC = true kernels
+// the document-masked causal pair (packed rows): the same checks, null doc_start / doc_end refused, the MASK_DOC kernels
 extern "C" int apertis_attention_doc_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
                                          const int64_t *key_valid, const int32_t *doc_start, const int32_t *doc_end, void *out,
                                          int64_t out_rs, float *lse, int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p,
                                          uint64_t seed, int dtype, void *stream) {
-  return attention_fwd_entry<true, true>(q, q_rs, k, k_rs, v, v_rs, key_valid, out, out_rs, lse, B, L, H, D, dropout_p, seed, dtype,
+  return attention_fwd_entry<true, MASK_DOC>(q, q_rs, k, k_rs, v, v_rs, key_valid, out, out_rs, lse, B, L, H, D, dropout_p, seed, dtype,
                                          stream, doc_start, doc_end);
 }
 
@@ -479,6 +513,24 @@ extern "C" int apertis_attention_doc_bwd(const void *q, int64_t q_rs, const void
                                          const int64_t *key_valid, const int32_t *doc_start, const int32_t *doc_end,
                                          float *workspace, void *dq, void *dk, void *dv, int64_t d_rs, int64_t B, int64_t L,
                                          int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream) {
-  return attention_bwd_entry<true, true>(q, q_rs, k, k_rs, v, v_rs, out, out_rs, dout, dout_rs, lse, key_valid, workspace, dq, dk, dv,
+  return attention_bwd_entry<true, MASK_DOC>(q, q_rs, k, k_rs, v, v_rs, out, out_rs, dout, dout_rs, lse, key_valid, workspace, dq, dk, dv,
                                          d_rs, B, L, H, D, dropout_p, seed, dtype, stream, doc_start, doc_end);
+}
+
+// the sliding-window causal pair: the same checks, window < 1 refused, the MASK_WINDOW kernels
+extern "C" int apertis_attention_window_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                            const int64_t *key_valid, int64_t window, void *out, int64_t out_rs, float *lse,
+                                            int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype,
+                                            void *stream) {
+  return attention_fwd_entry<true, MASK_WINDOW>(q, q_rs, k, k_rs, v, v_rs, key_valid, out, out_rs, lse, B, L, H, D, dropout_p, seed,
+                                                dtype, stream, nullptr, nullptr, window);
+}
+
+extern "C" int apertis_attention_window_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                            const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
+                                            const int64_t *key_valid, int64_t window, float *workspace, void *dq, void *dk, void *dv,
+                                            int64_t d_rs, int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed,
+                                            int dtype, void *stream) {
+  return attention_bwd_entry<true, MASK_WINDOW>(q, q_rs, k, k_rs, v, v_rs, out, out_rs, dout, dout_rs, lse, key_valid, workspace, dq,
+                                                dk, dv, d_rs, B, L, H, D, dropout_p, seed, dtype, stream, nullptr, nullptr, window);
 }

@@ -879,8 +879,11 @@ class ApertisAttention(nn.Module):
             q, k = ops.rope_qk(q, k, None if default_pos else pos_ids, *self._rope_tables(),
                                in_range=layout is not None and att_mask.layout_pos)
         heads, p = self.num_attention_heads, self.attention_dropout.p
-        if layout is not None:
+        window = att_mask.window if att_mask is not None else None
+        if layout is not None:                   # (packed rows under a window: the model clipped the layout, ops.window_layout)
             ctxv = ops.document_attention(q, k, v, heads, layout, key_valid, p, self.training)
+        elif window is not None and q.shape[1] > window:
+            ctxv = ops.window_attention(q, k, v, heads, window, key_valid, p, self.training, dead_rows=dead_rows)
         else:
             ctxv = ops.causal_attention(q, k, v, heads, key_valid, p, self.training, dead_rows=dead_rows)
         return self.out_proj(ctxv), ((k, v) if use_c else None)
@@ -928,7 +931,10 @@ class ApertisAttention(nn.Module):
             ctxv = ops.attention_decode_at(q, cache, layer, self.num_attention_heads)
         else:
             q = ops.kv_append_rope(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
-            ctxv = ops.attention_decode(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
+            if att_mask.window is None:
+                ctxv = ops.attention_decode(q, cache, layer, self.num_attention_heads, att_mask.key_valid)
+            else:                                                      # (only the last `window` rows of the cache are read)
+                ctxv = ops.attention_decode(q, cache, layer, self.num_attention_heads, att_mask.key_valid, window=att_mask.window)
         return self.out_proj(ctxv.unsqueeze(1)), cache
 
     def _chunk_ok(self, q, att_mask, past_kv, output_att, use_c):
@@ -944,6 +950,8 @@ class ApertisAttention(nn.Module):
             return False
         cache, kv = past_kv.cache, att_mask.key_valid
         n = cache.lengths[past_kv.layer]
+        if att_mask.window is not None and n + q.shape[1] > att_mask.window:
+            return False                         # (the chunk kernels have no window predicate: the stock branch applies the band)
         return (n + q.shape[1] <= cache.capacity and att_mask.pos_host == n
                 and (kv is None or tuple(kv.shape) == (q.shape[0], n + q.shape[1])))
 
@@ -982,8 +990,9 @@ class ApertisAttention(nn.Module):
         else:
             # decode with a plain-tensor KV cache (or what the decode kernels do not take of a KVCache: its views are the
             # past), output_attentions, other head dims, CPU, left padding without ops.ATTN_LEFT_PAD: stock torch.
+            window = None
             if isinstance(att_mask, _AttnMask):
-                att_mask = att_mask.additive()
+                window, att_mask = att_mask.window, att_mask.additive()
             k, v = self.k_proj(x), self.v_proj(x)
             if self.rope is not None:
                 q, k = self.rope(q, pos_ids), self.rope(k, pos_ids)
@@ -996,6 +1005,8 @@ class ApertisAttention(nn.Module):
                 i = torch.arange(Lq, device=x.device).unsqueeze(1) + (Lk - Lq)
                 att_mask = torch.zeros(Lq, Lk, device=x.device, dtype=qh.dtype).masked_fill_(
                     i < torch.arange(Lk, device=x.device).unsqueeze(0), torch.finfo(qh.dtype).min)
+            if window is not None and Lk > window:                 # the same band the kernels apply (ops.ATTN_WINDOW)
+                att_mask = _band_mask(att_mask, window, Lq, Lk, qh)
             if output_att:
                 scores = qh @ kh.transpose(-1, -2) / math.sqrt(self.attention_head_size)
                 probs = F.softmax(scores + att_mask if att_mask is not None else scores, dim=-1)
@@ -1134,6 +1145,31 @@ class ApertisFeedForward(nn.Module):
         return _dropout_add(self.output_dropout, out, hidden_s), lb, rz
 
 
+def _active_window(cfg):
+    """The sliding window a standard_mha model honours: `cfg.sliding_window` when ops.ATTN_WINDOW is on, else None (the
+    reference never reads the field, and neither does the default path).  With the switch on the field is None or an
+    integer >= 1: anything else raises ValueError, at the first forward."""
+    w = cfg.sliding_window
+    if not ops.ATTN_WINDOW or w is None or cfg.attention_type != "standard_mha":
+        return None
+    if isinstance(w, bool) or not isinstance(w, int) or w < 1:
+        raise ValueError(f"sliding_window must be None or an integer >= 1 under ops.ATTN_WINDOW, got {w!r}")
+    return w
+
+
+def _band_mask(att_mask, window, Lq, Lk, like):
+    """The stock branch's additive mask with the sliding-window band on top: query row i sits at key position Lk - Lq + i and
+    keeps keys above that position minus `window`.  One additive term, clamped back to finfo.min so that a row the mask
+    already emptied stays the uniform row it was (two finfo.min would add up to -inf).  att_mask None: the band alone (a
+    single-token step without padding has no mask)."""
+    like = like if att_mask is None else att_mask
+    lo = torch.finfo(like.dtype).min
+    i = torch.arange(Lq, device=like.device).unsqueeze(1) + (Lk - Lq)
+    band = torch.zeros(Lq, Lk, device=like.device, dtype=like.dtype).masked_fill_(
+        torch.arange(Lk, device=like.device).unsqueeze(0) <= i - window, lo)
+    return band if att_mask is None else (att_mask + band).clamp_(min=lo)
+
+
 class _AttnMask:
     """What a standard_mha layer receives as its mask from ApertisModel.forward: the raw key validity [B, L] (None: nothing
     padded) for the fused kernels, whether the fused path may run (no query row without a valid key), whether the positions
@@ -1149,13 +1185,17 @@ class _AttnMask:
     `layout` (packed rows, `document_ids`): the ops.DocumentLayout of this forward, computed once; the fused path then runs
     ops.document_attention, and the additive mask is the block-diagonal causal one.  `layout_pos`: the positions the layers
     receive are the layout's own (positions within each document, all in [0, L)), so the per-layer RoPE call does not
-    range-check them on the host again."""
+    range-check them on the host again.
+    `window`: the active sliding window (_active_window: None unless ops.ATTN_WINDOW is on and the configuration sets one) -
+    a query attends its last `window` keys only.  Every path reads it: ops.window_attention, ops.attention_decode(window=),
+    and the stock branch as a band on its additive mask; the chunk kernels and the graph replay decline once it matters.  A
+    packed forward carries it in `layout` instead (ops.window_layout clipped the bounds), so `window` is None there."""
     __slots__ = ("key_valid", "fused_ok", "default_pos", "_make", "_additive", "decode_ok", "pos_host", "step_cache", "dead_rows",
-                 "layout", "layout_pos")
+                 "layout", "layout_pos", "window")
 
     def __init__(self, key_valid, fused_ok, default_pos, make_additive, decode_ok=False, pos_host=None, step_cache=None,
                  dead_rows=False, layout=None, layout_pos=False):
-        self.layout, self.layout_pos = layout, layout_pos
+        self.layout, self.layout_pos, self.window = layout, layout_pos, None
         self.key_valid, self.fused_ok, self.default_pos = key_valid, fused_ok, default_pos
         self._make, self._additive = make_additive, None
         self.decode_ok, self.pos_host, self.step_cache = decode_ok, pos_host, step_cache
@@ -1426,6 +1466,9 @@ class ApertisModel(nn.Module):
                 raise ValueError("document_ids: a packed selective_ssm forward returns no attention weights (output_attentions)")
             mask = _SsmDocs(layout)
         elif layout is not None:
+            window = _active_window(cfg)
+            if window is not None and x.shape[1] > window:        # the documents' bounds clipped to the window, once per forward
+                layout = ops.window_layout(layout, window)
             mask = _AttnMask(None, True, False, lambda: self._document_additive_mask(layout, x.dtype), layout=layout,
                              layout_pos=own_pos)
         elif ssm:
@@ -1436,6 +1479,7 @@ class ApertisModel(nn.Module):
                                         past_len if own_pos and kv_cache is not None
                                         and (x.shape[1] == 1 or kv_cache.multi_token) else None,
                                         kv_cache if dev_step else None)
+            mask.window = _active_window(cfg)
 
         all_hs, all_att, all_cache = [], [], []
         lbs, rzs = [], []
@@ -1886,6 +1930,9 @@ class ApertisForCausalLM(nn.Module):
             return False
         attn = self.model.layers[0].attention
         n, (B, cap, _) = past.length, past.k[0].shape
+        window = _active_window(self.config)
+        if window is not None and n + left > window:
+            return False                         # (the replayed step reads its key count on the device: no window there)
         want = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else attn.q_proj.weight.dtype
         if not (n == tokens.shape[1] - 1 and B == tokens.shape[0] and n + left <= cap and past.dtype == want
                 and len(past) == len(self.model.layers) and ops.attention_decode_supported(past.k[0], attn.num_attention_heads)

@@ -3,6 +3,8 @@ preallocated KV cache (KVCache): single-token steps (kv_append_rope, attention_d
 (kv_append_rope_chunk, attention_chunk); the dead query rows of a left-padded batch (attention_dead_rows).  The vision tower's
 bidirectional attention (full_attention, full_attention_qkv: the same kernels with the diagonal compiled out).  Packed rows
 (document_layout, document_attention: the causal kernels under a document mask, with the tiles of other documents skipped).
+Sliding windows, opt-in (ATTN_WINDOW; window_attention, window_layout, attention_decode(window=): the causal kernels with
+bounds computed from the query index, packed rows on a clipped layout, a decode step that reads the last W cache rows).
 
 Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autograd bookkeeping only; every computation is a
 HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip, csrc/attention_deadrows.hip).
@@ -23,6 +25,10 @@ ATTN_FUSED = True
 # its dead query rows - no valid key at or before their own position - are filled in by attention_dead_rows below.  OFF by
 # default (APERTIS_MHA_LEFT_PAD=1 turns it on): tests pin that such a batch runs the stock path under the default switches
 ATTN_LEFT_PAD = os.environ.get("APERTIS_MHA_LEFT_PAD", "0") == "1"
+# a standard_mha model honours `config.sliding_window` (query i attends the last W keys, its own included) on every path:
+# window_attention, document_attention on a clipped layout, attention_decode(window=), a band on the stock branch.  OFF by
+# default (APERTIS_MHA_WINDOW=1 turns it on): the reference never reads the field, and neither does the default path
+ATTN_WINDOW = os.environ.get("APERTIS_MHA_WINDOW", "0") == "1"
 
 
 # ------------------------------------------------------------------------------------------------------ operand checks
@@ -183,24 +189,32 @@ class DocumentLayout:
         self.start, self.end, self.positions, self.pairs = start, end, positions, pairs
 
 
-# csrc/attention.hip has ONE kernel set templated on <CAUSAL, DOC> behind three pairs of entry points, and this is all that
-# differs between them on the host: form -> (forward launch, backward launch, forward work(B, L, H, D, layout) in flops -
-# two products over the pairs the mask keeps; the backward's is 2.5 times it - and whether layout.start / layout.end follow
-# key_valid in both argument lists)
+def window_pairs(L, window):
+    """The (query, key) pairs a sliding window of `window` keys keeps in one causal row of L tokens: sum_i min(i + 1, window)."""
+    w = min(int(window), L)
+    return w * (w + 1) // 2 + (L - w) * w
+
+
+# csrc/attention.hip has ONE kernel set templated on <CAUSAL, mask mode> behind four pairs of entry points, and this is all
+# that differs between them on the host: form -> (forward launch, backward launch, forward work(B, L, H, D, layout) in flops -
+# two products over the pairs the mask keeps; the backward's is 2.5 times it - and what follows key_valid in both argument
+# lists: layout.start / layout.end of "doc", the window of "window" - `layout` is then that integer - else nothing)
 _FORMS = {
     "causal": ("apertis_attention_fwd", "apertis_attention_bwd", lambda B, L, H, D, layout: 4.0 * B * H * D * L * (L + 1) / 2,
-               False),
+               lambda layout: ()),
     "full": ("apertis_attention_full_fwd", "apertis_attention_full_bwd", lambda B, L, H, D, layout: 4.0 * B * H * D * L * L,
-             False),
+             lambda layout: ()),
     "doc": ("apertis_attention_doc_fwd", "apertis_attention_doc_bwd", lambda B, L, H, D, layout: 4.0 * H * D * layout.pairs,
-            True),
+            lambda layout: (ptr(layout.start), ptr(layout.end))),
+    "window": ("apertis_attention_window_fwd", "apertis_attention_window_bwd",
+               lambda B, L, H, D, layout: 4.0 * B * H * D * window_pairs(L, layout), lambda layout: (int(layout),)),
 }
 
 
 def _attn_fwd(form, q, q_rs, k, k_rs, v, v_rs, key_valid, layout, B, L, W, heads, p, seed):
     """One forward launch of `form`: (O [B, L, W] packed, LSE [B, heads, L] fp32)."""
-    name, _, work, doc = _FORMS[form]
-    bounds = (ptr(layout.start), ptr(layout.end)) if doc else ()
+    name, _, work, bounds = _FORMS[form]
+    bounds = bounds(layout)
     out = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
     lse = torch.empty(B, heads, L, device=q.device, dtype=torch.float32)
     _launch(name, getattr(_lib.load(), name),
@@ -212,8 +226,8 @@ def _attn_fwd(form, q, q_rs, k, k_rs, v, v_rs, key_valid, layout, B, L, W, heads
 def _attn_bwd(form, q, q_rs, k, k_rs, v, v_rs, out, dout, lse, key_valid, layout, dq, dk, dv, d_rs, B, L, W, heads, p, seed):
     """One backward launch of `form` into dq, dk, dv (one row stride d_rs).  The incoming gradient is whatever autograd hands
     over: another dtype is cast, and rows the kernels cannot take as they are (_rows, _aligned_rows) are copied."""
-    _, name, work, doc = _FORMS[form]
-    bounds = (ptr(layout.start), ptr(layout.end)) if doc else ()
+    _, name, work, bounds = _FORMS[form]
+    bounds = bounds(layout)
     lib = _lib.load()
     dout = dout.to(q.dtype)
     dout, do_rs = _aligned_rows(*_rows(dout, W), W)
@@ -225,8 +239,8 @@ def _attn_bwd(form, q, q_rs, k, k_rs, v, v_rs, out, dout, lse, key_valid, layout
 
 
 class _Attention(torch.autograd.Function):
-    """causal_attention, full_attention and document_attention (`form`, a key of _FORMS; `layout`: the DocumentLayout of
-    "doc", else None)."""
+    """causal_attention, full_attention, document_attention and window_attention (`form`, a key of _FORMS; `layout`: the
+    DocumentLayout of "doc", the window - a host integer - of "window", else None)."""
 
     @staticmethod
     def forward(ctx, form, q, k, v, heads, key_valid, p, seed, layout=None):
@@ -237,14 +251,14 @@ class _Attention(torch.autograd.Function):
         out, lse = _attn_fwd(form, q, q_rs, k, k_rs, v, v_rs, key_valid, layout, B, L, W, heads, p, seed)
         doc = (layout.start, layout.end) if form == "doc" else ()
         ctx.save_for_backward(q, k, v, out, lse, key_valid, *doc)
-        ctx.cfg = (form, heads, p, seed, layout.pairs if doc else None)
+        ctx.cfg = (form, heads, p, seed, layout.pairs if doc else layout)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse, key_valid, *doc = ctx.saved_tensors
         form, heads, p, seed, pairs = ctx.cfg
-        layout = DocumentLayout(*doc, None, pairs) if doc else None
+        layout = DocumentLayout(*doc, None, pairs) if doc else pairs         # (the window of "window"; None otherwise)
         B, L, W = q.shape
         dq = torch.empty(B, L, W, device=q.device, dtype=q.dtype)
         dk = torch.empty_like(dq)
@@ -403,6 +417,70 @@ def document_attention(q, k, v, heads, layout, key_valid=None, dropout_p=0.0, tr
     key_valid = _key_valid_exact("document_attention", key_valid, B, L)
     p, seed = _dropout("document_attention", dropout_p, training)
     return _Attention.apply("doc", q, k, v, int(heads), key_valid, p, seed, layout)
+
+
+# ------------------------------------------------------------------------------------------------- sliding-window attention
+def _window(what, window):
+    """The window as the host integer the launches take: >= 1, else ValueError (bool and float are not integers here)."""
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"{what}: window must be an integer >= 1, got {window!r}")
+    return min(window, 2 ** 63 - 1)
+
+
+def window_attention(q, k, v, heads, window, key_valid=None, dropout_p=0.0, training=False, dead_rows=False):
+    """causal_attention under a SLIDING WINDOW: query i attends key j iff max(0, i - window + 1) <= j <= i (and key_valid) -
+    `window` keys, its own included; a host integer >= 1 (ValueError otherwise), any value >= L is the plain causal mask with
+    causal_attention's bits.  The layout contract, the dropout hash and seed, the saved tensors, the determinism of the
+    backward and the inference-only dead_rows fill are causal_attention's (a dead row of a windowed forward is still one with
+    no valid key at or before it, and gets the column mean over all L keys: the reference's value under its full mask).  The
+    kernels are the causal ones with bounds computed from the index (csrc/attention.hip, MASK_WINDOW): nothing is loaded for
+    them, key tiles in front of a wave's window and query tiles past it are never touched, and every output and gradient has
+    the bits of document_attention on window_layout((B, L), window, device).  Work: 4*B*heads*D*sum_i min(i + 1, window)
+    flops forward."""
+    window = _window("window_attention", window)
+    _require_gpu(q, k, v, key_valid)
+    if dead_rows:
+        _dead_rows_inference("window_attention", training, dropout_p, q, k, v)
+    if not (q.shape == k.shape == v.shape and q.dtype == k.dtype == v.dtype) or not attention_supported(q, heads):
+        raise ApertisHipError(f"window_attention: q/k/v {tuple(q.shape)} {q.dtype} with {heads} heads (D 64 or 128, fp32 or bf16, "
+                              "one shape and dtype)")
+    B, L, _ = q.shape
+    key_valid = _key_valid_exact("window_attention", key_valid, B, L)
+    p, seed = _dropout("window_attention", dropout_p, training)
+    out = _Attention.apply("window", q, k, v, int(heads), key_valid, p, seed, window)
+    if dead_rows and key_valid is not None and B:
+        attention_dead_rows(out, v, key_valid)
+    return out
+
+
+_WINDOW_ARRAYS = {}          # (L, window, device) -> (start, end) int32 [L] of a row that is one document: window_layout
+
+
+def window_layout(layout_or_shape, window, device=None):
+    """The DocumentLayout of a sliding window of `window` keys (an integer >= 1): for a shape (B, L), start[b, i] =
+    max(0, i - window + 1) and end[b, j] = min(L, j + window) on `device`; for a packed DocumentLayout, its bounds clipped to
+    the window, start = max(doc_start, i - window + 1), end = min(doc_end, j + window) (on the layout's device) - a document
+    shorter than the window keeps its triangle.  `positions` are the layout's own (0..L-1 for a shape), `pairs` is recomputed
+    on the host for a shape and with ONE host read for a layout.  document_attention on the result is the windowed attention,
+    on the document kernels as they are.  The unclipped arrays are built once per (L, window, device)."""
+    window = _window("window_layout", window)
+    lay = layout_or_shape if isinstance(layout_or_shape, DocumentLayout) else None
+    B, L = (tuple(lay.start.shape) if lay is not None else tuple(int(n) for n in layout_or_shape))
+    if L >= 2 ** 31:
+        raise ValueError(f"window_layout: rows of {L} tokens do not fit the int32 layout")
+    device = torch.device(lay.start.device if lay is not None else (device if device is not None else "cpu"))
+    key = (L, min(window, L), str(device))
+    if key not in _WINDOW_ARRAYS:
+        idx = torch.arange(L, device=device, dtype=torch.int64)
+        _WINDOW_ARRAYS[key] = ((idx - (key[1] - 1)).clamp_(min=0).to(torch.int32), (idx + key[1]).clamp_(max=L).to(torch.int32))
+    ws, we = _WINDOW_ARRAYS[key]
+    if lay is None:
+        positions = torch.arange(L, device=device, dtype=torch.int64).unsqueeze(0).expand(B, L)
+        return DocumentLayout(ws.unsqueeze(0).expand(B, L).contiguous(), we.unsqueeze(0).expand(B, L).contiguous(), positions,
+                              B * window_pairs(L, window))
+    start, end = torch.maximum(lay.start, ws), torch.minimum(lay.end, we)
+    pairs = int((torch.arange(1, L + 1, device=device) - start).sum()) if B and L else 0
+    return DocumentLayout(start.contiguous(), end.contiguous(), lay.positions, pairs)
 
 
 # ------------------------------------------------------------------------------------------- bidirectional attention
@@ -683,24 +761,33 @@ def attention_decode_splits(B, heads, Lk, D):
     return int(_lib.load().apertis_attention_decode_splits(B, heads, Lk, D))
 
 
-def attention_decode(q, cache, layer, heads, key_valid=None, splits=0):
+def attention_decode(q, cache, layer, heads, key_valid=None, splits=0, window=None):
     """softmax(q K^T / sqrt(D)) V for ONE query row per sequence and head over the rows layer `layer` of `cache` holds
     (Lk = lengths[layer]: after kv_append_rope, the new token's own key included).  q: [B, W] or [B, 1, W] in the cache's dtype
     (fp32 or bf16, D = W / heads in {64, 128}); returns O [B, W] where out_proj reads it.  key_valid: [B, >= Lk] (the raw
     attention_mask, nonzero = attend; columns >= Lk are never read) or None.  splits: 0 = apertis_attention_decode_splits'
     choice, else 1..min(Lk, ATTN_DECODE_MAX_SPLITS) pieces of the key range (tests reach every value); the same inputs and split count give
-    the same bits."""
+    the same bits.
+    window (an integer >= 1, or None): only the last `window` rows count (a sliding window: the query is the newest row).
+    With Lk > window the SAME launch runs on k, v and key_valid offset by begin = Lk - window rows / columns, with Lk' =
+    window and capacity' = capacity - begin: nothing is copied, the split count is chosen for Lk', and rows before `begin`
+    are never read.  With Lk <= window the call is the one without a window."""
     _require_gpu(q, cache.k[layer], key_valid)
     lib = _lib.load()
     kc, vc = cache.k[layer], cache.v[layer]
     B, cap, W = kc.shape
     Lk = cache.lengths[layer]
-    n = int(splits) if splits else lambda D: int(lib.apertis_attention_decode_splits(B, heads, max(Lk, 1), D)) if B else 1
+    begin = max(Lk - _window("attention_decode", window), 0) if window is not None else 0
+    n = int(splits) if splits else lambda D: int(lib.apertis_attention_decode_splits(B, heads, max(Lk - begin, 1), D)) if B else 1
     q, q_rs, D, ws, out = _decode_operands("attention_decode", lib, q, cache, layer, heads, n)
     key_valid, kv_rs = _mask_rows("attention_decode", key_valid, B, Lk)
-    nbytes = 2.0 * B * Lk * W * q.element_size()
+    # (pointer arithmetic on the host, no views: the launch reads the same buffers from row / column `begin` on)
+    es, cap, Lk = q.element_size(), cap - begin, Lk - begin
+    kp, vp = ptr(kc) + begin * kc.stride(1) * es, ptr(vc) + begin * vc.stride(1) * es
+    kvp = ptr(key_valid) + begin * 8 if key_valid is not None else None
+    nbytes = 2.0 * B * Lk * W * es
     _launch("apertis_attention_decode", lib.apertis_attention_decode,
-            (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
+            (ptr(q), q_rs, kp, kc.stride(1), kc.stride(0), vp, vc.stride(1), vc.stride(0), cap, kvp, kv_rs,
              ptr(out), W, ptr(ws), B, Lk, heads, D, int(splits), dtype_code(q), stream_ptr()),
             work=4.0 * B * Lk * W, detail=f"{B}x{heads}x{D}", nbytes=nbytes)
     return out

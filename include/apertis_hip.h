@@ -61,7 +61,8 @@ extern "C" {
  * So did the document-masked causal pair of packed rows (apertis_attention_doc_fwd / _bwd): still 4.12, 117 entry points.
  * So did the left-padded form of the conv forward (apertis_dwconv_silu_start_fwd): still 4.12, 118 entry points.
  * So did the packed-row forms of the SSM block (apertis_dwconv_silu_doc_fwd / _bwd, apertis_tiny_linear_doc_fwd): still 4.12,
- * 121 entry points. */
+ * 121 entry points.
+ * So did the sliding-window causal pair (apertis_attention_window_fwd / _bwd): still 4.12, 123 entry points. */
 #define APERTIS_ABI_VERSION ((4 << 16) | 12)
 int apertis_abi_version(void);
 /* Name of the code-object architecture this library was compiled for ("gfx950"). */
@@ -875,6 +876,27 @@ int apertis_attention_doc_bwd(const void *q, int64_t q_rs, const void *k, int64_
                               const int64_t *key_valid, const int32_t *doc_start, const int32_t *doc_end, float *workspace,
                               void *dq, void *dk, void *dv, int64_t d_rs, int64_t B, int64_t L, int64_t H, int64_t D,
                               float dropout_p, uint64_t seed, int dtype, void *stream);
+
+/* The causal pair under a SLIDING WINDOW of `window` keys, the query's own included:
+ *   O[b,i,h] = sum_{max(0, i - window + 1) <= j <= i, key_valid[b,j] != 0} drop(P[i,j]) V[b,j,h],  P = softmax over those j.
+ *   window        : by value, >= 1 (else APERTIS_ERR_ARG before any launch); any value >= L is the plain causal mask.  It is
+ *                   compared in 64 bits and only masks: no address is formed from it.  L > INT32_MAX is APERTIS_ERR_ARG, as
+ *                   for the document pair.
+ * The document pair's argument lists with `window` in place of doc_start, doc_end; every other argument, layout, limit, check,
+ * the dropout hash, the workspace (apertis_attention_bwd_workspace_bytes) and the determinism of the backward are those of
+ * apertis_attention_fwd / _bwd, and the kernels are the same templates.  The bounds are a function of the index: nothing is
+ * loaded for them.  A wave's key loop starts at the tile of max(0, q0 - window + 1) (q0: its first query) and its dK/dV query
+ * loop ends at min(L, k_last + window): the work is L*window, not L*L/2.  Every output has the bits of apertis_attention_doc_fwd /
+ * _bwd given doc_start[b,i] = max(0, i - window + 1), doc_end[b,j] = min(L, j + window), and with window >= L those of
+ * apertis_attention_fwd / _bwd. */
+int apertis_attention_window_fwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                 const int64_t *key_valid, int64_t window, void *out, int64_t out_rs, float *lse, int64_t B,
+                                 int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed, int dtype, void *stream);
+int apertis_attention_window_bwd(const void *q, int64_t q_rs, const void *k, int64_t k_rs, const void *v, int64_t v_rs,
+                                 const void *out, int64_t out_rs, const void *dout, int64_t dout_rs, const float *lse,
+                                 const int64_t *key_valid, int64_t window, float *workspace, void *dq, void *dk, void *dv,
+                                 int64_t d_rs, int64_t B, int64_t L, int64_t H, int64_t D, float dropout_p, uint64_t seed,
+                                 int dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * standard_mha single-token decode against a preallocated KV cache (the attention of core.py:639-700 with a past):
