@@ -1,5 +1,5 @@
 // MoE routing for gfx950: gate softmax/top-k (plain, with the auxiliary losses, noisy) and the dispatch plan (histogram +
-// capacity + radix-select + stable ranks).  The gather-LayerNorm and the weighted combine are in layernorm.hip.
+// capacity + overflow thresholds + stable ranks).  The gather-LayerNorm and the weighted combine are in layernorm.hip.
 //
 // Reference: AdaptiveExpertSystem.forward, /root/reference/src/model/core.py:470-607.
 // The reference walks a K x E Python loop with host syncs (nonzero / .any() / topk); here the
@@ -72,9 +72,10 @@ __global__ void gate_topk_bwd_k(const float *__restrict__ gates, const int32_t *
 constexpr int PLAN_HIST_BLOCKS = 512;   // most work-groups of the candidate histogram (each leaves one row of counts)
 struct PlanWs {
   int32_t *total, *keep, *mode, *quota, *seg_start, *bpart;   // bpart [PLAN_HIST_BLOCKS][P]: the histogram launch's rows
-  uint32_t *thr, *smask;   // radix select: prefix found so far / bits already fixed
-  int32_t *ghist;          // [P][256] digit histogram of the current radix pass
-  int32_t *done;           // [4] work-groups of plan_sel_hist_k that have added their bins, per digit (right behind ghist: one memset)
+  uint32_t *thr;           // [P] overflowing slot: the keep-th largest key (quota: how many of the ties at it are kept)
+  int32_t *cstart;         // [P] overflowing slot: where its candidates start in cand
+  int32_t *cbase;          // [PLAN_HIST_BLOCKS][P] exclusive prefix of bpart's columns: where a work-group's candidates start in the slot's run
+  uint32_t *cand;          // [S*K] the overflowing slots' candidate keys, slot after slot
   int32_t *cnt_g, *cnt_t;  // [P][NCH]
   int P, NCH;
 };
@@ -90,12 +91,12 @@ PlanWs carve_ws(void *ws, int64_t S, int64_t E, int64_t K) {
   w.quota = p; p += w.P;
   w.seg_start = p; p += w.P;
   w.thr = (uint32_t *)p; p += w.P;
-  w.smask = (uint32_t *)p; p += w.P;
-  w.ghist = p; p += (int64_t)w.P * 256;
-  w.done = p; p += 4;
+  w.cstart = p; p += w.P;
   w.cnt_g = p; p += (int64_t)w.P * w.NCH;
   w.cnt_t = p; p += (int64_t)w.P * w.NCH;
-  w.bpart = p;   // [PLAN_HIST_BLOCKS][P]
+  w.bpart = p; p += (int64_t)PLAN_HIST_BLOCKS * w.P;
+  w.cbase = p; p += (int64_t)PLAN_HIST_BLOCKS * w.P;
+  w.cand = (uint32_t *)p;   // [S*K]
   return w;
 }
 
@@ -129,26 +130,44 @@ plan_hist_k(const int32_t *__restrict__ idx, int32_t *__restrict__ bpart, int64_
   for (int i = threadIdx.x; i < P; i += blockDim.x) bpart[(int64_t)blockIdx.x * P + i] = h[i];
 }
 
-// per expert: consume capacity k-major (core.py:547-576); then lay the segments out expert-major
+// per expert: consume capacity k-major (core.py:547-576); then lay the segments out expert-major.  Also where every
+// work-group's candidates of a slot go in the compacted candidate array (plan_compact_k): cbase, cstart.
 __global__ void plan_capacity_k(PlanWs w, const uint8_t *__restrict__ active, int64_t capacity,
                                 int32_t *__restrict__ offsets, int E, int K, int nhist) {
   // totals: the histogram launch's per-work-group rows (integers: any order gives the same sums).  256 threads, 256 / P of them
-  // per slot when the slots are few
+  // per slot when the slots are few, each with a run of consecutive rows: the sums of the runs before a thread's own are
+  // where its rows' exclusive prefixes (cbase) start
   __shared__ int32_t s_sum[256];
   {
     const int P = E * K;
     const int g = P < 256 ? 256 / P : 1;                 // threads per slot
-    for (int p0 = 0; p0 < P; p0 += 256 / g) {
-      const int p = p0 + (int)threadIdx.x / g, sub = (int)threadIdx.x % g;
+    const int per = (nhist + g - 1) / g;                 // rows per thread
+    const int pc = 256 / g;                              // slots per trip; neighbouring threads hold neighbouring slots of one row
+    for (int p0 = 0; p0 < P; p0 += pc) {
+      const int p = p0 + (int)threadIdx.x % pc, sub = (int)threadIdx.x / pc;
+      const bool on = p < P && sub < g;
+      const int b0 = min(sub * per, nhist), b1 = min(b0 + per, nhist);
       int t = 0;
-      if (p < P && (int)threadIdx.x / g < 256 / g)
-        for (int b = sub; b < nhist; b += g) t += w.bpart[(int64_t)b * P + p];
+      if (on)
+        for (int b = b0; b < b1; ++b) t += w.bpart[(int64_t)b * P + p];
       s_sum[threadIdx.x] = t;
       __syncthreads();
-      if (p < P && sub == 0 && (int)threadIdx.x / g < 256 / g) {
-        int tt = 0;
-        for (int q = 0; q < g; ++q) tt += s_sum[threadIdx.x + q];
-        w.total[p] = tt;
+      if (on) {
+        int run = 0, tt = 0;
+        for (int q = 0; q < g; ++q) {
+          const int v = s_sum[q * pc + (int)threadIdx.x % pc];
+          if (q < sub) run += v;
+          tt += v;
+        }
+        if (sub == 0) w.total[p] = tt;
+        for (int b = b0; b < b1; b += 8) {   // (eight loads in flight: a load behind every store is a memory latency per row)
+          int v[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) v[u] = b + u < b1 ? w.bpart[(int64_t)(b + u) * P + p] : 0;
+#pragma unroll
+          for (int u = 0; u < 8; ++u)
+            if (b + u < b1) { w.cbase[(int64_t)(b + u) * P + p] = run; run += v[u]; }
+        }
       }
       __syncthreads();
     }
@@ -168,153 +187,156 @@ __global__ void plan_capacity_k(PlanWs w, const uint8_t *__restrict__ active, in
       }
       w.keep[p] = (int)keep;
       w.mode[p] = keep == 0 ? 0 : (keep == tot ? 1 : 2);
-      w.quota[p] = (int)keep;   // radix select: how many of the slot's candidates are still to be taken
-      w.thr[p] = 0;
-      w.smask[p] = 0;
+      w.quota[p] = (int)keep;   // (an overflowing slot: plan_select_keys_k sets the ties to keep, and thr)
       load += keep;
     }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    int run = 0;
+    int run = 0, crun = 0;
     for (int ee = 0; ee < E; ++ee) {
       offsets[ee] = run;
       for (int k = 0; k < K; ++k) {
-        w.seg_start[ee * K + k] = run;
-        run += w.keep[ee * K + k];
+        const int p = ee * K + k;
+        w.seg_start[p] = run;
+        run += w.keep[p];
+        w.cstart[p] = crun;
+        if (w.mode[p] == 2) crun += w.total[p];
       }
     }
     offsets[E] = run;
   }
 }
 
-// overflowing (e,k) slot: find the keep-th largest gate weight T (radix select on the float
-// bits; weights are >= 0 so unsigned order == float order) and how many ties at T to keep
-__global__ void __launch_bounds__(1024)
-plan_select_k(PlanWs w, const int32_t *__restrict__ idx, const float *__restrict__ wk, int64_t S, int K) {
+// The gate weights of every overflowing (mode 2) slot's candidates, gathered into one flat array: same grid and same
+// element-to-work-group mapping as plan_hist_k, so work-group b holds exactly bpart[b][p] candidates of slot p and writes
+// them from cstart[p] + cbase[b][p] on.  The rank inside the work-group comes from an LDS counter per slot that a wave
+// advances once per slot it holds (one ballot, as in plan_hist_k); the order inside a slot's run is free - the select
+// needs the multiset of keys only.  No global atomics: every word of cand has one writer.
+__global__ void __launch_bounds__(256)
+plan_compact_k(PlanWs w, const int32_t *__restrict__ idx, const float *__restrict__ wk, int64_t SK, int E, int K) {
+  __shared__ int32_t s_pos[MAXE * MAXK];   // next free word of cand for this work-group's candidates of the slot
+  __shared__ int32_t s_m2[MAXE * MAXK];    // slot overflows
+  const int P = E * K, lane = threadIdx.x & 63;
+  int any = 0;
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    const int m2 = w.mode[i] == 2;
+    s_m2[i] = m2;
+    s_pos[i] = m2 ? w.cstart[i] + w.cbase[(int64_t)blockIdx.x * P + i] : 0;
+    any |= m2;
+  }
+  if (!__syncthreads_or(any)) return;   // nothing overflows
+  const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  for (int64_t a0 = (int64_t)blockIdx.x * blockDim.x; a0 < SK; a0 += (int64_t)gridDim.x * blockDim.x) {   // (uniform trip count)
+    const int64_t a = a0 + threadIdx.x;
+    int slot = -1;
+    uint32_t bits = 0;
+    if (a < SK) {
+      const int e = idx[a];
+      bits = __float_as_uint(wk[a]);
+      if (e >= 0 && e < E) {
+        const int p = e * K + (int)(a % K);
+        if (s_m2[p]) slot = p;
+      }
+    }
+    unsigned long long todo = __ballot(slot >= 0);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const int s0 = __shfl(slot, leader);
+      const unsigned long long m = __ballot(slot == s0);
+      int base = 0;
+      if (lane == leader) base = atomicAdd(&s_pos[s0], __popcll(m));
+      base = __shfl(base, leader);
+      if (slot == s0) w.cand[base + __popcll(m & lt)] = bits;
+      todo &= ~m;
+    }
+  }
+}
+
+// Overflowing (e,k) slot, one work-group each: T = the keep-th largest key of the slot's candidates (keys are the raw bits of
+// gate weights >= 0, so unsigned order == float order) and how many of the ties at T to keep.  T is built from the top bit
+// down, two bits per round: the work-group counts the keys >= T | j << b for j = 1..3 and takes the largest j that still
+// leaves `keep` of them.  A count is a compare and an add-with-carry per key in the thread's own counters (as a ballot and a
+// scalar popcount per key the 16 waves queued up at the CU's one scalar unit: 47 us per slot of 22 500), summed over the wave
+// by DPP once per round; the 16 waves combine through 16 LDS rows (two sets, taken in turn: one barrier per round), which
+// each wave reads once, a row per lane, and sums by DPP again.  No histogram and no atomics.
+// On-chip budget: the first SEL_REG * 1024 = 32768 candidates stay in registers for all 17 rounds; a slot with more streams
+// the rest from cand (L2) every round.  Keys >= 1 are all that is ever counted, so the zero padding never counts.
+constexpr int SEL_THREADS = 1024, SEL_REG = 32, SEL_WAVES = SEL_THREADS / 64;
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
+__device__ __forceinline__ int wave_sum_i(int v) {   // (wave_sum, row_common.h, on integers)
+  v += dpp_i<0xB1, 0xf>(v);
+  v += dpp_i<0x4E, 0xf>(v);
+  v += dpp_i<0x141, 0xf>(v);
+  v += dpp_i<0x140, 0xf>(v);
+  v += dpp_i<0x142, 0xa>(v);
+  v += dpp_i<0x143, 0xc>(v);
+  return __builtin_amdgcn_readlane(v, 63);
+}
+__device__ __forceinline__ int row16_sum_i(int v) {   // sum over the lane's row of 16, in every lane
+  v += dpp_i<0xB1, 0xf>(v);
+  v += dpp_i<0x4E, 0xf>(v);
+  v += dpp_i<0x141, 0xf>(v);
+  v += dpp_i<0x140, 0xf>(v);
+  return v;
+}
+__global__ void __launch_bounds__(SEL_THREADS)
+plan_select_keys_k(PlanWs w) {
   const int p = blockIdx.x;
   if (w.mode[p] != 2) return;
-  const int e = p / K, k = p - e * K;
-  __shared__ int32_t hist[256];
-  __shared__ uint32_t s_prefix, s_mask;
-  __shared__ int32_t s_need;
-  if (threadIdx.x == 0) { s_prefix = 0; s_mask = 0; s_need = w.keep[p]; }
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-    const uint32_t prefix = s_prefix, mask = s_mask;
-    // 8 tokens per thread and trip, all 16 loads issued before the first use: one block per (e,k) walks
-    // all S tokens four times, and with one dependent load pair per trip that walk was pure latency (200 us)
-    for (int64_t s0 = threadIdx.x; s0 < S; s0 += (int64_t)blockDim.x * 8) {
-      int32_t ei[8];
-      uint32_t bi[8];
+  const int n = w.total[p], keep = w.keep[p];
+  const uint32_t *__restrict__ c = w.cand + w.cstart[p];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int4 s_c[2][SEL_WAVES];
+  uint32_t key[SEL_REG];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int64_t s = s0 + (int64_t)u * blockDim.x;
-        ei[u] = s < S ? idx[s * K + k] : -1;
-        bi[u] = s < S ? __float_as_uint(wk[s * K + k]) : 0u;
-      }
+  for (int i = 0; i < SEL_REG; ++i) {
+    const int j = i * SEL_THREADS + tid;
+    key[i] = j < n ? c[j] : 0u;
+  }
+  const int nreg = min((n + SEL_THREADS - 1) / SEL_THREADS, SEL_REG);   // register rows that hold a key at all
+  int round = 0;
+  // keys >= t1, >= t2, >= t3 in the whole slot (t1, t2, t3 >= 1); every thread gets the three sums
+  auto count3 = [&](uint32_t t1, uint32_t t2, uint32_t t3, int &n1, int &n2, int &n3) {
+    int c1 = 0, c2 = 0, c3 = 0;
 #pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (ei[u] == e && (bi[u] & mask) == prefix) atomicAdd(&hist[(bi[u] >> shift) & 255], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int need = s_need, cum = 0;
-      for (int b = 255; b >= 0; --b) {
-        if (cum + hist[b] >= need) {
-          s_need = need - cum;
-          s_prefix = prefix | ((uint32_t)b << shift);
-          s_mask = mask | (255u << shift);
-          break;
+    for (int i0 = 0; i0 < SEL_REG; i0 += 8)
+      if (i0 < nreg) {   // (eight rows per branch; a row of padding counts nothing)
+#pragma unroll
+        for (int i = i0; i < i0 + 8; ++i) {
+          c1 += key[i] >= t1;
+          c2 += key[i] >= t2;
+          c3 += key[i] >= t3;
         }
-        cum += hist[b];
       }
+    for (int j0 = SEL_REG * SEL_THREADS; j0 < n; j0 += SEL_THREADS) {   // past the budget (uniform trip count)
+      const int j = j0 + tid;
+      const uint32_t kk = j < n ? c[j] : 0u;
+      c1 += kk >= t1;
+      c2 += kk >= t2;
+      c3 += kk >= t3;
     }
+    c1 = wave_sum_i(c1); c2 = wave_sum_i(c2); c3 = wave_sum_i(c3);
+    int4 *row = s_c[round & 1];
+    ++round;
+    if (lane == 0) row[wave] = make_int4(c1, c2, c3, 0);
     __syncthreads();
+    // lane l takes wave l & 15's row: ONE LDS read per wave, then the sum over a DPP row of 16 lanes (every thread reading
+    // all 16 rows was 256 broadcast reads per round through the CU's LDS: 42 us per slot instead of 36)
+    const int4 r = row[lane & (SEL_WAVES - 1)];
+    n1 = row16_sum_i(r.x); n2 = row16_sum_i(r.y); n3 = row16_sum_i(r.z);
+  };
+  uint32_t T = 0;
+  for (int b = 30; b >= 0; b -= 2) {
+    int n1, n2, n3;
+    count3(T | (1u << b), T | (2u << b), T | (3u << b), n1, n2, n3);
+    const uint32_t j = n3 >= keep ? 3u : (n2 >= keep ? 2u : (n1 >= keep ? 1u : 0u));
+    T |= j << b;
   }
-  if (threadIdx.x == 0) { w.thr[p] = s_prefix; w.quota[p] = s_need; }
-}
-
-// one wave per slot: the bucket (from the top) where the running count reaches the slot's remaining need.  Runs in the LAST
-// work-group of plan_sel_hist_k to finish (round 6: a launch less per digit, four per plan): the bins were added by other
-// work-groups with device-scope atomics and are read here with device-scope loads (the XCDs' L2s are not coherent inside a kernel).
-__device__ __forceinline__ void plan_sel_pick(const PlanWs &w, int p, int lane, int shift) {
-  if (w.mode[p] != 2) return;
-  int32_t *h = w.ghist + p * 256;
-  // lane l owns bins 255-4l .. 252-4l (descending)
-  int c[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) c[j] = __hip_atomic_load(h + 255 - 4 * lane - j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int mine = (c[0] + c[1]) + (c[2] + c[3]);
-  int incl = mine;   // inclusive prefix over lanes 0..l
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int v = __shfl_up(incl, off);
-    if (lane >= off) incl += v;
-  }
-  const int need = w.quota[p];
-  const int before = incl - mine;
-  if (before < need && incl >= need) {   // exactly one lane
-    int cum = before, b = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (cum < need && cum + c[j] >= need) { b = 255 - 4 * lane - j; break; }
-      cum += c[j];
-    }
-    w.quota[p] = need - cum;
-    w.thr[p] = w.thr[p] | ((uint32_t)b << shift);
-    w.smask[p] = w.smask[p] | (255u << shift);
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) h[255 - 4 * lane - j] = 0;   // ready for the next digit
-}
-
-// The same radix select spread over the chip (one launch pair per 8-bit digit): every work-group histograms
-// its share of the tokens for ALL overflowing slots in LDS and adds the non-empty bins to the global
-// histogram (integer atomics: exact, order-free); the last work-group to finish then fixes the digit per slot (plan_sel_pick).  The
-// one-block-per-slot kernel above walks all S tokens four times with at most E*K blocks busy (154 us at
-// S = 131k with 8 overflowing slots); kept for P > 32 slots (LDS).
-__global__ void __launch_bounds__(256)
-plan_sel_hist_k(PlanWs w, const int32_t *__restrict__ idx, const float *__restrict__ wk, int64_t S, int E, int K, int shift, int digit) {
-  extern __shared__ int32_t lh[];   // [P][256]
-  __shared__ int32_t s_mode[32];     // (P <= 32 on this path) the slots' state, once per work-group instead of three dependent
-  __shared__ uint32_t s_mask[32], s_thr[32];   // global loads per element
-  const int P = w.P;
-  for (int i = threadIdx.x; i < P * 256; i += 256) lh[i] = 0;
-  if (threadIdx.x < P) { s_mode[threadIdx.x] = w.mode[threadIdx.x]; s_mask[threadIdx.x] = w.smask[threadIdx.x]; s_thr[threadIdx.x] = w.thr[threadIdx.x]; }
-  __syncthreads();
-  const int64_t SK = S * K;
-  for (int64_t a0 = (int64_t)blockIdx.x * 256 + threadIdx.x; a0 < SK; a0 += (int64_t)gridDim.x * 256 * 4) {
-    int32_t ei[4];
-    uint32_t bi[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int64_t a = a0 + (int64_t)u * gridDim.x * 256;
-      ei[u] = a < SK ? idx[a] : -1;
-      bi[u] = a < SK ? __float_as_uint(wk[a]) : 0u;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int64_t a = a0 + (int64_t)u * gridDim.x * 256;
-      if (ei[u] >= 0 && ei[u] < E) {
-        const int p = ei[u] * K + (int)(a % K);
-        if (s_mode[p] == 2 && (bi[u] & s_mask[p]) == s_thr[p]) atomicAdd(&lh[p * 256 + ((bi[u] >> shift) & 255)], 1);
-      }
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < P * 256; i += 256)
-    if (lh[i]) atomicAdd(&w.ghist[i], lh[i]);
-  // the last work-group to get here fixes the digit of every slot (round 5: a launch of its own per digit)
-  __threadfence();
-  __syncthreads();
-  __shared__ int s_last;
-  if (threadIdx.x == 0) s_last = atomicAdd(&w.done[digit], 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  for (int p = threadIdx.x >> 6; p < P; p += 4) plan_sel_pick(w, p, threadIdx.x & 63, shift);
+  int gt = 0, u2, u3;
+  if (T != 0xffffffffu) count3(T + 1u, 0xffffffffu, 0xffffffffu, gt, u2, u3);
+  if (tid == 0) { w.thr[p] = T; w.quota[p] = keep - gt; }
 }
 
 __device__ __forceinline__ void plan_flags(const PlanWs &w, const int32_t *idx, const float *wk, int64_t s,
@@ -684,7 +706,7 @@ extern "C" int apertis_moe_gate_topk_bwd(const float *gates, const int32_t *idx,
 
 extern "C" int64_t apertis_moe_plan_workspace_bytes(int64_t S, int64_t E, int64_t K) {
   int64_t P = E * K, NCH = ceil_div64(S > 0 ? S : 1, 64);
-  return (7 * P + 256 * P + 4 + 2 * P * NCH + PLAN_HIST_BLOCKS * P) * 4 + 64;
+  return (7 * P + 2 * P * NCH + 2 * PLAN_HIST_BLOCKS * P + (S > 0 ? S : 1) * K) * 4 + 64;
 }
 
 extern "C" int apertis_moe_plan(const int32_t *idx, const float *w, const uint8_t *active,
@@ -709,15 +731,9 @@ extern "C" int apertis_moe_plan(const int32_t *idx, const float *w, const uint8_
   hipLaunchKernelGGL(plan_capacity_k, dim3(1), dim3(256), 0, st, pw, active, capacity, expert_offsets, (int)E, (int)K, nhist);
   if (S > 0) {
     if (capacity > 0) {
-      if (pw.P <= 32) {
-        hipMemsetAsync(pw.ghist, 0, sizeof(int32_t) * (pw.P * 256 + 4), st);   // (the bins and the four arrival counters)
-        const unsigned nbh = (unsigned)std::min<int64_t>(ceil_div64(S * K, 1024), 512);
-        for (int shift = 24; shift >= 0; shift -= 8)
-          hipLaunchKernelGGL(plan_sel_hist_k, dim3(nbh), dim3(256), (size_t)pw.P * 256 * sizeof(int32_t), st, pw, idx, w, S,
-                             (int)E, (int)K, shift, 3 - shift / 8);
-      } else {
-        hipLaunchKernelGGL(plan_select_k, dim3(pw.P), dim3(1024), 0, st, pw, idx, w, S, (int)K);
-      }
+      // overflow thresholds (whether any slot overflows is known on the device only)
+      hipLaunchKernelGGL(plan_compact_k, dim3((unsigned)nhist), dim3(256), 0, st, pw, idx, w, S * K, (int)E, (int)K);
+      hipLaunchKernelGGL(plan_select_keys_k, dim3((unsigned)pw.P), dim3(SEL_THREADS), 0, st, pw);
     }
     dim3 cgrid((unsigned)ceil_div64(pw.NCH, 4)), cblock(256);
     hipLaunchKernelGGL(plan_count_k, cgrid, cblock, 0, st, pw, idx, w, S, (int)E, (int)K);

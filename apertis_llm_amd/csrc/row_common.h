@@ -56,7 +56,7 @@ __device__ __forceinline__ void gate_topk_row(const float *__restrict__ row, flo
 // The whole plan in ONE launch for a handful of tokens (S <= 64, E * K <= 16: the single-token decode step, reference
 // core.py:1578-1603 - the five launches of apertis_moe_plan were a fifth of a captured token step).  One wave per (expert, k) slot,
 // lane = token.  Same semantics: candidates idx[s, k] == e; per expert the capacity is consumed k-major; an overflowing
-// slot keeps its `keep` largest gate weights (compared as bits, as the radix select does), ties at the threshold in token
+// slot keeps its `keep` largest gate weights (compared as bits, as plan_select_keys_k does), ties at the threshold in token
 // order; the kept rows of a slot sit in token order, the slots expert-major then k.
 __device__ __forceinline__ void
 plan_small_body(const int32_t *idx, const float *wk, const uint8_t *__restrict__ active, int64_t capacity,
