@@ -206,21 +206,34 @@ SIGNATURES = {
 }
 
 
+# Entry points added after the 4.12 table (include/apertis_hip_ext.h): SIGNATURES mirrors apertis_hip.h name for name and is frozen
+# with it; these are exported by the same library under the same ABI version and bound the same way.
+EXT_SIGNATURES = {
+    # apertis_attention_decode_at with `window` after `len`
+    "apertis_attention_decode_window_at": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                  _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
+    # apertis_attention_chunk with `window` after `n`
+    "apertis_attention_chunk_window": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
+                                              _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
+}
+
+
 class _Lib:
-    """CDLL wrapper that binds each entry point on first use with its declared signature."""
+    """CDLL wrapper that binds each entry point on first use with its declared signature (either table)."""
 
     def __init__(self, cdll):
         self._cdll = cdll
 
     def __getattr__(self, name):
-        if name not in SIGNATURES:
+        table = SIGNATURES if name in SIGNATURES else EXT_SIGNATURES
+        if name not in table:
             raise AttributeError(name)
         try:
             fn = getattr(self._cdll, name)
         except AttributeError:
             raise ApertisHipError(f"{LIB_PATH} does not export {name}: rebuild with "
                                   "`python -m apertis_llm_amd.build --force`") from None
-        fn.restype, fn.argtypes = SIGNATURES[name]
+        fn.restype, fn.argtypes = table[name]
         setattr(self, name, fn)
         return fn
 

@@ -29,7 +29,7 @@ def _hipcc():
 
 def _deps_mtime():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs.append(os.path.join(HERE, "..", "include", "apertis_hip.h"))
+    hdrs += [os.path.join(HERE, "..", "include", h) for h in ("apertis_hip.h", "apertis_hip_ext.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -77,14 +77,6 @@ __device__ __forceinline__ int rows16_max(int v) {
   return __builtin_amdgcn_readfirstlane(v);
 }
 
-// WINDOW: the first key of the wave's first tile, max(0, q0 - W + 1) rounded down to a tile (q0 >= 0 and W >= 1: the difference
-// cannot wrap).  q0 comes from threadIdx.x >> 6, which the compiler cannot see is wave-uniform; read through lane 0 (as a tile
-// index: the entry points refuse L > INT32_MAX, as the document pair does) the loop counter and the tile addresses built from it stay scalar
-__device__ __forceinline__ int64_t window_first_tile(int64_t q0, int64_t window) {
-  const int64_t first = max(q0 - window + 1, (int64_t)0) / TILE;
-  return (int64_t)__builtin_amdgcn_readfirstlane((int)first) * TILE;
-}
-
 // ---------------------------------------------------------------------------------------------------------- forward
 template <typename T, int D, bool DROP, bool CAUSAL, Mask M>
 __global__ __launch_bounds__(256) void attn_fwd_k(Args<M> a) {

@@ -24,8 +24,13 @@
 // LDS), so at one split a query gets the bits attn_fwd_k gives it in the whole sequence.  A short chunk against a long past is
 // few work-groups walking many keys: with splits > 1 each wave cuts ITS key tiles into `splits` runs (grid.z), leaves fp32
 // (m, l, o[D]) per (row, head, run) in the workspace, and attn_decode_merge_k - unchanged, over B * Lq rows - folds them in order.
+//
+// Sliding window (entry points of apertis_hip_ext.h): attn_decode_k<.., WIN> cuts keys [max(Lk - window, 0), Lk) of the length it
+// read into the fixed pieces, attn_chunk_k<.., WIN> is the forward's window form (first tile, one unsigned compare).  The plain
+// instantiations are the code they were: the window is a template flag, its scalar the last field of the argument structs.
 #include "attn_tile.h"
 #include "rope_common.h"
+#include "../../include/apertis_hip_ext.h"
 
 namespace {
 
@@ -66,9 +71,12 @@ struct DecArgs {
   const int64_t *len;                 // the *_at form: Lk = min(*len + 1, cap) is read here, a.Lk holds cap (null: a.Lk is Lk)
   int H, splits;
   float sl2;                          // scale * log2(e)
+  int64_t window;                     // attn_decode_k<.., WIN = true> only: the keys that count, the newest included (>= 1)
 };
 
-template <typename T, int D>
+// WIN (apertis_attention_decode_window_at): only keys [begin, Lk), begin = max(Lk - window, 0), are cut into the pieces, each
+// wave's walk starts at its piece's j0 as ever - the by-value call on pointers offset by `begin` rows, with the same bits.
+template <typename T, int D, bool WIN = false>
 __global__ __launch_bounds__(256) void attn_decode_k(DecArgs a) {
   constexpr int E = 16 / (int)sizeof(T), LPR = D / E, KPW = APERTIS_WAVE / LPR, STEP = DEC_WAVES * KPW;
   __shared__ float sm_m[DEC_WAVES], sm_l[DEC_WAVES], sm_o[DEC_WAVES][D];
@@ -79,7 +87,12 @@ __global__ __launch_bounds__(256) void attn_decode_k(DecArgs a) {
     const int64_t n = *a.len + 1;
     Lk = n < 0 ? 0 : n < a.Lk ? n : a.Lk;
   }
-  const int64_t j0 = (int64_t)s * Lk / a.splits, j1 = (int64_t)(s + 1) * Lk / a.splits;
+  int64_t j0 = (int64_t)s * Lk / a.splits, j1 = (int64_t)(s + 1) * Lk / a.splits;
+  if constexpr (WIN) {                // (Lk >= 0 and window >= 1: no wrap; rows, V rows and mask columns before `begin` are never read)
+    const int64_t begin = Lk > a.window ? Lk - a.window : 0, n = Lk - begin;
+    j0 = begin + (int64_t)s * n / a.splits;
+    j1 = begin + (int64_t)(s + 1) * n / a.splits;
+  }
   float qf[E];
   unpack16<T>(*reinterpret_cast<const uint4 *>(static_cast<const T *>(a.q) + (int64_t)b * a.q_rs + h * D + c), qf);
   const T *kp = static_cast<const T *>(a.k) + (int64_t)b * a.k_bs + h * D + c;
@@ -186,7 +199,9 @@ __global__ __launch_bounds__(D) void attn_decode_merge_k(DecArgs a) {
 }
 
 template <typename T, int D> int launch_decode(const DecArgs &a, int64_t B, hipStream_t st) {
-  hipLaunchKernelGGL((attn_decode_k<T, D>), dim3((unsigned)a.splits, (unsigned)a.H, (unsigned)B), dim3(64 * DEC_WAVES), 0, st, a);
+  const dim3 grid((unsigned)a.splits, (unsigned)a.H, (unsigned)B);
+  if (a.window > 0) hipLaunchKernelGGL((attn_decode_k<T, D, true>), grid, dim3(64 * DEC_WAVES), 0, st, a);
+  else hipLaunchKernelGGL((attn_decode_k<T, D>), grid, dim3(64 * DEC_WAVES), 0, st, a);
   if (a.splits > 1) hipLaunchKernelGGL((attn_decode_merge_k<T, D>), dim3((unsigned)a.H, (unsigned)B), dim3(D), 0, st, a);
   return apertis_check_launch();
 }
@@ -289,13 +304,19 @@ struct ChunkArgs {
   int64_t q_rs, k_rs, k_bs, v_rs, v_bs, kv_rs, out_rs, Lq, n;
   int H, splits;
   float scale;
+  int64_t window;                     // attn_chunk_k<.., WIN = true> only: the keys a row sees, its own included (>= 1)
 };
 
 // Query row i of the chunk sits at key position n + i and attends keys j <= n + i with key_valid[b, j] != 0.  Grid: 64-row
 // blocks of the chunk (the last, longest-walking block first, as attn_fwd_k) x (B * H) x splits.  A key row at or past n + Lq,
 // the row of a masked key and a mask column at or past n + Lq are never read: such a row enters the tile as zeros, and its score
 // is replaced by -inf before anything reads it.
-template <typename T, int D>
+// WIN (apertis_attention_chunk_window): the forward's MASK_WINDOW form.  Row i attends keys j with n + i - window < j <= n + i: the
+// diagonal and the window are ONE unsigned compare of the distance against the scalar, the wave starts at the tile that holds the
+// first key its first row sees (window_first_tile; tiles in front of it are never touched) and the `splits` runs cut [first, ntile).
+// Inside that first tile the rows in front of the wave's first key enter as zeros like any row that may not be read: none of the
+// wave's rows counts them, so no bit moves.  No loads for the mask, no address that depends on the window.
+template <typename T, int D, bool WIN = false>
 __global__ __launch_bounds__(256) void attn_chunk_k(ChunkArgs a) {
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int64_t Lq = a.Lq, Lk = a.n + a.Lq;
@@ -317,24 +338,36 @@ __global__ __launch_bounds__(256) void attn_chunk_k(ChunkArgs a) {
   for (int dt = 0; dt < D / 16; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   // the wave's tiles: up to the one that holds its last row's own key; run `sp` of `splits` (wave-uniform, possibly empty)
   const int64_t ntile = (a.n + min(q0 + ROWS - 1, Lq - 1)) / TILE + 1;
-  const int64_t t0 = sp * ntile / a.splits, t1 = (sp + 1) * ntile / a.splits;
+  int64_t t0 = sp * ntile / a.splits, t1 = (sp + 1) * ntile / a.splits;
+  int64_t wb = 0;                                          // WIN: the first key any row of the wave sees
+  if constexpr (WIN) {                                     // (n + q0 >= 0 and window >= 1: the differences cannot wrap)
+    const int64_t first = window_first_tile(a.n + q0, a.window) / TILE, nt = ntile - first;
+    t0 = first + sp * nt / a.splits;
+    t1 = first + (sp + 1) * nt / a.splits;
+    wb = max(a.n + q0 - a.window + 1, (int64_t)0);
+  }
   for (int64_t kb = t0 * TILE; kb < t1 * TILE; kb += TILE) {
     bool valid[8];                                         // k-slot t of this lane group: may the row be read at all
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       const int64_t key = kb + tile_row(g, t);
       valid[t] = key < Lk;
+      if constexpr (WIN) valid[t] = valid[t] && key >= wb;
       if (kv && valid[t]) valid[t] = kv[key] != 0;
     }
     attn_fwd_tile<T, D>(
         qf, kp, a.k_rs, vp, a.v_rs, kb, sl2, m, lsum, acc, lane,
         [=](int64_t kr) {
           bool ok = kr < Lk;
+          if constexpr (WIN) ok = ok && kr >= wb;
           if (kv && ok) ok = kv[kr] != 0;
           return ok;
         },
-        [&](int t) { return valid[t] && kb + tile_row(g, t) <= pi; }, [&](int t) { return valid[t]; },
-        [](float p, int) { return p; });
+        [&](int t) {
+          if constexpr (WIN) return valid[t] && (uint64_t)(pi - (kb + tile_row(g, t))) < (uint64_t)a.window;
+          else return valid[t] && kb + tile_row(g, t) <= pi;
+        },
+        [&](int t) { return valid[t]; }, [](float p, int) { return p; });
   }
   const float l = xor_sum(lsum);
   if (qi >= Lq) return;
@@ -355,7 +388,8 @@ constexpr int64_t MERGE_MAX_ROWS = 65535;                  // grid.y of attn_dec
 
 template <typename T, int D> int launch_chunk(const ChunkArgs &a, int64_t B, hipStream_t st) {
   const dim3 grid((unsigned)ceil_div64(a.Lq, WG_ROWS), (unsigned)(B * a.H), (unsigned)a.splits);
-  hipLaunchKernelGGL((attn_chunk_k<T, D>), grid, dim3(256), 0, st, a);
+  if (a.window > 0) hipLaunchKernelGGL((attn_chunk_k<T, D, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((attn_chunk_k<T, D>), grid, dim3(256), 0, st, a);
   if (a.splits > 1) {
     const int64_t rows = B * a.Lq;
     for (int64_t r0 = 0; r0 < rows; r0 += MERGE_MAX_ROWS) {
@@ -452,7 +486,7 @@ extern "C" int64_t apertis_attention_decode_workspace_bytes(int64_t B, int64_t H
 static int attention_decode_impl(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs, const void *v_cache,
                           int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *len, const int64_t *key_valid, int64_t kv_rs,
                           void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lk, int64_t H, int64_t D, int64_t splits,
-                          int dtype, void *stream) {
+                          int dtype, void *stream, int64_t window = 0) {
   if (!q || !k_cache || !v_cache || !out) return APERTIS_ERR_ARG;
   if (B < 0 || H <= 0 || D <= 0 || cap < 1 || Lk < 1 || Lk > cap || (dtype != APERTIS_F32 && dtype != APERTIS_BF16))
     return APERTIS_ERR_ARG;
@@ -475,6 +509,7 @@ static int attention_decode_impl(const void *q, int64_t q_rs, const void *k_cach
   a.ws_o = workspace ? workspace + 2 * B * H * splits : nullptr;
   a.q_rs = q_rs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.kv_rs = kv_rs; a.out_rs = out_rs; a.Lk = Lk;
   a.len = len;
+  a.window = window;                  // (0: the three entry points of the 4.12 table, attn_decode_k<.., false>)
   a.H = (int)H;
   a.splits = (int)splits;
   a.sl2 = (1.f / sqrtf((float)D)) * LOG2E_F;
@@ -499,6 +534,18 @@ extern "C" int apertis_attention_decode_at(const void *q, int64_t q_rs, const vo
   // (Lk = cap for the shared checks: key_valid must cover every column the kernel can reach, and the kernel clamps to it)
   return attention_decode_impl(q, q_rs, k_cache, k_rs, k_bs, v_cache, v_rs, v_bs, cap, len, key_valid, kv_rs, out, out_rs, workspace,
                                B, cap, H, D, splits, dtype, stream);
+}
+
+// apertis_attention_decode_at under a sliding window (apertis_hip_ext.h): the kernel reads Lk as there and attends keys
+// [max(Lk - window, 0), Lk) only, cut into the caller's fixed `splits`
+extern "C" int apertis_attention_decode_window_at(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
+                                                  const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *len,
+                                                  int64_t window, const int64_t *key_valid, int64_t kv_rs, void *out, int64_t out_rs,
+                                                  float *workspace, int64_t B, int64_t H, int64_t D, int64_t splits, int dtype,
+                                                  void *stream) {
+  if (!len || window < 1) return APERTIS_ERR_ARG;
+  return attention_decode_impl(q, q_rs, k_cache, k_rs, k_bs, v_cache, v_rs, v_bs, cap, len, key_valid, kv_rs, out, out_rs, workspace,
+                               B, cap, H, D, splits, dtype, stream, window);
 }
 
 extern "C" int apertis_rope_kv_append_chunk(const void *q, int64_t q_rs, int64_t q_bs, const void *k, int64_t k_rs, int64_t k_bs,
@@ -538,10 +585,11 @@ extern "C" int64_t apertis_attention_chunk_workspace_bytes(int64_t B, int64_t H,
   return splits == 1 ? 0 : B * Lq * H * splits * (D + 2) * (int64_t)sizeof(float);
 }
 
-extern "C" int apertis_attention_chunk(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
-                                       const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid,
-                                       int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lq, int64_t n,
-                                       int64_t H, int64_t D, int64_t splits, int dtype, void *stream) {
+// both chunk attentions: window 0 is the plain causal form (attn_chunk_k<.., false>), else the keys a row sees
+static int attention_chunk_impl(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs, const void *v_cache,
+                                int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid, int64_t kv_rs, void *out,
+                                int64_t out_rs, float *workspace, int64_t B, int64_t Lq, int64_t n, int64_t H, int64_t D,
+                                int64_t splits, int dtype, void *stream, int64_t window) {
   if (!q || !k_cache || !v_cache || !out) return APERTIS_ERR_ARG;
   if (B < 0 || H <= 0 || D <= 0 || cap < 1 || Lq < 1 || n < 0 || n > cap || Lq > cap - n ||
       (dtype != APERTIS_F32 && dtype != APERTIS_BF16))
@@ -557,7 +605,8 @@ extern "C" int apertis_attention_chunk(const void *q, int64_t q_rs, const void *
                         (uint64_t)(k_bs * es) | (uint64_t)(v_rs * es) | (uint64_t)(v_bs * es);
   if (bits & 15u) return APERTIS_ERR_UNSUPPORTED;
   if (B == 0) return APERTIS_OK;
-  if (splits == 0) splits = chunk_splits(B, H, Lq, n + Lq);
+  // (under a window no wave walks more than window + Lq keys: the rule is asked at that length; no sizing point is measured for it)
+  if (splits == 0) splits = chunk_splits(B, H, Lq, window > 0 && window < n ? window + Lq : n + Lq);
   if (splits > 1 && (!workspace || ((uintptr_t)workspace & 15u))) return APERTIS_ERR_ARG;
   ChunkArgs a{};
   a.q = q; a.k = k_cache; a.v = v_cache; a.key_valid = key_valid; a.out = out;
@@ -565,10 +614,30 @@ extern "C" int apertis_attention_chunk(const void *q, int64_t q_rs, const void *
   a.ws_o = workspace ? workspace + 2 * B * Lq * H * splits : nullptr;
   a.q_rs = q_rs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.kv_rs = kv_rs; a.out_rs = out_rs;
   a.Lq = Lq; a.n = n;
+  a.window = window;
   a.H = (int)H;
   a.splits = (int)splits;
   a.scale = 1.f / sqrtf((float)D);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == APERTIS_F32) return D == 64 ? launch_chunk<float, 64>(a, B, st) : launch_chunk<float, 128>(a, B, st);
   return D == 64 ? launch_chunk<bf16_t, 64>(a, B, st) : launch_chunk<bf16_t, 128>(a, B, st);
+}
+
+extern "C" int apertis_attention_chunk(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
+                                       const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid,
+                                       int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lq, int64_t n,
+                                       int64_t H, int64_t D, int64_t splits, int dtype, void *stream) {
+  return attention_chunk_impl(q, q_rs, k_cache, k_rs, k_bs, v_cache, v_rs, v_bs, cap, key_valid, kv_rs, out, out_rs, workspace, B, Lq,
+                              n, H, D, splits, dtype, stream, 0);
+}
+
+// apertis_attention_chunk under a sliding window (apertis_hip_ext.h): row i attends keys j with n + i - window < j <= n + i
+extern "C" int apertis_attention_chunk_window(const void *q, int64_t q_rs, const void *k_cache, int64_t k_rs, int64_t k_bs,
+                                              const void *v_cache, int64_t v_rs, int64_t v_bs, int64_t cap, const int64_t *key_valid,
+                                              int64_t kv_rs, void *out, int64_t out_rs, float *workspace, int64_t B, int64_t Lq,
+                                              int64_t n, int64_t window, int64_t H, int64_t D, int64_t splits, int dtype,
+                                              void *stream) {
+  if (window < 1) return APERTIS_ERR_ARG;
+  return attention_chunk_impl(q, q_rs, k_cache, k_rs, k_bs, v_cache, v_rs, v_bs, cap, key_valid, kv_rs, out, out_rs, workspace, B, Lq,
+                              n, H, D, splits, dtype, stream, window);
 }

@@ -135,6 +135,16 @@ struct RowsBelow {
   __device__ __forceinline__ bool operator()(int t) const { return tile_row(g, t) < nr; }
 };
 
+// Sliding window (the forward, the dQ kernel, attn_chunk_k): the first key of the wave's first tile for a wave whose first row
+// sits at key position q0, max(0, q0 - W + 1) rounded down to a tile (q0 >= 0 and W >= 1: the difference cannot wrap).  q0 comes
+// from threadIdx.x >> 6, which the compiler cannot see is wave-uniform; read through lane 0 the loop counter and the tile
+// addresses built from it stay scalar.  (Read as a TILE INDEX in 32 bits: the window pair refuses L > INT32_MAX as the document
+// pair does, and a KV cache of 2^36 rows does not exist.)
+__device__ __forceinline__ int64_t window_first_tile(int64_t q0, int64_t window) {
+  const int64_t first = max(q0 - window + 1, (int64_t)0) / TILE;
+  return (int64_t)__builtin_amdgcn_readfirstlane((int)first) * TILE;
+}
+
 // One 32-key tile (keys kb .. kb + 31) of the forward for the 16 queries of a wave, query c = lane & 15 in qf:
 // S^T = K Q^T, mask, the online softmax's running (m, lsum) in log2 units, O^T += V^T P^T.  kp / vp: row 0 of this head.
 //   k_row_ok(j): whether key row j may be read for the scores (else it enters as zeros; j = kb + 16s + c)

@@ -950,8 +950,8 @@ class ApertisAttention(nn.Module):
             return False
         cache, kv = past_kv.cache, att_mask.key_valid
         n = cache.lengths[past_kv.layer]
-        if att_mask.window is not None and n + q.shape[1] > att_mask.window:
-            return False                         # (the chunk kernels have no window predicate: the stock branch applies the band)
+        if att_mask.window is not None and n + q.shape[1] > att_mask.window and not ops.ATTN_WINDOW_CACHE:
+            return False                         # (opt-in: ops.attention_chunk(window=); else the stock branch applies the band)
         return (n + q.shape[1] <= cache.capacity and att_mask.pos_host == n
                 and (kv is None or tuple(kv.shape) == (q.shape[0], n + q.shape[1])))
 
@@ -959,7 +959,11 @@ class ApertisAttention(nn.Module):
         cache, layer = past_kv.cache, past_kv.layer
         cos, sin = self._rope_tables()
         q = ops.kv_append_rope_chunk(q, k, v, cache, layer, att_mask.pos_host, cos, sin)
-        ctxv = ops.attention_chunk(q, cache, layer, self.num_attention_heads, att_mask.key_valid, dead_rows=att_mask.dead_rows)
+        if att_mask.window is None:
+            ctxv = ops.attention_chunk(q, cache, layer, self.num_attention_heads, att_mask.key_valid, dead_rows=att_mask.dead_rows)
+        else:                                    # (past the window only under ops.ATTN_WINDOW_CACHE: _chunk_ok)
+            ctxv = ops.attention_chunk(q, cache, layer, self.num_attention_heads, att_mask.key_valid, dead_rows=att_mask.dead_rows,
+                                       window=att_mask.window)
         return self.out_proj(ctxv), cache
 
     def _heads(self, t):
@@ -1931,8 +1935,8 @@ class ApertisForCausalLM(nn.Module):
         attn = self.model.layers[0].attention
         n, (B, cap, _) = past.length, past.k[0].shape
         window = _active_window(self.config)
-        if window is not None and n + left > window:
-            return False                         # (the replayed step reads its key count on the device: no window there)
+        if window is not None and n + left > window and not ops.ATTN_WINDOW_CACHE:
+            return False                         # (opt-in: the replayed step's window form, KVCache.step_state_begin(window=))
         want = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else attn.q_proj.weight.dtype
         if not (n == tokens.shape[1] - 1 and B == tokens.shape[0] and n + left <= cap and past.dtype == want
                 and len(past) == len(self.model.layers) and ops.attention_decode_supported(past.k[0], attn.num_attention_heads)
@@ -1986,7 +1990,10 @@ class ApertisForCausalLM(nn.Module):
         else:
             s_past, start, cap = cache, cache.length, cache.capacity
             # one split count for the whole tail, from the length it ends at (which end to size for)
-            cache.step_state_begin(self.config.num_attention_heads, mask, L_end=start + left)
+            # (a window reaches the replayed step only under ops.ATTN_WINDOW_CACHE: without it _mha_graph_ok let no tail past the
+            #  window in, and the launches stay the ones they were)
+            window = _active_window(self.config) if ops.ATTN_WINDOW_CACHE else None
+            cache.step_state_begin(self.config.num_attention_heads, mask, L_end=start + left, window=window)
             state += [cache.dev_len, cache.dev_valid, cache.dev_err]
             err_word = cache.dev_err
 

@@ -4,7 +4,9 @@ preallocated KV cache (KVCache): single-token steps (kv_append_rope, attention_d
 bidirectional attention (full_attention, full_attention_qkv: the same kernels with the diagonal compiled out).  Packed rows
 (document_layout, document_attention: the causal kernels under a document mask, with the tiles of other documents skipped).
 Sliding windows, opt-in (ATTN_WINDOW; window_attention, window_layout, attention_decode(window=): the causal kernels with
-bounds computed from the query index, packed rows on a clipped layout, a decode step that reads the last W cache rows).
+bounds computed from the query index, packed rows on a clipped layout, a decode step that reads the last W cache rows; and,
+under ATTN_WINDOW_CACHE on top, the device-length step and the chunk step past the window: KVCache.step_state_begin(window=),
+attention_chunk(window=)).
 
 Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autograd bookkeeping only; every computation is a
 HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip, csrc/attention_deadrows.hip).
@@ -29,6 +31,10 @@ ATTN_LEFT_PAD = os.environ.get("APERTIS_MHA_LEFT_PAD", "0") == "1"
 # window_attention, document_attention on a clipped layout, attention_decode(window=), a band on the stock branch.  OFF by
 # default (APERTIS_MHA_WINDOW=1 turns it on): the reference never reads the field, and neither does the default path
 ATTN_WINDOW = os.environ.get("APERTIS_MHA_WINDOW", "0") == "1"
+# under ATTN_WINDOW, for a model with an active window: generate()'s graph replay and its multi-token cache steps stay on the
+# KV-cache kernels past the window (attention_decode_at with the cache's step_window, attention_chunk(window=)) instead of
+# declining.  OFF by default; without ATTN_WINDOW it does nothing.
+ATTN_WINDOW_CACHE = os.environ.get("APERTIS_MHA_WINDOW_CACHE", "0") == "1"
 
 
 # ------------------------------------------------------------------------------------------------------ operand checks
@@ -587,6 +593,7 @@ class KVCache:
     and writes the validity column of the new token.  WHILE THE DEVICE STATE DRIVES THE STEPS THE HOST `lengths` ARE STALE
     (and with them the views `cache[i]` hands out); step_state_end() makes them current again - from `dev_len` with one
     host read, or from the length its caller knows - and the by-value steps may go on.  Still one continuation per cache.
+    step_state_begin(window=W) also keeps `step_window`: while it is set, attention_decode_at attends the newest W rows only.
 
     `multi_token` (a flag, default False): a forward of several tokens extends this cache in place on the chunk kernels
     (kv_append_rope_chunk, attention_chunk) and hands the same object back, as a single-token step does; without the flag such
@@ -606,7 +613,7 @@ class KVCache:
         self.multi_token = bool(multi_token)
         self._ws = None
         self.dev_len = self.dev_valid = self.dev_err = None
-        self.step_active, self.step_splits = False, 1
+        self.step_active, self.step_splits, self.step_window = False, 1, None
 
     @classmethod
     def empty(cls, layers, B, capacity, W, dtype=torch.float32, device=None, multi_token=False):
@@ -645,11 +652,16 @@ class KVCache:
     def __iter__(self):
         return (KVLayer(self, i) for i in range(len(self.k)))
 
-    def step_state_begin(self, heads, key_valid=None, L_end=None, splits=None):
+    def step_state_begin(self, heads, key_valid=None, L_end=None, splits=None, window=None):
         """Device step state from the host state (class docstring).  key_valid: the mask so far, [B, <= capacity], or None
         (every key valid).  The split count of attention_decode_at is fixed here, once - apertis_attention_decode_splits at
         `L_end` keys (the length the steps can reach; default: the capacity) unless `splits` gives it - and the workspace is
-        sized for it, so nothing is allocated by a step."""
+        sized for it, so nothing is allocated by a step.
+        window (an integer >= 1, or None): the steps attend the newest `window` rows only - it is kept as `step_window`,
+        attention_decode_at launches the window form while it is set, and the split count is sized at min(L_end, window)
+        keys, the most a step reads.  step_state_end() clears it."""
+        if window is not None:
+            window = _window("KVCache.step_state_begin", window)
         if len(set(self.lengths)) != 1:
             raise ApertisHipError(f"KVCache.step_state_begin: the layers disagree on the length ({self.lengths})")
         B, cap, W = self.k[0].shape
@@ -657,8 +669,10 @@ class KVCache:
         if W % heads:
             raise ApertisHipError(f"KVCache.step_state_begin: width {W} with {heads} heads")
         lib = _lib.load()
-        n = int(splits) if splits is not None else int(lib.apertis_attention_decode_splits(
-            max(B, 1), heads, min(max(int(L_end if L_end is not None else cap), 1), cap), W // heads))
+        keys = min(max(int(L_end if L_end is not None else cap), 1), cap)
+        if window is not None:
+            keys = min(keys, window)
+        n = int(splits) if splits is not None else int(lib.apertis_attention_decode_splits(max(B, 1), heads, keys, W // heads))
         nbytes = int(lib.apertis_attention_decode_workspace_bytes(B, heads, W // heads, n))
         if nbytes < 0:
             raise ApertisHipError(f"KVCache.step_state_begin: {n} splits outside [1, {ATTN_DECODE_MAX_SPLITS}]")
@@ -671,7 +685,7 @@ class KVCache:
         self.dev_valid = valid
         self.dev_len = torch.full((1,), self.lengths[0], dtype=torch.int64, device=dev)
         self.dev_err = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.step_active, self.step_splits = True, n
+        self.step_active, self.step_splits, self.step_window = True, n, window
 
     def step_state_end(self, length=None):
         """The host lengths (every layer) from the device state: `length` if the caller knows it (no host read; `dev_len` is
@@ -685,7 +699,7 @@ class KVCache:
         if not 0 <= length <= self.capacity:
             raise ApertisHipError(f"KVCache.step_state_end: length {length} outside [0, {self.capacity}]")
         self.lengths = [int(length)] * len(self.k)
-        self.step_active = False
+        self.step_active, self.step_window = False, None
 
     def _workspace(self, nbytes):
         if nbytes and (self._ws is None or self._ws.numel() * 4 < nbytes):
@@ -837,7 +851,7 @@ def attention_chunk_workspace_bytes(B, heads, Lq, D, splits):
     return int(_lib.load().apertis_attention_chunk_workspace_bytes(B, heads, Lq, D, splits))
 
 
-def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0, dead_rows=False):
+def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0, dead_rows=False, window=None):
     """Causal softmax attention of the Lq rows kv_append_rope_chunk has JUST appended to layer `layer` of `cache` over
     everything the layer holds: row i of q ([B, Lq, W], the cache's dtype, D = W / heads in {64, 128}) sits at key position
     n + i, n = lengths[layer] - Lq, and attends keys j <= n + i.  Returns O [B, Lq, W] where out_proj reads it.  key_valid:
@@ -846,7 +860,13 @@ def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0, dead_rows=
     split count give the same bits, and at one split row i has the bits causal_attention gives row n + i of the whole
     sequence.  Inference only (no dropout, nothing saved for a backward).  A row with no valid key at or before it comes out
     as zeros; dead_rows=True fills such rows (after the merge of the runs) with the reference's value, the column mean of the
-    layer's v rows [0, n + Lq) (attention_dead_rows; it raises when q requires grad under autograd)."""
+    layer's v rows [0, n + Lq) (attention_dead_rows; it raises when q requires grad under autograd).
+    window (an integer >= 1, or None): a sliding window - row i attends keys j with n + i - window < j <= n + i.  With
+    n + Lq > window the launch is apertis_attention_chunk_window (key tiles in front of a wave's window are never touched; at
+    one split row i has the bits window_attention gives row n + i of the whole sequence; splits = 0 asks the same rule at
+    min(n + Lq, window + Lq) keys, the most a wave walks - no sizing point has been measured for the windowed walk);
+    otherwise it is the call without a window.  dead_rows keeps its meaning (a row with no valid key at or before it, over
+    [0, n + Lq), as window_attention(dead_rows=True) fills them)."""
     _require_gpu(q, cache.k[layer], key_valid)
     if dead_rows:
         _dead_rows_inference("attention_chunk", False, 0.0, q)
@@ -857,21 +877,32 @@ def attention_chunk(q, cache, layer, heads, key_valid=None, splits=0, dead_rows=
         raise ApertisHipError(f"attention_chunk: q {tuple(q.shape)} {q.dtype} with {heads} heads against a cache of "
                               f"[{B}, {cap}, {W}] {cache.dtype} (D 64 or 128, fp32 or bf16, one dtype)")
     Lq, Lk = q.shape[1], cache.lengths[layer]
+    if window is not None and _window("attention_chunk", window) >= Lk:
+        window = None                                      # (every row sees all of its keys: the call without a window)
     if Lq > Lk:
         raise ApertisHipError(f"attention_chunk: {Lq} query rows but the layer holds {Lk} (kv_append_rope_chunk first)")
     q, q_rs = _aligned_rows(*_rows(q, W), W)
     D, ns, ws = W // heads, int(splits), None              # ns: the split count the workspace is sized for AND the launch takes
+    walk = Lk if window is None else min(Lk, window + Lq)  # the keys a wave walks at most
     if ns == 0:
-        ns = int(lib.apertis_attention_chunk_splits(B, heads, Lq, Lk, D)) if B else 1
+        ns = int(lib.apertis_attention_chunk_splits(B, heads, Lq, walk, D)) if B else 1
     if 1 <= ns <= ATTN_DECODE_MAX_SPLITS:
         ws = cache._workspace(max(int(lib.apertis_attention_chunk_workspace_bytes(B, heads, Lq, D, ns)), 0))
     key_valid, kv_rs = _mask_rows("attention_chunk", key_valid, B, Lk)
     out = torch.empty(B, Lq, W, device=q.device, dtype=q.dtype)
-    _launch("apertis_attention_chunk", lib.apertis_attention_chunk,
-            (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
-             ptr(out), W, ptr(ws), B, Lq, Lk - Lq, heads, D, ns, dtype_code(q), stream_ptr()),
-            work=4.0 * B * W * Lq * (Lk - Lq + (Lq + 1) / 2), detail=f"{B}x{heads}x{D}x{Lq}",
-            nbytes=(2.0 * B * Lk + 2.0 * B * Lq) * W * q.element_size())
+    if window is None:
+        _launch("apertis_attention_chunk", lib.apertis_attention_chunk,
+                (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
+                 ptr(out), W, ptr(ws), B, Lq, Lk - Lq, heads, D, ns, dtype_code(q), stream_ptr()),
+                work=4.0 * B * W * Lq * (Lk - Lq + (Lq + 1) / 2), detail=f"{B}x{heads}x{D}x{Lq}",
+                nbytes=(2.0 * B * Lk + 2.0 * B * Lq) * W * q.element_size())
+    else:
+        pairs = window_pairs(Lk, window) - window_pairs(Lk - Lq, window)           # (query, key) pairs of the chunk's rows
+        _launch("apertis_attention_chunk_window", lib.apertis_attention_chunk_window,
+                (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(key_valid), kv_rs,
+                 ptr(out), W, ptr(ws), B, Lq, Lk - Lq, window, heads, D, ns, dtype_code(q), stream_ptr()),
+                work=4.0 * B * W * pairs, detail=f"{B}x{heads}x{D}x{Lq}",
+                nbytes=(2.0 * B * walk + 2.0 * B * Lq) * W * q.element_size())
     if dead_rows and key_valid is not None and B:
         attention_dead_rows(out, vc, key_valid, Lk - Lq)
     return out
@@ -905,7 +936,9 @@ def attention_decode_at(q, cache, layer, heads, splits=None):
     """attention_decode over Lk = min(dev_len[0] + 1, capacity) keys, read by the kernel (after kv_append_rope_at and BEFORE
     `dev_len` moves: the new token's own key included), under the cache's `dev_valid`.  splits: the FIXED number of pieces,
     1..ATTN_DECODE_MAX_SPLITS, not bounded by Lk (default: what step_state_begin chose) - grid and workspace depend on it
-    alone, an empty piece contributes nothing.  The same bits as attention_decode(..., splits=n) for the same Lk."""
+    alone, an empty piece contributes nothing.  The same bits as attention_decode(..., splits=n) for the same Lk.
+    With `cache.step_window` set (step_state_begin(window=)) the launch is apertis_attention_decode_window_at: only keys
+    [max(Lk - window, 0), Lk) are cut into the pieces and read - the bits of attention_decode(..., window=, splits=n)."""
     _step_state(cache, "attention_decode_at")
     _require_gpu(q, cache.k[layer])
     lib = _lib.load()
@@ -913,9 +946,16 @@ def attention_decode_at(q, cache, layer, heads, splits=None):
     B, cap, W = kc.shape
     n = cache.step_splits if splits is None else int(splits)
     q, q_rs, D, ws, out = _decode_operands("attention_decode_at", lib, q, cache, layer, heads, n)
-    kv = cache.dev_valid
-    _launch("apertis_attention_decode_at", lib.apertis_attention_decode_at,
-            (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(cache.dev_len),
-             ptr(kv), kv.stride(0), ptr(out), W, ptr(ws), B, heads, D, n, dtype_code(q), stream_ptr()),
-            work=4.0 * B * cap * W, detail=f"{B}x{heads}x{D}", nbytes=2.0 * B * cap * W * q.element_size())
+    kv, win = cache.dev_valid, cache.step_window
+    if win is None:
+        _launch("apertis_attention_decode_at", lib.apertis_attention_decode_at,
+                (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(cache.dev_len),
+                 ptr(kv), kv.stride(0), ptr(out), W, ptr(ws), B, heads, D, n, dtype_code(q), stream_ptr()),
+                work=4.0 * B * cap * W, detail=f"{B}x{heads}x{D}", nbytes=2.0 * B * cap * W * q.element_size())
+    else:
+        keys = min(cap, win)                               # (the most a step reads: the device length is not known here)
+        _launch("apertis_attention_decode_window_at", lib.apertis_attention_decode_window_at,
+                (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(cache.dev_len),
+                 win, ptr(kv), kv.stride(0), ptr(out), W, ptr(ws), B, heads, D, n, dtype_code(q), stream_ptr()),
+                work=4.0 * B * keys * W, detail=f"{B}x{heads}x{D}", nbytes=2.0 * B * keys * W * q.element_size())
     return out
