@@ -7,6 +7,8 @@
 // walks tokens, so per-channel reductions (dD, dw, dbias) stay in registers; a block covers
 // RP = 256/CPR rows at a time (CPR = Dn/4 chunks per row) and leaves [nblk, ...] partials that a
 // deterministic column-sum kernel folds.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -111,47 +113,58 @@ ssm_gate_bwd_k(const TIO *__restrict__ dout, int64_t dout_rs, const TY *__restri
 // ---------------------------------------------------------------- depthwise causal conv + SiLU
 constexpr int CONV_TT = 16;  // tokens per thread run
 
-template <typename T, int KW>
+// ---- run per thread: a thread owns four channels of a 16-token run, with the taps and the x window (in the backward also the
+// dpre history) in KM-long register arrays.  The tap count is the template's KW (2..4, KM == KW: the model's widths) or, with
+// KW == 0, the runtime k <= KM (5..16, an ssm_conv_kernel off the default path).  The arrays are right-aligned - tap q sits in
+// slot off + q, off = KM - k - so every index is a constant once the loops unroll, and the wave-uniform tests `m >= off` skip
+// the unused slots (no 0 * x terms: a non-finite value outside the window stays outside); with KW > 0, off is 0 and the tests
+// fold away.  Every sum runs q ascending from the bias, whatever the mode: bias + sum_q w[q] * x[t - (k-1) + q].
+constexpr int CONV_KMAX = 16;
+
+template <typename T, int KM, int KW>
 __global__ void __launch_bounds__(256)
 dwconv_silu_fwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
-                  T *__restrict__ out, int64_t out_rs, int64_t B, int64_t L, int Dn) {
+                  T *__restrict__ out, int64_t out_rs, int64_t B, int64_t L, int Dn, int k_rt) {
+  static_assert(KW == 0 || KW == KM, "a compile-time tap count fills the arrays");
+  const int k = KW > 0 ? KW : k_rt, off = KM - k;
   const Geo g = make_geo(Dn);
   const int rr = threadIdx.x / g.CPR;
   if (rr >= g.RP) return;
   const int64_t runs_per_seq = ceil_div64(L, CONV_TT);
   for (int c = threadIdx.x - rr * g.CPR; c < g.CPR; c += 256) {
-    float wv[4][KW], bv[4];
+    float wv[4][KM], bv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       bv[j] = bias[c * 4 + j];
 #pragma unroll
-      for (int q = 0; q < KW; ++q) wv[j][q] = w[(c * 4 + j) * KW + q];
+      for (int m = 0; m < KM; ++m) wv[j][m] = m >= off ? w[(c * 4 + j) * k + (m - off)] : 0.f;
     }
     for (int64_t run = (int64_t)blockIdx.x * g.RP + rr; run < B * runs_per_seq; run += (int64_t)gridDim.x * g.RP) {
       const int64_t b = run / runs_per_seq, t0 = (run - b * runs_per_seq) * CONV_TT;
       const T *xb = x + b * L * x_rs + c * 4;
       T *ob = out + b * L * out_rs + c * 4;
-      float win[KW][4];  // win[q] = x[t-(KW-1)+q]
+      float win[KM][4];  // win[m] = x[t-(KM-1)+m]
 #pragma unroll
-      for (int q = 0; q < KW - 1; ++q) {
-        int64_t tt = t0 - (KW - 1) + q;
-        float4 v = tt >= 0 ? ld4<T>(xb + tt * x_rs) : make_float4(0, 0, 0, 0);
-        win[q + 1][0] = v.x; win[q + 1][1] = v.y; win[q + 1][2] = v.z; win[q + 1][3] = v.w;
+      for (int m = 0; m < KM - 1; ++m) {
+        const int64_t tt = t0 - (KM - 1) + m;
+        float4 v = (m >= off && tt >= 0) ? ld4<T>(xb + tt * x_rs) : make_float4(0, 0, 0, 0);
+        win[m + 1][0] = v.x; win[m + 1][1] = v.y; win[m + 1][2] = v.z; win[m + 1][3] = v.w;
       }
       const int64_t t1 = min(t0 + CONV_TT, L);
       for (int64_t t = t0; t < t1; ++t) {
 #pragma unroll
-        for (int q = 0; q < KW - 1; ++q)
+        for (int m = 0; m < KM - 1; ++m)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) win[q][j] = win[q + 1][j];
+          for (int j = 0; j < 4; ++j) win[m][j] = win[m + 1][j];
         float4 v = ld4<T>(xb + t * x_rs);
-        win[KW - 1][0] = v.x; win[KW - 1][1] = v.y; win[KW - 1][2] = v.z; win[KW - 1][3] = v.w;
+        win[KM - 1][0] = v.x; win[KM - 1][1] = v.y; win[KM - 1][2] = v.z; win[KM - 1][3] = v.w;
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           float s = bv[j];
 #pragma unroll
-          for (int q = 0; q < KW; ++q) s += wv[j][q] * win[q][j];
+          for (int m = 0; m < KM; ++m)
+            if (m >= off) s += wv[j][m] * win[m][j];
           s = to_f32(from_f32<T>(s));  // conv output is stored in the activation dtype before SiLU
           o[j] = siluf_(s);
         }
@@ -265,402 +278,26 @@ dwconv_silu_fwd_tile_k(const T *__restrict__ x, int64_t x_rs, const float *__res
   }
 }
 
-// (A tile form of the backward - x and dout rows in LDS, a thread walking six consecutive rows of one 16-byte piece with the x
-// window and the last KW dpre values in registers - was built and measured: 111 us against 102 us for the run-per-thread
-// kernel below at B=40, L=4096, Dn=176; 180 VGPRs leave two waves per SIMD for a walk that is all dependent LDS-read -> FMA
-// chains.  Removed; the backward stays as it was.)
-// backward: dpre[t] = dout[t]*silu'(pre[t]); dx[t] = sum_q w[q]*dpre[t+(KW-1)-q]; dw,db partials
-template <typename T, int KW>
-__global__ void __launch_bounds__(256)
-dwconv_silu_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
-                  const T *__restrict__ dout, int64_t dout_rs, const T *__restrict__ dout2, int64_t dout2_rs,
-                  T *__restrict__ dx, int64_t dx_rs,
-                  float *__restrict__ dw_part, float *__restrict__ db_part, int64_t B, int64_t L, int Dn) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *red = reinterpret_cast<float *>(smem);  // [RP][CPR][4*(KW+1)]
-  constexpr int NA = 4 * (KW + 1);
-  const Geo g = make_geo(Dn);
-  const int rr = threadIdx.x / g.CPR;
-  const bool on = rr < g.RP;
-  const int64_t runs_per_seq = ceil_div64(L, CONV_TT);
-  for (int c0 = 0; c0 < g.CPR; c0 += 256) {
-    const int c = c0 + (on ? threadIdx.x - rr * g.CPR : 0);
-    float accw[4][KW], accb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { accb[j] = 0.f;
-#pragma unroll
-      for (int q = 0; q < KW; ++q) accw[j][q] = 0.f; }
-    if (on && c < g.CPR) {
-      float wv[4][KW], bv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        bv[j] = bias[c * 4 + j];
-#pragma unroll
-        for (int q = 0; q < KW; ++q) wv[j][q] = w[(c * 4 + j) * KW + q];
-      }
-      for (int64_t run = (int64_t)blockIdx.x * g.RP + rr; run < B * runs_per_seq; run += (int64_t)gridDim.x * g.RP) {
-        const int64_t b = run / runs_per_seq, t0 = (run - b * runs_per_seq) * CONV_TT;
-        const T *xb = x + b * L * x_rs + c * 4;
-        const T *gb = dout + b * L * dout_rs + c * 4;
-        // dout2: a second gradient of the same output (its other consumer's), added here as autograd's add kernel would have
-        // added it - the sum rounded to T - instead of in a pass of its own
-        const T *gb2 = dout2 ? dout2 + b * L * dout2_rs + c * 4 : nullptr;
-        T *dxb = dx + b * L * dx_rs + c * 4;
-        const int64_t t1 = min(t0 + CONV_TT, L);
-        // sliding x window win[q] = x[t-(KW-1)+q] and dpre history dp[q] = dpre[t-(KW-1)+q];
-        // walk t over [t0, t1+KW-1): dpre[t] for t>=t1 belongs to the next run but feeds our dx
-        float win[KW][4], dp[KW][4];
-#pragma unroll
-        for (int q = 0; q < KW; ++q)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { win[q][j] = 0.f; dp[q][j] = 0.f; }
-#pragma unroll
-        for (int q = 0; q < KW - 1; ++q) {
-          int64_t tt = t0 - (KW - 1) + q;
-          if (tt >= 0) { float4 v = ld4<T>(xb + tt * x_rs); win[q + 1][0] = v.x; win[q + 1][1] = v.y; win[q + 1][2] = v.z; win[q + 1][3] = v.w; }
-        }
-        for (int64_t t = t0; t < t1 + (KW - 1); ++t) {
-#pragma unroll
-          for (int q = 0; q < KW - 1; ++q)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { win[q][j] = win[q + 1][j]; dp[q][j] = dp[q + 1][j]; }
-          if (t < L) {
-            float4 v = ld4<T>(xb + t * x_rs), gv = ld4<T>(gb + t * dout_rs);
-            if (gb2) {
-              const float4 g2 = ld4<T>(gb2 + t * dout2_rs);
-              gv = make_float4(to_f32(from_f32<T>(gv.x + g2.x)), to_f32(from_f32<T>(gv.y + g2.y)), to_f32(from_f32<T>(gv.z + g2.z)),
-                               to_f32(from_f32<T>(gv.w + g2.w)));
-            }
-            win[KW - 1][0] = v.x; win[KW - 1][1] = v.y; win[KW - 1][2] = v.z; win[KW - 1][3] = v.w;
-            const float g_[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float s = bv[j];
-#pragma unroll
-              for (int q = 0; q < KW; ++q) s += wv[j][q] * win[q][j];
-              s = to_f32(from_f32<T>(s));
-              float d = g_[j] * silu_grad(s);
-              dp[KW - 1][j] = d;
-              if (t < t1) {  // own tokens only: parameter gradients are not double counted
-                accb[j] += d;
-#pragma unroll
-                for (int q = 0; q < KW; ++q) accw[j][q] += d * win[q][j];
-              }
-            }
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { win[KW - 1][j] = 0.f; dp[KW - 1][j] = 0.f; }
-          }
-          // dx[t'] with t' = t-(KW-1): sum_q w[q]*dpre[t'+(KW-1)-q] = sum_q w[q]*dp[KW-1-q]
-          const int64_t tp = t - (KW - 1);
-          if (tp >= t0 && tp < t1) {
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float s = 0.f;
-#pragma unroll
-              for (int q = 0; q < KW; ++q) s += wv[j][q] * dp[KW - 1 - q][j];
-              o[j] = s;
-            }
-            st4<T>(dxb + tp * dx_rs, make_float4(o[0], o[1], o[2], o[3]));
-          }
-        }
-      }
-    }
-    const int cw = min(g.CPR, 256);
-    __syncthreads();
-    if (on && c < g.CPR) {
-      float *r = red + ((int64_t)rr * cw + (c - c0)) * NA;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        r[j * (KW + 1) + KW] = accb[j];
-#pragma unroll
-        for (int q = 0; q < KW; ++q) r[j * (KW + 1) + q] = accw[j][q];
-      }
-    }
-    __syncthreads();
-    if (on && rr == 0 && c < g.CPR) {
-      for (int j = 0; j < 4; ++j) {
-        for (int q = 0; q <= KW; ++q) {
-          float s = 0.f;
-          for (int r = 0; r < g.RP; ++r) s += red[((int64_t)r * cw + (c - c0)) * NA + j * (KW + 1) + q];
-          if (q < KW) dw_part[((int64_t)blockIdx.x * Dn + c * 4 + j) * KW + q] = s;
-          else db_part[(int64_t)blockIdx.x * Dn + c * 4 + j] = s;
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ---- widths 5..16 (an ssm_conv_kernel other than 2..4; off the model's default path): the run-per-thread forms above with the
-// tap count k a runtime value.  Window, dpre history and taps are CONV_KMAX-long register arrays, right-aligned - tap q sits in
-// slot off + q, off = CONV_KMAX - k - so every index is a constant once the loops unroll, and the wave-uniform tests `m >= off`
-// skip the unused slots (no 0 * x terms: a non-finite value outside the window stays outside).  The backward emits dx
-// CONV_KMAX - 1 tokens behind the walk instead of k - 1: dx[t - (KMAX-1)] = sum_q w[q] * dp[k-1-q] and w[q] = wv[KMAX-k+q],
-// i.e. slot KMAX-1-m of the taps meets slot m of the history.  Same geometry, grid and partial layout as the templated kernels;
-// the sums run in the same order.
-constexpr int CONV_KMAX = 16;
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-dwconv_silu_fwd_kn(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
-                   T *__restrict__ out, int64_t out_rs, int64_t B, int64_t L, int Dn, int k) {
-  constexpr int KM = CONV_KMAX;
-  const int off = KM - k;
-  const Geo g = make_geo(Dn);
-  const int rr = threadIdx.x / g.CPR;
-  if (rr >= g.RP) return;
-  const int64_t runs_per_seq = ceil_div64(L, CONV_TT);
-  for (int c = threadIdx.x - rr * g.CPR; c < g.CPR; c += 256) {
-    float wv[4][KM], bv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      bv[j] = bias[c * 4 + j];
-#pragma unroll
-      for (int m = 0; m < KM; ++m) wv[j][m] = m >= off ? w[(c * 4 + j) * k + (m - off)] : 0.f;
-    }
-    for (int64_t run = (int64_t)blockIdx.x * g.RP + rr; run < B * runs_per_seq; run += (int64_t)gridDim.x * g.RP) {
-      const int64_t b = run / runs_per_seq, t0 = (run - b * runs_per_seq) * CONV_TT;
-      const T *xb = x + b * L * x_rs + c * 4;
-      T *ob = out + b * L * out_rs + c * 4;
-      float win[KM][4];  // win[m] = x[t-(KM-1)+m]
-#pragma unroll
-      for (int m = 0; m < KM - 1; ++m) {
-        const int64_t tt = t0 - (KM - 1) + m;
-        float4 v = (m >= off && tt >= 0) ? ld4<T>(xb + tt * x_rs) : make_float4(0, 0, 0, 0);
-        win[m + 1][0] = v.x; win[m + 1][1] = v.y; win[m + 1][2] = v.z; win[m + 1][3] = v.w;
-      }
-      const int64_t t1 = min(t0 + CONV_TT, L);
-      for (int64_t t = t0; t < t1; ++t) {
-#pragma unroll
-        for (int m = 0; m < KM - 1; ++m)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) win[m][j] = win[m + 1][j];
-        float4 v = ld4<T>(xb + t * x_rs);
-        win[KM - 1][0] = v.x; win[KM - 1][1] = v.y; win[KM - 1][2] = v.z; win[KM - 1][3] = v.w;
-        float o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float s = bv[j];
-#pragma unroll
-          for (int m = 0; m < KM; ++m)
-            if (m >= off) s += wv[j][m] * win[m][j];
-          s = to_f32(from_f32<T>(s));  // conv output is stored in the activation dtype before SiLU
-          o[j] = siluf_(s);
-        }
-        st4<T>(ob + t * out_rs, make_float4(o[0], o[1], o[2], o[3]));
-      }
-    }
-  }
-}
-
-// ---- the forward of LEFT-PADDED rows (generate()'s prefill under ops.ssm.SSM_LEFT_PAD): batch row b's sequence begins at token
-// start[b].  A tap that falls before it reads as zero - what t - j < 0 is to the kernels above - and the output rows before it
-// are exact zeros, so that x_param_proj (no bias) hands the scan Bt = C = dt_in = 0 there and the state stays at 0 up to the
-// first real token.  One form for every width 2..16 and every Dn % 4 == 0: a work-group takes (batch, 64 tokens, CB <= 64
-// 4-channel chunks).  The tile's pad rows are a PREFIX, [0, first): they are zero-filled by all threads and never loaded or
-// convolved - `first` is uniform over the work-group, no lane tests a row - and a tile that is all pad ends there.  The other
-// rows and the k - 1 before them come into LDS as fp32 (rows before start[b]: zeros, not loaded) next to the taps, transposed
-// to [k][CB] so that one 16-byte read brings tap q of a thread's four channels; thread (rg, p) owns chunk p of rows first + rg,
-// first + rg + RG, ...  Each output is bias + sum_q w[q] * x[t - (k-1) + q], q ascending, rounded to the io dtype before SiLU:
-// the sum of the kernels above term for term, so a row's outputs from start[b] on carry the bits those kernels give the row
-// alone.  This runs once per generate() and layer; the taps cost an LDS read per term instead of k registers per channel.
-template <typename T>
-__global__ void __launch_bounds__(256)
-dwconv_silu_start_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
-                    const int32_t *__restrict__ start, T *__restrict__ out, int64_t out_rs, int64_t L, int CPR, int k, int CB,
-                    int nchunks, int ncb) {
-  constexpr int TT = CONV_TILE_T;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float4 *tile = reinterpret_cast<float4 *>(smem);   // [TT + k - 1][CB]
-  float4 *taps = tile + (TT + k - 1) * CB;           // [k][CB]
-  const int tid = threadIdx.x;
-  const int cb = (int)(blockIdx.x % ncb);
-  const int64_t bt = blockIdx.x / ncb, b = bt / nchunks;
-  const int64_t t0 = (bt - b * nchunks) * TT;
-  const int rows = (int)min((int64_t)TT, L - t0);
-  const int c_lo = cb * CB, nc = min(CB, CPR - c_lo);
-  const int64_t s = min(max((int64_t)start[b], (int64_t)0), L);
-  const int first = (int)min(max(s - t0, (int64_t)0), (int64_t)rows);
-  const T *xb = x + b * L * x_rs + c_lo * 4;
-  T *ob = out + (b * L + t0) * out_rs + c_lo * 4;
-  for (int i = tid; i < first * nc; i += 256) {
-    const int r = i / nc, c = i - r * nc;
-    st4<T>(ob + (int64_t)r * out_rs + c * 4, make_float4(0.f, 0.f, 0.f, 0.f));
-  }
-  if (first == rows) return;
-  const int nrow = rows - first + k - 1;             // tile row j = token t0 + first - (k - 1) + j
-  const int64_t tf = t0 + first - (k - 1);
-  for (int i = tid; i < nrow * nc; i += 256) {
-    const int r = i / nc, c = i - r * nc;
-    const int64_t t = tf + r;
-    tile[r * CB + c] = t >= s ? ld4<T>(xb + t * x_rs + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  for (int i = tid; i < k * nc; i += 256) {
-    const int q = i / nc, c = i - q * nc;
-    const float *wc = w + (int64_t)(c_lo + c) * 4 * k + q;
-    taps[q * CB + c] = make_float4(wc[0], wc[k], wc[2 * k], wc[3 * k]);
-  }
-  __syncthreads();
-  const int rg = tid / CB, p = tid - rg * CB, RG = 256 / CB;
-  if (rg >= RG || p >= nc) return;
-  const float *bp = bias + (c_lo + p) * 4;
-  const float4 bv = make_float4(bp[0], bp[1], bp[2], bp[3]);
-  for (int r = rg; r < rows - first; r += RG) {
-    float acc[4] = {bv.x, bv.y, bv.z, bv.w};
-    for (int q = 0; q < k; ++q) {
-      const float4 f = tile[(r + q) * CB + p], wq = taps[q * CB + p];
-      acc[0] += wq.x * f.x; acc[1] += wq.y * f.y; acc[2] += wq.z * f.z; acc[3] += wq.w * f.w;
-    }
-    float o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float sj = to_f32(from_f32<T>(acc[j]));  // conv output is stored in the activation dtype before SiLU
-      o[j] = siluf_(sj);
-    }
-    st4<T>(ob + (int64_t)(first + r) * out_rs + p * 4, make_float4(o[0], o[1], o[2], o[3]));
-  }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-dwconv_silu_bwd_kn(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
-                   const T *__restrict__ dout, int64_t dout_rs, const T *__restrict__ dout2, int64_t dout2_rs,
-                   T *__restrict__ dx, int64_t dx_rs,
-                   float *__restrict__ dw_part, float *__restrict__ db_part, int64_t B, int64_t L, int Dn, int k) {
-  constexpr int KM = CONV_KMAX;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *red = reinterpret_cast<float *>(smem);  // [RP][CPR][4*(k+1)]
-  const int off = KM - k, NA = 4 * (k + 1);
-  const Geo g = make_geo(Dn);
-  const int rr = threadIdx.x / g.CPR;
-  const bool on = rr < g.RP;
-  const int64_t runs_per_seq = ceil_div64(L, CONV_TT);
-  for (int c0 = 0; c0 < g.CPR; c0 += 256) {
-    const int c = c0 + (on ? threadIdx.x - rr * g.CPR : 0);
-    float accw[4][KM], accb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { accb[j] = 0.f;
-#pragma unroll
-      for (int m = 0; m < KM; ++m) accw[j][m] = 0.f; }
-    if (on && c < g.CPR) {
-      float wv[4][KM], bv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        bv[j] = bias[c * 4 + j];
-#pragma unroll
-        for (int m = 0; m < KM; ++m) wv[j][m] = m >= off ? w[(c * 4 + j) * k + (m - off)] : 0.f;
-      }
-      for (int64_t run = (int64_t)blockIdx.x * g.RP + rr; run < B * runs_per_seq; run += (int64_t)gridDim.x * g.RP) {
-        const int64_t b = run / runs_per_seq, t0 = (run - b * runs_per_seq) * CONV_TT;
-        const T *xb = x + b * L * x_rs + c * 4;
-        const T *gb = dout + b * L * dout_rs + c * 4;
-        const T *gb2 = dout2 ? dout2 + b * L * dout2_rs + c * 4 : nullptr;
-        T *dxb = dx + b * L * dx_rs + c * 4;
-        const int64_t t1 = min(t0 + CONV_TT, L), te = min(t1 + (k - 1), L);
-        // win[m] = x[t-(KM-1)+m], dp[m] = dpre[t-(KM-1)+m]; dpre is formed on [t0, te) - the next run's first k-1 tokens feed
-        // our dx - and taken as zero outside it
-        float win[KM][4], dp[KM][4];
-#pragma unroll
-        for (int m = 0; m < KM; ++m)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { win[m][j] = 0.f; dp[m][j] = 0.f; }
-#pragma unroll
-        for (int m = 0; m < KM - 1; ++m) {
-          const int64_t tt = t0 - (KM - 1) + m;
-          if (m >= off && tt >= 0) { float4 v = ld4<T>(xb + tt * x_rs); win[m + 1][0] = v.x; win[m + 1][1] = v.y; win[m + 1][2] = v.z; win[m + 1][3] = v.w; }
-        }
-        for (int64_t t = t0; t < t1 + (KM - 1); ++t) {
-#pragma unroll
-          for (int m = 0; m < KM - 1; ++m)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { win[m][j] = win[m + 1][j]; dp[m][j] = dp[m + 1][j]; }
-          if (t < te) {
-            float4 v = ld4<T>(xb + t * x_rs), gv = ld4<T>(gb + t * dout_rs);
-            if (gb2) {
-              const float4 g2 = ld4<T>(gb2 + t * dout2_rs);
-              gv = make_float4(to_f32(from_f32<T>(gv.x + g2.x)), to_f32(from_f32<T>(gv.y + g2.y)), to_f32(from_f32<T>(gv.z + g2.z)),
-                               to_f32(from_f32<T>(gv.w + g2.w)));
-            }
-            win[KM - 1][0] = v.x; win[KM - 1][1] = v.y; win[KM - 1][2] = v.z; win[KM - 1][3] = v.w;
-            const float g_[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float s = bv[j];
-#pragma unroll
-              for (int m = 0; m < KM; ++m)
-                if (m >= off) s += wv[j][m] * win[m][j];
-              s = to_f32(from_f32<T>(s));
-              float d = g_[j] * silu_grad(s);
-              dp[KM - 1][j] = d;
-              if (t < t1) {  // own tokens only: parameter gradients are not double counted
-                accb[j] += d;
-#pragma unroll
-                for (int m = 0; m < KM; ++m)
-                  if (m >= off) accw[j][m] += d * win[m][j];
-              }
-            }
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { win[KM - 1][j] = 0.f; dp[KM - 1][j] = 0.f; }
-          }
-          const int64_t tp = t - (KM - 1);
-          if (tp >= t0) {  // (tp < t1 by the loop bound)
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float s = 0.f;
-#pragma unroll
-              for (int m = KM - 1; m >= 0; --m)  // q = k-1-m ascending, as in the templated kernel
-                if (m < k) s += wv[j][KM - 1 - m] * dp[m][j];
-              o[j] = s;
-            }
-            st4<T>(dxb + tp * dx_rs, make_float4(o[0], o[1], o[2], o[3]));
-          }
-        }
-      }
-    }
-    const int cw = min(g.CPR, 256);
-    __syncthreads();
-    if (on && c < g.CPR) {
-      float *r = red + ((int64_t)rr * cw + (c - c0)) * NA;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        r[j * (k + 1) + k] = accb[j];
-#pragma unroll
-        for (int m = 0; m < KM; ++m)
-          if (m >= off) r[j * (k + 1) + (m - off)] = accw[j][m];
-      }
-    }
-    __syncthreads();
-    if (on && rr == 0 && c < g.CPR) {
-      for (int j = 0; j < 4; ++j) {
-        for (int q = 0; q <= k; ++q) {
-          float s = 0.f;
-          for (int r = 0; r < g.RP; ++r) s += red[((int64_t)r * cw + (c - c0)) * NA + j * (k + 1) + q];
-          if (q < k) dw_part[((int64_t)blockIdx.x * Dn + c * 4 + j) * k + q] = s;
-          else db_part[(int64_t)blockIdx.x * Dn + c * 4 + j] = s;
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ---- PACKED rows (training under ops.ssm.SSM_PACKED): a batch row holds several documents, contiguous runs of tokens, and
-// token t of row b belongs to the document [start[b, t], end[b, t]) (int32 [B, L], ops.document_layout).  The conv stops at a
-// document's first token: a tap at t - j < start[b, t] reads as zero - what t - j < 0 is to the kernels above - so every
-// document gets what it gets in a row of its own.
-// Forward: dwconv_silu_start_k's geometry - a work-group takes (batch, 64 tokens, CB <= 64 four-channel chunks), thread (rg, p)
-// owns chunk p of rows rg, rg + RG, ..., the taps sit in LDS transposed to [k][CB], one form for every width 2..16 and every
-// Dn % 4 == 0 - with two differences.  The boundary is per token ROW, not a prefix of the batch row: the 64 starts of the tile
-// come into LDS and a row masks its own taps with a select in front of the multiply (the product with the zero is still
-// added, as the kernels above add the zeros they load in front of a sequence: bias + sum_q w[q] * x[t - (k-1) + q], q
-// ascending, rounded to the io dtype before SiLU, term for term - a document's outputs carry the bits the plain forward gives
-// it alone, and with one document per row they are the plain forward's).  And the tile holds the rows as stored (8 bytes per
-// chunk in bf16, not 16): this kernel runs in every layer of every training step, and at Dn = 176, k = 4 the fp32 tile's
-// 47 KiB would leave three work-groups per CU where the stored form's 24 KiB leaves six.
+// ---- BOUNDED rows: a token's sequence begins somewhere inside its batch row, and a tap in front of that boundary reads as
+// zero - what t - j < 0 is to the kernels above.  Two layouts:
+//   PACKED rows (training under ops.ssm.SSM_PACKED): a batch row holds several documents, contiguous runs of tokens, and token
+//   t of row b belongs to the document [start[b, t], end[b, t]) (int32 [B, L], ops.document_layout).  The conv stops at a
+//   document's first token, so every document gets what it gets in a row of its own.
+//   LEFT-PADDED rows (generate()'s prefill under ops.ssm.SSM_LEFT_PAD, forward only): batch row b's sequence begins at token
+//   start[b] (int32 [B], clamped to [0, L]).  The output rows before it are exact zeros, so that x_param_proj (no bias) hands
+//   the scan Bt = C = dt_in = 0 there and the state stays at 0 up to the first real token.
+// Forward, one kernel for both (ROW: the boundary is one start per batch row, else one per token), every width 2..16 and every
+// Dn % 4 == 0: a work-group takes (batch, 64 tokens, CB <= 64 four-channel chunks), thread (rg, p) owns chunk p of rows rg,
+// rg + RG, ..., and the taps sit in LDS transposed to [k][CB], so that one 16-byte read brings tap q of a thread's four
+// channels.  One int per tile row says how many of its leading taps lie before the boundary, and the row masks them with a
+// select in front of the multiply: whatever the tile holds there (a left-padded row's pad inputs are loaded like any other)
+// never reaches a product, and the product with the zero is still added, as the kernels above add the zeros they load in
+// front of a sequence: bias + sum_q w[q] * x[t - (k-1) + q], q ascending, rounded to the io dtype before SiLU, term for term -
+// a document's, or a left-padded row's, outputs carry the bits the plain forward gives it alone.  A row whose count reaches k
+// lies before the boundary itself: a pad row, which stores its zeros and computes nothing (a token of a document never gets
+// there: it is in its own document).  The tile holds the rows as stored (8 bytes per chunk in bf16, not 16): the packed form
+// runs in every layer of every training step, and at Dn = 176, k = 4 an fp32 tile's 47 KiB would leave three work-groups per
+// CU where the stored form's 24 KiB leaves six.
 template <typename T> struct Raw4;
 template <> struct Raw4<float> {
   typedef float4 R;
@@ -678,11 +315,11 @@ template <> struct Raw4<bf16_t> {
   }
 };
 
-template <typename T>
+template <typename T, bool ROW>
 __global__ void __launch_bounds__(256)
-dwconv_silu_doc_fwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
-                      const int32_t *__restrict__ start, T *__restrict__ out, int64_t out_rs, int64_t L, int CPR, int k, int CB,
-                      int nchunks, int ncb) {
+dwconv_silu_bound_fwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
+                        const int32_t *__restrict__ start, T *__restrict__ out, int64_t out_rs, int64_t L, int CPR, int k, int CB,
+                        int nchunks, int ncb) {
   constexpr int TT = CONV_TILE_T;
   typedef Raw4<T> RW;
   typedef typename RW::R R;
@@ -709,8 +346,19 @@ dwconv_silu_doc_fwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
     const float *wc = w + (int64_t)(c_lo + c) * 4 * k + q;
     taps[q * CB + c] = make_float4(wc[0], wc[k], wc[2 * k], wc[3 * k]);
   }
-  // token t - (k-1) + q lies before the document iff q < start[b, t] - t + (k-1)   (<= k-1: a token is in its own document)
-  if (tid < rows) st[tid] = (int32_t)min((int64_t)start[b * L + t0 + tid] - (t0 + tid) + (k - 1), (int64_t)k);
+  // token t - (k-1) + q lies before the boundary s of token t iff q < s - t + (k-1)   (<= k-1 for a token of a document)
+  if (tid < rows) {
+    int64_t n;
+    if constexpr (ROW) {
+      // a row may be longer than 2^31 tokens: the count is clamped from below as well before it narrows to an int (a token far
+      // behind start[b] has a very negative one, which masks what 0 masks: nothing)
+      const int64_t s = min(max((int64_t)start[b], (int64_t)0), L);
+      n = max(s - (t0 + tid) + (k - 1), (int64_t)0);
+    } else {
+      n = (int64_t)start[b * L + t0 + tid] - (t0 + tid) + (k - 1);   // (L < 2^31 here: this fits an int)
+    }
+    st[tid] = (int32_t)min(n, (int64_t)k);
+  }
   __syncthreads();
   const int rg = tid / CB, p = tid - rg * CB, RG = 256 / CB;
   if (rg >= RG || p >= nc) return;
@@ -718,6 +366,12 @@ dwconv_silu_doc_fwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
   const float4 bv = make_float4(bp[0], bp[1], bp[2], bp[3]);
   for (int r = rg; r < rows; r += RG) {
     const int lim = st[r];
+    if constexpr (ROW) {
+      if (lim == k) {
+        st4<T>(ob + (int64_t)r * out_rs + p * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+        continue;
+      }
+    }
     float acc[4] = {bv.x, bv.y, bv.z, bv.w};
     for (int q = 0; q < k; ++q) {
       float4 f = RW::f4(tile[(r + q) * CB + p]);
@@ -735,24 +389,34 @@ dwconv_silu_doc_fwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
   }
 }
 
-// Backward of the same: dwconv_silu_bwd_kn's walk (a thread owns four channels of a 16-token run, x window and dpre history in
-// registers, right-aligned KM-long arrays with the tap count k a runtime value; same grid, partial layout and order of every
-// sum) in two capacities, KM = 4 for the widths 2..4 and KM = 16 for 5..16.  pre is recomputed under the forward's predicate:
-// where the walk reaches a document's first token (start[b, t] == t) the window in front of it is zeroed - the tokens of one
-// document share their start, so the zeros hold until they leave the window - and the window a run begins with is masked by
-// the start of its first token.  Hence dw[c, q] sums pairs of one document only.  dx[t] = sum_q w[q] * dpre[t + (k-1) - q]
-// takes a dpre at t' >= end[b, t] as zero - the select sits in front of the multiply, as above - and db is what it was.
-// With one document per row every select passes exactly where the plain kernels read a value they loaded, so dx carries
-// their bits.  No atomics: per-block partials, folded in a fixed order by colsum_rows_k.
-template <typename T, int KM>
-__global__ void __launch_bounds__(256, KM == 4 ? 3 : 1)   // (KM = 4: the plain k = 4 kernel's three waves per SIMD - 168 VGPRs)
-dwconv_silu_doc_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
-                      const T *__restrict__ dout, int64_t dout_rs, const T *__restrict__ dout2, int64_t dout2_rs,
-                      const int32_t *__restrict__ start, const int32_t *__restrict__ end, T *__restrict__ dx, int64_t dx_rs,
-                      float *__restrict__ dw_part, float *__restrict__ db_part, int64_t B, int64_t L, int Dn, int k) {
+// ---- backward, run per thread as the forward at the top (KM, KW: the same two modes; a thread owns four channels of a 16-token
+// run): dpre[t] = dout[t] * silu'(pre[t]), dx[t] = sum_q w[q] * dpre[t + (k-1) - q], and per-block dw, db partials that
+// colsum_rows_k folds in a fixed order - no atomics.  The walk runs KM - 1 tokens past the run: dx is emitted KM - 1 tokens
+// behind it, dx[t - (KM-1)] = sum_q w[q] * dp[k-1-q] with w[q] = wv[off + q], i.e. slot KM-1-m of the taps meets slot m of the
+// history; dpre of the next run's first k - 1 tokens feeds our dx but not our parameter gradients.
+// DOC, packed rows (start, end as in the forward above; KW == 0, KM = 4 for the widths 2..4 and 16 for 5..16): pre is recomputed
+// under the forward's predicate - where the walk reaches a document's first token (start[b, t] == t) the window in front of it
+// is zeroed (the tokens of one document share their start, so the zeros hold until they leave the window), and the window a run
+// begins with is masked by the start of its first token.  Hence dw[c, q] sums pairs of one document only.  dx takes a dpre at
+// t' >= end[b, t] as zero, the select in front of the multiply as in the forward.  With one document per row every select
+// passes exactly where the plain form reads a value it loaded, so dx carries its bits.  db is summed in fp64 there: it is one
+// chain over every token of the batch, the longest sum of the kernel (see the fold at the end).
+// (A tile form of the backward - x and dout rows in LDS, a thread walking six consecutive rows of one 16-byte piece with the x
+// window and the last KW dpre values in registers - was built and measured: 111 us against 102 us for the run-per-thread
+// kernel below at B=40, L=4096, Dn=176; 180 VGPRs leave two waves per SIMD for a walk that is all dependent LDS-read -> FMA
+// chains.  Removed; the backward stays as it was.)
+template <typename T, int KM, int KW, bool DOC>
+__global__ void __launch_bounds__(256, DOC && KM == 4 ? 3 : 1)   // (DOC, KM = 4: the plain k = 4 form's three waves per SIMD - 168 VGPRs)
+dwconv_silu_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__restrict__ w, const float *__restrict__ bias,
+                  const T *__restrict__ dout, int64_t dout_rs, const T *__restrict__ dout2, int64_t dout2_rs,
+                  const int32_t *__restrict__ start, const int32_t *__restrict__ end, T *__restrict__ dx, int64_t dx_rs,
+                  float *__restrict__ dw_part, float *__restrict__ db_part, int64_t B, int64_t L, int Dn, int k_rt) {
+  static_assert(KW == 0 || (KW == KM && !DOC), "a compile-time tap count fills the arrays; the packed form takes it at run time");
+  typedef typename std::conditional<DOC, double, float>::type BSum;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *red = reinterpret_cast<float *>(smem);  // [RP][CPR][4*(k+2)]: per channel k tap sums, then the bias sum as (hi, lo)
-  const int off = KM - k, NA = 4 * (k + 2);
+  // [RP][CPR][4*KS]: per channel k tap sums, then the bias sum (DOC: as (hi, lo))
+  float *red = reinterpret_cast<float *>(smem);
+  const int k = KW > 0 ? KW : k_rt, off = KM - k, KS = k + (DOC ? 2 : 1), NA = 4 * KS;
   const Geo g = make_geo(Dn);
   const int rr = threadIdx.x / g.CPR;
   const bool on = rr < g.RP;
@@ -760,9 +424,9 @@ dwconv_silu_doc_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
   for (int c0 = 0; c0 < g.CPR; c0 += 256) {
     const int c = c0 + (on ? threadIdx.x - rr * g.CPR : 0);
     float accw[4][KM];
-    double accb[4];      // (fp64: db is one chain over every token of the batch, the longest sum of the kernel - see the fold below)
+    BSum accb[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { accb[j] = 0.0;
+    for (int j = 0; j < 4; ++j) { accb[j] = 0;
 #pragma unroll
       for (int m = 0; m < KM; ++m) accw[j][m] = 0.f; }
     if (on && c < g.CPR) {
@@ -777,18 +441,20 @@ dwconv_silu_doc_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
         const int64_t b = run / runs_per_seq, t0 = (run - b * runs_per_seq) * CONV_TT;
         const T *xb = x + b * L * x_rs + c * 4;
         const T *gb = dout + b * L * dout_rs + c * 4;
+        // dout2: a second gradient of the same output (its other consumer's), added here as autograd's add kernel would have
+        // added it - the sum rounded to T - instead of in a pass of its own
         const T *gb2 = dout2 ? dout2 + b * L * dout2_rs + c * 4 : nullptr;
-        const int32_t *sb = start + b * L, *eb = end + b * L;
+        const int32_t *sb = DOC ? start + b * L : nullptr, *eb = DOC ? end + b * L : nullptr;
         T *dxb = dx + b * L * dx_rs + c * 4;
-        const int64_t t1 = min(t0 + CONV_TT, L), te = min(t1 + (k - 1), L);
-        // win[m] = x[t-(KM-1)+m] (zero in front of t's document), dp[m] = dpre[t-(KM-1)+m]; dpre is formed on [t0, te) - the
-        // next run's first k-1 tokens feed our dx - and taken as zero outside it
+        // win[m] = x[t-(KM-1)+m] (zero in front of t's document), dp[m] = dpre[t-(KM-1)+m]; dpre is formed on [t0, te) and taken
+        // as zero outside it (KW > 0: the loop bound already stops at t1 + KW - 1)
+        const int64_t t1 = min(t0 + CONV_TT, L), te = KW > 0 ? L : min(t1 + (k - 1), L);
         float win[KM][4], dp[KM][4];
 #pragma unroll
         for (int m = 0; m < KM; ++m)
 #pragma unroll
           for (int j = 0; j < 4; ++j) { win[m][j] = 0.f; dp[m][j] = 0.f; }
-        const int64_t s0 = max((int64_t)sb[t0], (int64_t)0);
+        const int64_t s0 = DOC ? max((int64_t)sb[t0], (int64_t)0) : 0;   // the run's first token's document begins here
 #pragma unroll
         for (int m = 0; m < KM - 1; ++m) {
           const int64_t tt = t0 - (KM - 1) + m;
@@ -801,16 +467,18 @@ dwconv_silu_doc_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
             for (int j = 0; j < 4; ++j) { win[m][j] = win[m + 1][j]; dp[m][j] = dp[m + 1][j]; }
           if (t < te) {
             float4 v = ld4<T>(xb + t * x_rs), gv = ld4<T>(gb + t * dout_rs);
-            const bool first = (int64_t)sb[t] == t;       // a document begins here: nothing in front of it is its own
+            const bool first = DOC && (int64_t)sb[t] == t;   // a document begins here: nothing in front of it is its own
             if (gb2) {
               const float4 g2 = ld4<T>(gb2 + t * dout2_rs);
               gv = make_float4(to_f32(from_f32<T>(gv.x + g2.x)), to_f32(from_f32<T>(gv.y + g2.y)), to_f32(from_f32<T>(gv.z + g2.z)),
                                to_f32(from_f32<T>(gv.w + g2.w)));
             }
+            if constexpr (DOC) {
 #pragma unroll
-            for (int m = 0; m < KM - 1; ++m)
+              for (int m = 0; m < KM - 1; ++m)
 #pragma unroll
-              for (int j = 0; j < 4; ++j) win[m][j] = first ? 0.f : win[m][j];
+                for (int j = 0; j < 4; ++j) win[m][j] = first ? 0.f : win[m][j];
+            }
             win[KM - 1][0] = v.x; win[KM - 1][1] = v.y; win[KM - 1][2] = v.z; win[KM - 1][3] = v.w;
             const float g_[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
@@ -823,7 +491,7 @@ dwconv_silu_doc_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
               float d = g_[j] * silu_grad(s);
               dp[KM - 1][j] = d;
               if (t < t1) {  // own tokens only: parameter gradients are not double counted
-                accb[j] += (double)d;
+                accb[j] += (BSum)d;
 #pragma unroll
                 for (int m = 0; m < KM; ++m)
                   if (m >= off) accw[j][m] += d * win[m][j];
@@ -835,13 +503,13 @@ dwconv_silu_doc_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
           }
           const int64_t tp = t - (KM - 1);
           if (tp >= t0) {  // (tp < t1 by the loop bound)
-            const int64_t lim = (int64_t)eb[tp] - tp;       // dp[m] is dpre[tp + m]: inside tp's document iff m < lim
+            const int64_t lim = DOC ? (int64_t)eb[tp] - tp : KM;   // dp[m] is dpre[tp + m]: inside tp's document iff m < lim
             float o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               float s = 0.f;
 #pragma unroll
-              for (int m = KM - 1; m >= 0; --m)  // q = k-1-m ascending, as in the plain kernels
+              for (int m = KM - 1; m >= 0; --m)  // q = k-1-m ascending
                 if (m < k) s += wv[j][KM - 1 - m] * (m < lim ? dp[m][j] : 0.f);
               o[j] = s;
             }
@@ -857,25 +525,26 @@ dwconv_silu_doc_bwd_k(const T *__restrict__ x, int64_t x_rs, const float *__rest
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float hi = (float)accb[j];
-        r[j * (k + 2) + k] = hi;
-        r[j * (k + 2) + k + 1] = (float)(accb[j] - (double)hi);
+        r[j * KS + k] = hi;
+        if constexpr (DOC) r[j * KS + k + 1] = (float)(accb[j] - (double)hi);
 #pragma unroll
         for (int m = 0; m < KM; ++m)
-          if (m >= off) r[j * (k + 2) + (m - off)] = accw[j][m];
+          if (m >= off) r[j * KS + (m - off)] = accw[j][m];
       }
     }
     __syncthreads();
     if (on && rr == 0 && c < g.CPR) {
       for (int j = 0; j < 4; ++j) {
         for (int q = 0; q <= k; ++q) {
-          // (the rows' partials meet in fp64, off the token walk, and db - whose chains were fp64 already - comes over as a
+          // (DOC: the rows' partials meet in fp64, off the token walk, and db - whose chains were fp64 already - comes over as a
           //  (hi, lo) pair: a packed row's dw then carries the rounding of the threads' own 16-token chains and one more, its
           //  db one rounding, as the short documents' do when each is run alone and summed outside.  Measured against the
           //  fp64 restatement at Dn = 4, L = 64, fp32: all-fp32 sums left db at 3.0e-6, the alone runs at 7.4e-7)
-          double s = 0.0;
+          BSum s = 0;
           for (int r = 0; r < g.RP; ++r) {
-            const float *e = red + ((int64_t)r * cw + (c - c0)) * NA + j * (k + 2);
-            s += q < k ? (double)e[q] : (double)e[k] + (double)e[k + 1];
+            const float *e = red + ((int64_t)r * cw + (c - c0)) * NA + j * KS;
+            if constexpr (DOC) s += q < k ? (double)e[q] : (double)e[k] + (double)e[k + 1];
+            else s += e[q];
           }
           if (q < k) dw_part[((int64_t)blockIdx.x * Dn + c * 4 + j) * k + q] = (float)s;
           else db_part[(int64_t)blockIdx.x * Dn + c * 4 + j] = (float)s;
@@ -1155,30 +824,84 @@ extern "C" int apertis_dwconv_silu_fwd(const void *x, int64_t x_rs, const float 
   }
   dim3 grid(conv_blocks(B, L, Dn)), block(256);
   if (k > 4 && k <= CONV_KMAX) {
-    CONV_TYPES(dtype_io, hipLaunchKernelGGL(dwconv_silu_fwd_kn<T>, grid, block, 0, st, (const T *)x, x_rs, w, bias, (T *)out,
-                                            out_rs, B, L, (int)Dn, (int)k));
+    CONV_TYPES(dtype_io, hipLaunchKernelGGL((dwconv_silu_fwd_k<T, CONV_KMAX, 0>), grid, block, 0, st, (const T *)x, x_rs, w, bias,
+                                            (T *)out, out_rs, B, L, (int)Dn, (int)k));
     return apertis_check_launch();
   }
-  CONV_DISPATCH(k, dtype_io, hipLaunchKernelGGL((dwconv_silu_fwd_k<T, KW>), grid, block, 0, st, (const T *)x, x_rs, w, bias,
-                                                (T *)out, out_rs, B, L, (int)Dn));
+  CONV_DISPATCH(k, dtype_io, hipLaunchKernelGGL((dwconv_silu_fwd_k<T, KW, KW>), grid, block, 0, st, (const T *)x, x_rs, w, bias,
+                                                (T *)out, out_rs, B, L, (int)Dn, (int)k));
   return apertis_check_launch();
 }
 
-extern "C" int apertis_dwconv_silu_start_fwd(const void *x, int64_t x_rs, const float *w, const float *bias, const int32_t *start,
-                                             void *out, int64_t out_rs, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
-                                             void *stream) {
+// the bounded forward of both layouts: `row` - start is [B], one boundary per batch row (left-padded), else [B, L] (packed)
+static int conv_bound_fwd(bool row, const void *x, int64_t x_rs, const float *w, const float *bias, const int32_t *start, void *out,
+                          int64_t out_rs, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io, void *stream) {
   if (!x || !w || !bias || !start || !out || B < 0 || L < 0) return APERTIS_ERR_ARG;
   if (dtype_io != APERTIS_F32 && dtype_io != APERTIS_BF16) return APERTIS_ERR_ARG;
-  if (!rows_ok(Dn) || (x_rs | out_rs) % 4 || x_rs < Dn || out_rs < Dn || k < 2 || k > CONV_KMAX) return APERTIS_ERR_UNSUPPORTED;
+  // (a packed row's int32 starts cannot name a token past 2^31, and its kernel narrows start - t to an int.  The left-padded
+  // form needs no such refusal: it keeps start[b] and the token index in 64 bits and clamps the count to [0, k] before it
+  // narrows, so a row of any length that the grid holds goes through)
+  if (!rows_ok(Dn) || (x_rs | out_rs) % 4 || x_rs < Dn || out_rs < Dn || k < 2 || k > CONV_KMAX || (!row && L >= 0x7fffffffLL))
+    return APERTIS_ERR_UNSUPPORTED;
   const uintptr_t piece = dtype_io == APERTIS_BF16 ? 8 : 16;        // a thread moves four channels at a time
   if ((uintptr_t)x % piece || (uintptr_t)out % piece) return APERTIS_ERR_UNSUPPORTED;
   if (B == 0 || L == 0) return APERTIS_OK;
   const int CPR = (int)(Dn / 4), CB = std::min(CPR, 64);
   const int64_t nchunks = ceil_div64(L, CONV_TILE_T), ncb = ceil_div64(CPR, CB);
   if (nchunks >= 0x7fffffffLL || B * nchunks * ncb >= 0x7fffffffLL) return APERTIS_ERR_UNSUPPORTED;
-  const size_t lds = (size_t)(CONV_TILE_T + 2 * k - 1) * CB * sizeof(float4);   // tile + taps: at most 95 rows of 1 KiB
-  CONV_TYPES(dtype_io, launch_lds(dwconv_silu_start_k<T>, dim3((unsigned)(B * nchunks * ncb)), dim3(256), lds, (hipStream_t)stream,
-                                  (const T *)x, x_rs, w, bias, start, (T *)out, out_rs, L, CPR, (int)k, CB, (int)nchunks, (int)ncb));
+  // taps + tile as stored + the tile's counts: at most 16 + 79 KiB at k = 16, fp32; 27 KiB at k = 4, Dn = 176, bf16
+  const size_t lds = (size_t)k * CB * sizeof(float4) + (size_t)(CONV_TILE_T + k - 1) * CB * piece + CONV_TILE_T * sizeof(int32_t);
+  const dim3 grid((unsigned)(B * nchunks * ncb)), block(256);
+#define BOUND_FWD(ROW_)                                                                                                          \
+  CONV_TYPES(dtype_io, launch_lds(dwconv_silu_bound_fwd_k<T, ROW_>, grid, block, lds, (hipStream_t)stream, (const T *)x, x_rs, w, \
+                                  bias, start, (T *)out, out_rs, L, CPR, (int)k, CB, (int)nchunks, (int)ncb))
+  if (row) BOUND_FWD(true); else BOUND_FWD(false);
+#undef BOUND_FWD
+  return apertis_check_launch();
+}
+
+extern "C" int apertis_dwconv_silu_start_fwd(const void *x, int64_t x_rs, const float *w, const float *bias, const int32_t *start,
+                                             void *out, int64_t out_rs, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
+                                             void *stream) {
+  return conv_bound_fwd(true, x, x_rs, w, bias, start, out, out_rs, B, L, Dn, k, dtype_io, stream);
+}
+
+extern "C" int apertis_dwconv_silu_doc_fwd(const void *x, int64_t x_rs, const float *w, const float *bias, const int32_t *start,
+                                           void *out, int64_t out_rs, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
+                                           void *stream) {
+  return conv_bound_fwd(false, x, x_rs, w, bias, start, out, out_rs, B, L, Dn, k, dtype_io, stream);
+}
+
+// the backward of the plain rows (`doc` false; start, end unused) and of packed rows
+static int conv_bwd(bool doc, const void *x, int64_t x_rs, const float *w, const float *bias, const void *dout, int64_t dout_rs,
+                    const void *dout2, int64_t dout2_rs, const int32_t *start, const int32_t *end, void *dx, int64_t dx_rs,
+                    float *dw_part, float *db_part, float *dw, float *db, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
+                    void *stream) {
+  if (!x || !w || !bias || !dout || !dx || !dw_part || !db_part || !dw || !db || B < 0 || L < 0) return APERTIS_ERR_ARG;
+  // (the packed form refuses an unknown dtype here, the plain form after the shapes, where its dispatch meets it)
+  if (doc && (!start || !end || (dtype_io != APERTIS_F32 && dtype_io != APERTIS_BF16))) return APERTIS_ERR_ARG;
+  if (!dout2) dout2_rs = 0;
+  if (!rows_ok(Dn) || (x_rs | dout_rs | dout2_rs | dx_rs) % 4 || k < 2 || k > CONV_KMAX || (doc && L >= 0x7fffffffLL))
+    return APERTIS_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = conv_blocks(B, L, Dn);
+  const Geo g = make_geo(Dn);
+  // per chunk and channel k tap sums and the bias sum (packed: in two floats); up to 68 KiB at k = 16, 72 KiB packed
+  const size_t lds = (size_t)g.RP * std::min(g.CPR, 256) * 4 * (k + (doc ? 2 : 1)) * sizeof(float);
+  const dim3 grid(nblk), block(256);
+#define CONV_BWD(KM_, KW_, DOC_)                                                                                                   \
+  CONV_TYPES(dtype_io, launch_lds(dwconv_silu_bwd_k<T, KM_, KW_, DOC_>, grid, block, lds, st, (const T *)x, x_rs, w, bias,         \
+                                  (const T *)dout, dout_rs, (const T *)dout2, dout2_rs, start, end, (T *)dx, dx_rs, dw_part, db_part, \
+                                  B, L, (int)Dn, (int)k))
+  if (doc) { if (k > 4) CONV_BWD(CONV_KMAX, 0, true); else CONV_BWD(4, 0, true); }
+  else if (k > 4) CONV_BWD(CONV_KMAX, 0, false);
+  else if (k == 4) CONV_BWD(4, 4, false);
+  else if (k == 3) CONV_BWD(3, 3, false);
+  else CONV_BWD(2, 2, false);
+#undef CONV_BWD
+  hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn * k, 64)), dim3(1024), 0, st, dw_part, dw, (int64_t)nblk,
+                     Dn * k);
+  hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn, 64)), dim3(1024), 0, st, db_part, db, (int64_t)nblk, Dn);
   return apertis_check_launch();
 }
 
@@ -1186,28 +909,8 @@ extern "C" int apertis_dwconv_silu_bwd2(const void *x, int64_t x_rs, const float
                                         int64_t dout_rs, const void *dout2, int64_t dout2_rs, void *dx, int64_t dx_rs,
                                         float *dw_part, float *db_part, float *dw, float *db, int64_t B, int64_t L, int64_t Dn,
                                         int64_t k, int dtype_io, void *stream) {
-  if (!x || !w || !bias || !dout || !dx || !dw_part || !db_part || !dw || !db || B < 0 || L < 0) return APERTIS_ERR_ARG;
-  if (!dout2) dout2_rs = 0;
-  if (!rows_ok(Dn) || (x_rs | dout_rs | dout2_rs | dx_rs) % 4 || k < 2 || k > CONV_KMAX) return APERTIS_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = conv_blocks(B, L, Dn);
-  {
-    Geo g = make_geo(Dn);
-    size_t lds = (size_t)g.RP * std::min(g.CPR, 256) * 4 * (k + 1) * sizeof(float);
-    dim3 grid(nblk), block(256);
-    if (k > 4) {  // (up to 68 KiB at k = 16)
-      CONV_TYPES(dtype_io, launch_lds(dwconv_silu_bwd_kn<T>, grid, block, lds, st, (const T *)x, x_rs, w, bias, (const T *)dout,
-                                      dout_rs, (const T *)dout2, dout2_rs, (T *)dx, dx_rs, dw_part, db_part, B, L, (int)Dn, (int)k));
-    } else {
-      CONV_DISPATCH(k, dtype_io, launch_lds(dwconv_silu_bwd_k<T, KW>, grid, block, lds, st, (const T *)x, x_rs, w,
-                                                    bias, (const T *)dout, dout_rs, (const T *)dout2, dout2_rs, (T *)dx, dx_rs,
-                                                    dw_part, db_part, B, L, (int)Dn));
-    }
-  }
-  hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn * k, 64)), dim3(1024), 0, st, dw_part, dw, (int64_t)nblk,
-                     Dn * k);
-  hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn, 64)), dim3(1024), 0, st, db_part, db, (int64_t)nblk, Dn);
-  return apertis_check_launch();
+  return conv_bwd(false, x, x_rs, w, bias, dout, dout_rs, dout2, dout2_rs, nullptr, nullptr, dx, dx_rs, dw_part, db_part, dw, db, B,
+                  L, Dn, k, dtype_io, stream);
 }
 
 extern "C" int apertis_dwconv_silu_bwd(const void *x, int64_t x_rs, const float *w, const float *bias, const void *dout,
@@ -1218,48 +921,12 @@ extern "C" int apertis_dwconv_silu_bwd(const void *x, int64_t x_rs, const float 
                                   dtype_io, stream);
 }
 
-extern "C" int apertis_dwconv_silu_doc_fwd(const void *x, int64_t x_rs, const float *w, const float *bias, const int32_t *start,
-                                           void *out, int64_t out_rs, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io,
-                                           void *stream) {
-  if (!x || !w || !bias || !start || !out || B < 0 || L < 0) return APERTIS_ERR_ARG;
-  if (dtype_io != APERTIS_F32 && dtype_io != APERTIS_BF16) return APERTIS_ERR_ARG;
-  if (!rows_ok(Dn) || (x_rs | out_rs) % 4 || x_rs < Dn || out_rs < Dn || k < 2 || k > CONV_KMAX || L >= 0x7fffffffLL)
-    return APERTIS_ERR_UNSUPPORTED;
-  const uintptr_t piece = dtype_io == APERTIS_BF16 ? 8 : 16;        // a thread moves four channels at a time
-  if ((uintptr_t)x % piece || (uintptr_t)out % piece) return APERTIS_ERR_UNSUPPORTED;
-  if (B == 0 || L == 0) return APERTIS_OK;
-  const int CPR = (int)(Dn / 4), CB = std::min(CPR, 64);
-  const int64_t nchunks = ceil_div64(L, CONV_TILE_T), ncb = ceil_div64(CPR, CB);
-  if (B * nchunks * ncb >= 0x7fffffffLL) return APERTIS_ERR_UNSUPPORTED;
-  // taps + tile as stored + the tile's starts: at most 16 + 79 KiB at k = 16, fp32; 27 KiB at k = 4, Dn = 176, bf16
-  const size_t lds = (size_t)k * CB * sizeof(float4) + (size_t)(CONV_TILE_T + k - 1) * CB * piece + CONV_TILE_T * sizeof(int32_t);
-  CONV_TYPES(dtype_io, launch_lds(dwconv_silu_doc_fwd_k<T>, dim3((unsigned)(B * nchunks * ncb)), dim3(256), lds, (hipStream_t)stream,
-                                  (const T *)x, x_rs, w, bias, start, (T *)out, out_rs, L, CPR, (int)k, CB, (int)nchunks, (int)ncb));
-  return apertis_check_launch();
-}
-
 extern "C" int apertis_dwconv_silu_doc_bwd(const void *x, int64_t x_rs, const float *w, const float *bias, const void *dout,
                                            int64_t dout_rs, const void *dout2, int64_t dout2_rs, const int32_t *start,
                                            const int32_t *end, void *dx, int64_t dx_rs, float *dw_part, float *db_part, float *dw,
                                            float *db, int64_t B, int64_t L, int64_t Dn, int64_t k, int dtype_io, void *stream) {
-  if (!x || !w || !bias || !dout || !start || !end || !dx || !dw_part || !db_part || !dw || !db || B < 0 || L < 0) return APERTIS_ERR_ARG;
-  if (dtype_io != APERTIS_F32 && dtype_io != APERTIS_BF16) return APERTIS_ERR_ARG;
-  if (!dout2) dout2_rs = 0;
-  if (!rows_ok(Dn) || (x_rs | dout_rs | dout2_rs | dx_rs) % 4 || k < 2 || k > CONV_KMAX || L >= 0x7fffffffLL) return APERTIS_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = conv_blocks(B, L, Dn);
-  Geo g = make_geo(Dn);
-  const size_t lds = (size_t)g.RP * std::min(g.CPR, 256) * 4 * (k + 2) * sizeof(float);   // (up to 72 KiB at k = 16)
-  dim3 grid(nblk), block(256);
-#define DOC_BWD(KM_)                                                                                                          \
-  CONV_TYPES(dtype_io, launch_lds(dwconv_silu_doc_bwd_k<T, KM_>, grid, block, lds, st, (const T *)x, x_rs, w, bias, (const T *)dout, \
-                                  dout_rs, (const T *)dout2, dout2_rs, start, end, (T *)dx, dx_rs, dw_part, db_part, B, L, (int)Dn, (int)k))
-  if (k > 4) DOC_BWD(CONV_KMAX); else DOC_BWD(4);
-#undef DOC_BWD
-  hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn * k, 64)), dim3(1024), 0, st, dw_part, dw, (int64_t)nblk,
-                     Dn * k);
-  hipLaunchKernelGGL(colsum_rows_k, dim3((unsigned)ceil_div64(Dn, 64)), dim3(1024), 0, st, db_part, db, (int64_t)nblk, Dn);
-  return apertis_check_launch();
+  return conv_bwd(true, x, x_rs, w, bias, dout, dout_rs, dout2, dout2_rs, start, end, dx, dx_rs, dw_part, db_part, dw, db, B, L, Dn,
+                  k, dtype_io, stream);
 }
 
 extern "C" int apertis_cast_transpose(const float *src, void *dst, void *dstT, int64_t E, int64_t R, int64_t C,

@@ -16,76 +16,19 @@ from ._base import _ColSlot, _f32, _grad_out, _require_gpu, _rows, _slot_of
 # ----------------------------------------------------------------------------------------------
 # SSM companions: depthwise causal conv + SiLU, post-scan gate
 # ----------------------------------------------------------------------------------------------
-class _DwConvSilu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, b):
-        _require_gpu(x, w, b)
-        lib = _lib.load()
-        B, L, Dn = x.shape
-        ctx.slot = _slot_of(x)
-        x, x_rs = _rows(x, Dn)
-        w2 = _f32(w).reshape(Dn, -1)
-        b2 = _f32(b)
-        k = w2.shape[1]
-        out = torch.empty(B, L, Dn, device=x.device, dtype=x.dtype)
-        check(lib.apertis_dwconv_silu_fwd(ptr(x), x_rs, ptr(w2), ptr(b2), ptr(out), Dn, B, L, Dn, k, dtype_code(x),
-                                          stream_ptr()), "apertis_dwconv_silu_fwd")
-        ctx.save_for_backward(x, w2, b2)
-        ctx.wshape = w.shape
-        return out
-
-    @staticmethod
-    def backward(ctx, dout, dout2=None):
-        lib = _lib.load()
-        x, w2, b2 = ctx.saved_tensors
-        B, L, Dn = x.shape
-        k = w2.shape[1]
-        if dout is None:
-            dout, dout2 = dout2, None
-        if dout is None:
-            return None, None, None
-        # (the kernel reads both gradients in the io dtype: the "same bits as autograd's add" claim of the pair form holds only
-        # then - a consumer that hands back another dtype is cast here, as autograd's own accumulation would cast it)
-        dout = dout.to(x.dtype).contiguous()
-        if dout2 is not None:
-            dout2 = dout2.to(x.dtype).contiguous()
-        nblk = lib.apertis_dwconv_bwd_blocks(B, L, Dn)
-        dev = x.device
-        dx, dx_rs = _grad_out(ctx.slot, (B, L), Dn, x.dtype, dev)
-        dw_part = torch.empty(nblk, Dn, k, device=dev, dtype=torch.float32)
-        db_part = torch.empty(nblk, Dn, device=dev, dtype=torch.float32)
-        dw = torch.empty(Dn, k, device=dev, dtype=torch.float32)
-        db = torch.empty(Dn, device=dev, dtype=torch.float32)
-        check(lib.apertis_dwconv_silu_bwd2(ptr(x), x.stride(-2), ptr(w2), ptr(b2), ptr(dout), Dn, ptr(dout2), Dn, ptr(dx), dx_rs,
-                                           ptr(dw_part), ptr(db_part), ptr(dw), ptr(db), B, L, Dn, k, dtype_code(x),
-                                           stream_ptr()), "apertis_dwconv_silu_bwd")
-        return dx, dw.reshape(ctx.wshape), db
-
-
 # APERTIS_NO_DWCONV_PAIR=1: the conv output as ONE tensor for both consumers (autograd adds their gradients in a pass of its own)
 DWCONV_PAIR = not _os.environ.get("APERTIS_NO_DWCONV_PAIR")
-
-
-class _DwConvSiluPair(_DwConvSilu):
-    """The conv output handed out TWICE (two views of one tensor) for its two consumers - x_param_proj and the scan
-    (reference core.py:376 and :388-396): their gradients then reach this node separately and the backward kernel adds them
-    where it reads the rows, instead of autograd running a [B, L, Dn] add in front of it (30 us per layer at the bench shape;
-    the sum is rounded to the io dtype as that add rounds it: the same bits).
-    CONTRACT: the two outputs alias one storage, so neither may be written in place by a consumer (autograd marks the second a
-    view made inside a custom Function and raises on an in-place op under grad mode; the model's two consumers only read).
-    For the grad-enabled path only - without a gradient to merge there is nothing to gain from the alias (dwconv_silu_pair)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        out = _DwConvSilu.forward(ctx, x, w, b)
-        ctx.set_materialize_grads(False)
-        return out, out.view_as(out)
-
 
 # APERTIS_SSM_LEFT_PAD=1: a left-padded prefill of a selective_ssm model (eval, no autograd) gives every row what it gets alone -
 # the conv treats a row's pad prefix as "before the sequence" (dwconv_silu(start=...)), which keeps the scan's state at exactly
 # 0 up to the first real token.  Off by default: the reference runs the pads through conv and scan (DESIGN.md section 7).
 SSM_LEFT_PAD = _os.environ.get("APERTIS_SSM_LEFT_PAD", "0") == "1"
+
+# APERTIS_SSM_PACKED=1: a selective_ssm model takes PACKED rows (document_ids; ApertisTrainer(pack_sequences=True)), in training
+# and in eval forwards, and every document of a row gets what it gets in a row of its own: the conv stops at a document's first
+# token (dwconv_silu(layout=...)) and the scan's state is reset there (ops.scan_gate_dt(layout=...)).  Off by default: the
+# reference has no packed rows (DESIGN.md section 7), and with it off such a model refuses them as before.
+SSM_PACKED = _os.environ.get("APERTIS_SSM_PACKED", "0") == "1"
 
 
 def left_pad_starts(attention_mask):
@@ -104,31 +47,6 @@ def left_pad_starts(attention_mask):
     return (L - n).to(torch.int32)
 
 
-def _dwconv_silu_start(x, w, b, start):
-    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad):
-        raise ApertisHipError("dwconv_silu(start=...) is forward only (a left-padded inference prefill): not under autograd")
-    _require_gpu(x, w, b, start)
-    lib = _lib.load()
-    B, L, Dn = x.shape
-    if start.dtype != torch.int32 or tuple(start.shape) != (B,):
-        raise ApertisHipError(f"start must be int32 [{B}], got {start.dtype} {tuple(start.shape)}")
-    x, x_rs = _rows(x, Dn)
-    w2 = _f32(w).reshape(Dn, -1)
-    b2 = _f32(b)
-    start = start.contiguous()
-    out = torch.empty(B, L, Dn, device=x.device, dtype=x.dtype)
-    check(lib.apertis_dwconv_silu_start_fwd(ptr(x), x_rs, ptr(w2), ptr(b2), ptr(start), ptr(out), Dn, B, L, Dn, w2.shape[1],
-                                            dtype_code(x), stream_ptr()), "apertis_dwconv_silu_start_fwd")
-    return out
-
-
-# APERTIS_SSM_PACKED=1: a selective_ssm model takes PACKED rows (document_ids; ApertisTrainer(pack_sequences=True)), in training
-# and in eval forwards, and every document of a row gets what it gets in a row of its own: the conv stops at a document's first
-# token (dwconv_silu(layout=...)) and the scan's state is reset there (ops.scan_gate_dt(layout=...)).  Off by default: the
-# reference has no packed rows (DESIGN.md section 7), and with it off such a model refuses them as before.
-SSM_PACKED = _os.environ.get("APERTIS_SSM_PACKED", "0") == "1"
-
-
 def doc_layout_check(what, layout, B, L, device):
     """(start, end) of an ops.DocumentLayout, checked against rows [B, L] on `device` as the kernels read them."""
     start, end = getattr(layout, "start", None), getattr(layout, "end", None)
@@ -139,37 +57,75 @@ def doc_layout_check(what, layout, B, L, device):
     return start, end
 
 
-class _DwConvSiluDoc(torch.autograd.Function):
-    """_DwConvSilu on packed rows: both directions stop at the document boundaries of `layout`."""
+def _conv_operands(x, w, b):
+    """What every conv forward hands its kernel: x [B,L,Dn] as rows with their stride, the taps as fp32 [Dn, k], the bias as
+    fp32, and the output to fill."""
+    B, L, Dn = x.shape
+    x, x_rs = _rows(x, Dn)
+    return x, x_rs, _f32(w).reshape(Dn, -1), _f32(b), torch.empty(B, L, Dn, device=x.device, dtype=x.dtype)
+
+
+def _dwconv_silu_start(x, w, b, start):
+    if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad):
+        raise ApertisHipError("dwconv_silu(start=...) is forward only (a left-padded inference prefill): not under autograd")
+    _require_gpu(x, w, b, start)
+    lib = _lib.load()
+    B, L, Dn = x.shape
+    if start.dtype != torch.int32 or tuple(start.shape) != (B,):
+        raise ApertisHipError(f"start must be int32 [{B}], got {start.dtype} {tuple(start.shape)}")
+    x, x_rs, w2, b2, out = _conv_operands(x, w, b)
+    start = start.contiguous()
+    check(lib.apertis_dwconv_silu_start_fwd(ptr(x), x_rs, ptr(w2), ptr(b2), ptr(start), ptr(out), Dn, B, L, Dn, w2.shape[1],
+                                            dtype_code(x), stream_ptr()), "apertis_dwconv_silu_start_fwd")
+    return out
+
+
+class _DwConvSilu(torch.autograd.Function):
+    """silu(depthwise causal conv) and its backward.  `layout` (None, or packed rows: both directions stop at its document
+    boundaries) picks the entry points.
+    `pair`: the output handed out TWICE (two views of one tensor) for its two consumers - x_param_proj and the scan
+    (reference core.py:376 and :388-396): their gradients then reach this node separately and the backward kernel adds them
+    where it reads the rows, instead of autograd running a [B, L, Dn] add in front of it (30 us per layer at the bench shape;
+    the sum is rounded to the io dtype as that add rounds it: the same bits).
+    CONTRACT: the two outputs alias one storage, so neither may be written in place by a consumer (autograd marks the second a
+    view made inside a custom Function and raises on an in-place op under grad mode; the model's two consumers only read).
+    For the grad-enabled path only - without a gradient to merge there is nothing to gain from the alias (dwconv_silu_pair)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, layout):
+    def forward(ctx, x, w, b, layout, pair):
         _require_gpu(x, w, b)
         lib = _lib.load()
         B, L, Dn = x.shape
-        start, end = doc_layout_check("dwconv_silu", layout, B, L, x.device)
+        bounds = () if layout is None else doc_layout_check("dwconv_silu", layout, B, L, x.device)
         ctx.slot = _slot_of(x)
-        x, x_rs = _rows(x, Dn)
-        w2 = _f32(w).reshape(Dn, -1)
-        b2 = _f32(b)
-        out = torch.empty(B, L, Dn, device=x.device, dtype=x.dtype)
-        check(lib.apertis_dwconv_silu_doc_fwd(ptr(x), x_rs, ptr(w2), ptr(b2), ptr(start), ptr(out), Dn, B, L, Dn, w2.shape[1],
-                                              dtype_code(x), stream_ptr()), "apertis_dwconv_silu_doc_fwd")
-        ctx.save_for_backward(x, w2, b2, start, end)
+        x, x_rs, w2, b2, out = _conv_operands(x, w, b)
+        k = w2.shape[1]
+        if layout is None:
+            check(lib.apertis_dwconv_silu_fwd(ptr(x), x_rs, ptr(w2), ptr(b2), ptr(out), Dn, B, L, Dn, k, dtype_code(x),
+                                              stream_ptr()), "apertis_dwconv_silu_fwd")
+        else:
+            check(lib.apertis_dwconv_silu_doc_fwd(ptr(x), x_rs, ptr(w2), ptr(b2), ptr(bounds[0]), ptr(out), Dn, B, L, Dn, k,
+                                                  dtype_code(x), stream_ptr()), "apertis_dwconv_silu_doc_fwd")
+        ctx.save_for_backward(x, w2, b2, *bounds)
         ctx.wshape = w.shape
-        return out
+        if not pair:
+            return out
+        ctx.set_materialize_grads(False)
+        return out, out.view_as(out)
 
     @staticmethod
     def backward(ctx, dout, dout2=None):
         lib = _lib.load()
-        x, w2, b2, start, end = ctx.saved_tensors
+        x, w2, b2, *bounds = ctx.saved_tensors
         B, L, Dn = x.shape
         k = w2.shape[1]
         if dout is None:
             dout, dout2 = dout2, None
         if dout is None:
-            return None, None, None, None
-        dout = dout.to(x.dtype).contiguous()            # (as _DwConvSilu.backward: both gradients in the io dtype)
+            return None, None, None, None, None
+        # (the kernel reads both gradients in the io dtype: the "same bits as autograd's add" claim of the pair form holds only
+        # then - a consumer that hands back another dtype is cast here, as autograd's own accumulation would cast it)
+        dout = dout.to(x.dtype).contiguous()
         if dout2 is not None:
             dout2 = dout2.to(x.dtype).contiguous()
         nblk = lib.apertis_dwconv_bwd_blocks(B, L, Dn)
@@ -179,20 +135,13 @@ class _DwConvSiluDoc(torch.autograd.Function):
         db_part = torch.empty(nblk, Dn, device=dev, dtype=torch.float32)
         dw = torch.empty(Dn, k, device=dev, dtype=torch.float32)
         db = torch.empty(Dn, device=dev, dtype=torch.float32)
-        check(lib.apertis_dwconv_silu_doc_bwd(ptr(x), x.stride(-2), ptr(w2), ptr(b2), ptr(dout), Dn, ptr(dout2), Dn, ptr(start),
-                                              ptr(end), ptr(dx), dx_rs, ptr(dw_part), ptr(db_part), ptr(dw), ptr(db), B, L, Dn, k,
-                                              dtype_code(x), stream_ptr()), "apertis_dwconv_silu_doc_bwd")
-        return dx, dw.reshape(ctx.wshape), db, None
-
-
-class _DwConvSiluDocPair(_DwConvSiluDoc):
-    """_DwConvSiluPair on packed rows: the output as two views, one per consumer; same contract."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, layout):
-        out = _DwConvSiluDoc.forward(ctx, x, w, b, layout)
-        ctx.set_materialize_grads(False)
-        return out, out.view_as(out)
+        ins = (ptr(x), x.stride(-2), ptr(w2), ptr(b2), ptr(dout), Dn, ptr(dout2), Dn)
+        outs = (ptr(dx), dx_rs, ptr(dw_part), ptr(db_part), ptr(dw), ptr(db), B, L, Dn, k, dtype_code(x), stream_ptr())
+        if not bounds:
+            check(lib.apertis_dwconv_silu_bwd2(*ins, *outs), "apertis_dwconv_silu_bwd")
+        else:
+            check(lib.apertis_dwconv_silu_doc_bwd(*ins, ptr(bounds[0]), ptr(bounds[1]), *outs), "apertis_dwconv_silu_doc_bwd")
+        return dx, dw.reshape(ctx.wshape), db, None, None
 
 
 def dwconv_silu(x, weight, bias, start=None, layout=None):
@@ -206,20 +155,16 @@ def dwconv_silu(x, weight, bias, start=None, layout=None):
         raise ApertisHipError("dwconv_silu: start (a left-padded prefill) and layout (packed rows) do not go together")
     if start is not None:
         return _dwconv_silu_start(x, weight, bias, start)
-    if layout is not None:
-        return _DwConvSiluDoc.apply(x, weight, bias, layout)
-    return _DwConvSilu.apply(x, weight, bias)
+    return _DwConvSilu.apply(x, weight, bias, layout, False)
 
 
 def dwconv_silu_pair(x, weight, bias, layout=None):
-    """dwconv_silu as two views of the one output, one per consumer: see _DwConvSiluPair (under no_grad: one tensor, twice).
+    """dwconv_silu as two views of the one output, one per consumer: see _DwConvSilu (under no_grad: one tensor, twice).
     layout: packed rows, as in dwconv_silu."""
     if not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or bias.requires_grad)):
         out = dwconv_silu(x, weight, bias, layout=layout)
         return out, out
-    if layout is not None:
-        return _DwConvSiluDocPair.apply(x, weight, bias, layout)
-    return _DwConvSiluPair.apply(x, weight, bias)
+    return _DwConvSilu.apply(x, weight, bias, layout, True)
 
 
 class _DropoutAdd(torch.autograd.Function):

@@ -67,7 +67,7 @@ def _conv_inputs(dev, Dn, k, dt, layout, seed):
 @pytest.mark.parametrize("layout", ["dense", "xz"])
 @pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("k", [2, 4, 8, 16])
-@pytest.mark.parametrize("Dn", [12, 176])
+@pytest.mark.parametrize("Dn", [12, 176, 272])     # (272: 68 chunks per row - two channel blocks, the second four chunks wide)
 def test_start_kernel_is_the_plain_forward_of_every_row_alone(dev, ops, Dn, k, dt, layout):
     x, w, b = _conv_inputs(dev, Dn, k, dt, layout, 100 * Dn + k)
     start = torch.tensor(STARTS, dtype=torch.int32, device=dev)
