@@ -1,4 +1,5 @@
-"""ctypes binding of libapertis_hip.so (the C ABI declared in include/apertis_hip.h).
+"""ctypes binding of libapertis_hip.so (the C ABI declared in include/apertis_hip.h).  The argument lists and constants are
+not repeated here: they are read from the headers at import (parse_header), so declaring an entry point there binds it.
 
 The library is loaded lazily (safe after fork(); DataLoader workers never touch HIP) and there
 is NO fallback: if the .so is missing or a call returns an error code, ApertisHipError is
@@ -6,15 +7,15 @@ raised.  Nothing in this package routes compute through PyTorch eager ops or the
 """
 import ctypes
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # APERTIS_HIP_LIB: developer switch - another build of the same library (tools/ A/B runs); never a fallback
 LIB_PATH = os.environ.get("APERTIS_HIP_LIB") or os.path.join(_HERE, "libapertis_hip.so")
-
-F32, BF16 = 0, 1
-ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU = 0, 1, 2, 3
-ACT_SAVE_GRAD, ACT_MUL_SAVED = 0x100, 0x200      # flags of apertis_grouped_gemm_nt's `act` (apertis_hip.h)
+# the C headers: what the library is compiled against (build.py watches these two files) and what this binding is read from
+INCLUDE_DIR = os.path.join(_HERE, "..", "include")
+HEADERS = ("apertis_hip.h", "apertis_hip_ext.h")
 
 
 class ApertisHipError(RuntimeError):
@@ -24,198 +25,72 @@ class ApertisHipError(RuntimeError):
 _lock = threading.Lock()
 _lib = None
 
-_vp, _i64, _i32, _f32, _u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_uint64
-_f64 = ctypes.c_double
-
-# name -> (restype, argtypes).  Order and meaning mirror include/apertis_hip.h exactly.
-ABI_VERSION = (4 << 16) | 12     # = APERTIS_ABI_VERSION of include/apertis_hip.h (tests/test_host_cpu.py compares them)
-SIGNATURES = {
-    "apertis_abi_version": (ctypes.c_int, []),
-    "apertis_arch": (ctypes.c_char_p, []),
-    "apertis_strerror": (ctypes.c_char_p, [_i32]),
-    "apertis_scan_chunk_len": (_i64, [_i64, _i64, _i64]),
-    "apertis_scan_num_chunks": (_i64, [_i64, _i64, _i64]),
-    "apertis_selective_scan_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
-                                          _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
-    "apertis_selective_scan_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64,
-                                          _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
-    "apertis_ssm_gate_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_ssm_gate_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
-                                    _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_ssm_gate_bwd_blocks": (_i64, [_i64, _i64]),
-    "apertis_scan_gate_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "apertis_scan_gate_chunk_len": (_i64, []),
-    "apertis_scan_gate_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
-                                     _vp, ctypes.c_uint32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
-    "apertis_scan_gate_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp,
-                                     _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _i64, _i64,
-                                     _i64, _i64, _i32, _i32, _i32, _vp]),
-    "apertis_scan_lean_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                                     _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_scan_lean_fwd_dt": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
-                                        _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_scan_lean_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64,
-                                     _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_scan_lookback_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "apertis_scan_lookback_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                                         ctypes.c_uint32, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_scan_lookback_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp,
-                                         _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _i64, _i64, _i64,
-                                         _i64, _i32, _vp]),
-    "apertis_ssm_decode_conv": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_ssm_decode_state": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i32,
-                                        _i32, _vp]),
-    "apertis_ssm_decode_state_dt": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64,
-                                           _i64, _i64, _i32, _i32, _vp]),
-    "apertis_dropout_add_fwd": (_i32, [_vp, _vp, _vp, _i64, _f32, _u64, _i32, _i32, _vp]),
-    "apertis_dropout_bwd": (_i32, [_vp, _vp, _i64, _f32, _u64, _i32, _i32, _vp]),
-    "apertis_dwconv_silu_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_dwconv_silu_start_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_dwconv_silu_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
-                                       _i64, _i32, _vp]),
-    "apertis_dwconv_silu_bwd2": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
-                                        _i64, _i32, _vp]),
-    "apertis_dwconv_bwd_blocks": (_i64, [_i64, _i64, _i64]),
-    "apertis_dwconv_silu_doc_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_dwconv_silu_doc_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64,
-                                           _i64, _i64, _i64, _i32, _vp]),
-    "apertis_moe_gate_topk_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
-    "apertis_decode_pre_conv": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_decode_pre_state": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
-                                        _i32, _i32, _vp]),
-    "apertis_decode_dense_gemv": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp]),
-    "apertis_decode_post": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_decode_inproj": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64,
-                                     _i64, _vp]),
-    "apertis_moe_enter_small": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                       _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_moe_route_small": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
-                                       _i32, _i32, _vp]),
-    "apertis_moe_gate_topk_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
-    "apertis_skinny_linear_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_skinny_linear_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_skinny_linear_bwd_blocks": (_i64, [_i64]),
-    "apertis_moe_plan_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "apertis_moe_plan": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
-    "apertis_moe_gather_ln_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_moe_gather_ln_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
-                                         _i32, _i32, _vp]),
-    "apertis_moe_gather_ln_bwd_blocks": (_i64, [_i64]),
-    "apertis_layernorm_fwd": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_layernorm_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _u64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_layernorm_combine_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                             _i64, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_dropout_add_layernorm_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _i64, _f32,
-                                                 _u64, _i32, _i32, _vp]),
-    "apertis_dropout_add_layernorm_router_fwd": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp,
-                                                        _vp, _vp, _i64, _i64, _i64, _f32, _u64, _i32, _i32, _vp]),
-    "apertis_layernorm_bwd_blocks": (_i64, [_i64, _i64]),
-    "apertis_rmsnorm_fwd": (_i32, [_vp, _vp, _f32, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_rmsnorm_bwd": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _f32, _u64, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_rmsnorm_bwd_blocks": (_i64, [_i64, _i64]),
-    "apertis_dropout_add_rmsnorm_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _i64, _f32, _u64, _i32, _i32,
-                                               _vp]),
-    "apertis_swiglu_fwd": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp]),
-    "apertis_swiglu_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
-    "apertis_moe_combine_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
-    "apertis_moe_combine_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                       _i32, _i32, _vp]),
-    "apertis_grouped_gemm_nt": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _f32, _u64,
-                                       _i32, _i32, _vp]),
-    "apertis_grouped_gemm_nt_saves_grad": (_i32, [_i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32]),
-    "apertis_grouped_gemm_nt_q": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _f32, _u64,
-                                         _i32, _i32, _vp, _vp]),
-    "apertis_grouped_gemm_tn_workspace_bytes": (_i64, [_i64, _i32]),
-    "apertis_grouped_gemm_tn_dense_variant": (_i32, [_i64, _i64]),
-    "apertis_grouped_gemm_tn_pair": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64,
-                                            _vp, _i64, _i32, _vp]),
-    "apertis_grouped_gemm_tn_pair_q": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64,
-                                              _vp, _i64, _i32, _i32, _vp]),
-    "apertis_grouped_gemm_tn_q": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _vp]),
-    "apertis_cast_transpose": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_weight_prep_entry_bytes": (_i64, []),
-    "apertis_weight_prep": (_i32, [_vp, _i64, _i64, _vp]),
-    "apertis_grouped_gemm_tn": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _vp]),
-    "apertis_moe_gate_topk_aux_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _vp]),
-    "apertis_moe_gate_topk_aux_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _i64, _i64, _i64, _vp]),
-    "apertis_moe_gate_topk_noisy_aux_fwd": (_i32, [_vp, _vp, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32,
-                                                   _f32, _vp]),
-    "apertis_moe_gate_topk_noisy_aux_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _f32, _u64, _vp, _vp, _vp,
-                                                   _i64, _i64, _i64, _vp]),
-    "apertis_moe_gate_aux_blocks": (_i64, [_i64]),
-    "apertis_router_fwd": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_router_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_router_bwd_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64,
-                                       _i32, _vp]),
-    "apertis_router_bwd_blocks": (_i64, [_i64]),
-    "apertis_boundary_router_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp]),
-    "apertis_tiny_linear_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_tiny_linear_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_tiny_linear_doc_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_tiny_linear_bwd_pad": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_tiny_linear_bwd_blocks": (_i64, [_i64]),
-    "apertis_cross_entropy_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_cross_entropy_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_cross_entropy_fwd_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_colsum_f32": (_i32, [_vp, _vp, _i64, _i64, _vp]),
-    "apertis_act_dropout_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _u64, _i32, _vp]),
-    "apertis_opt_chunk_elems": (_i64, []),
-    "apertis_grad_sumsq": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
-    "apertis_clip_coef": (_i32, [_vp, _i64, _f32, _vp, _vp, _vp]),
-    "apertis_adamw_step": (_i32, [_vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _vp, _vp]),
-    "apertis_rope_qk_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_rope_qk_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_attention_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _u64,
-                                     _i32, _vp]),
-    "apertis_attention_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "apertis_attention_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                     _i64, _i64, _i64, _i64, _f32, _u64, _i32, _vp]),
-    "apertis_attention_full_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _u64,
-                                          _i32, _vp]),
-    "apertis_attention_full_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                          _i64, _i64, _i64, _i64, _i64, _f32, _u64, _i32, _vp]),
-    "apertis_attention_doc_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32,
-                                         _u64, _i32, _vp]),
-    "apertis_attention_doc_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                         _vp, _i64, _i64, _i64, _i64, _i64, _f32, _u64, _i32, _vp]),
-    "apertis_attention_window_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32,
-                                            _u64, _i32, _vp]),
-    "apertis_attention_window_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
-                                            _vp, _i64, _i64, _i64, _i64, _i64, _f32, _u64, _i32, _vp]),
-    "apertis_rope_kv_append": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64,
-                                      _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_attention_decode_splits": (_i64, [_i64, _i64, _i64, _i64]),
-    "apertis_attention_decode_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
-    "apertis_attention_decode": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
-                                        _i64, _i64, _i64, _i32, _vp]),
-    "apertis_rope_kv_append_at": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
-                                         _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_attention_decode_at": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
-                                           _i64, _i64, _i64, _i32, _vp]),
-    "apertis_rope_kv_append_chunk": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
-                                            _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_attention_chunk_splits": (_i64, [_i64, _i64, _i64, _i64, _i64]),
-    "apertis_attention_chunk_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
-    "apertis_attention_chunk": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
-                                       _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_attention_dead_rows": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-    "apertis_token_counts": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "apertis_sample_next": (_i32, [_vp, _i64, _i32, _i64, _i64, _vp, _f32, _i32, _f32, _i64, _f32, _u64, _vp, _i64, _vp, _vp, _vp,
-                                   _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-}
+# The closed table of value types the headers use; every pointer parameter is a c_void_p and `const char *` is returned as c_char_p.
+_CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64,
+           "float": ctypes.c_float, "double": ctypes.c_double}
+_DECL = re.compile(r"^[ \t]*([\w \t*]+?)[ \t]*\b(apertis_\w+)[ \t]*\(([^()]*)\)\s*;", re.M)
+_PARAM = re.compile(r"\s*(?:const\s+)?(\w+)(\s*\*\s*|\s+)(\w+)\s*")
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(APERTIS_\w+)[ \t]+(\S.*?)[ \t]*$", re.M)
+_INT_EXPR = re.compile(r"(?:0[xX][0-9a-fA-F]+|\d+|<<|[()|\- ])+")
 
 
-# Entry points added after the 4.12 table (include/apertis_hip_ext.h): SIGNATURES mirrors apertis_hip.h name for name and is frozen
-# with it; these are exported by the same library under the same ABI version and bound the same way.
-EXT_SIGNATURES = {
-    # apertis_attention_decode_at with `window` after `len`
-    "apertis_attention_decode_window_at": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
-                                                  _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
-    # apertis_attention_chunk with `window` after `n`
-    "apertis_attention_chunk_window": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
-                                              _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
-}
+def parse_header(text, where):
+    """(signatures, constants) of one C header's text: `RET apertis_name(ARGS);` -> name: (restype, [argtypes]) in declaration
+    order, and `#define APERTIS_NAME <integer expression>` -> APERTIS_NAME: int.  #include is not followed.  Function-like macros
+    and non-integer values are skipped; a declaration this reader cannot type raises ApertisHipError (`where` names the header)
+    - a row skipped or guessed here would be a call with the wrong argument list."""
+    def fail(what, why):
+        raise ApertisHipError(f"{where}: {what}: {why}")
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {}
+    for name, value in _DEFINE.findall(text):
+        if _INT_EXPR.fullmatch(value):
+            try:
+                consts[name] = int(eval(value, {"__builtins__": {}}))       # digits, hex, ( ) << | - only: see _INT_EXPR
+            except (SyntaxError, TypeError):
+                fail(f"#define {name} {value}", "not an integer expression")
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    sigs = {}
+    for ret, name, params in _DECL.findall(text):
+        ret = " ".join(ret.replace("*", " * ").split())
+        restype = ctypes.c_char_p if ret == "const char *" else _CTYPES.get(ret)
+        if restype is None or name in sigs:
+            fail(f"declaration of {name}", "declared twice" if name in sigs else f"return type `{ret}` is not in the binding's type table")
+        argtypes = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            m = _PARAM.fullmatch(p)
+            if m is None:
+                fail(f"declaration of {name}", f"parameter `{p.strip()}` is not `type name`")
+            ctype = ctypes.c_void_p if "*" in m.group(2) else _CTYPES.get(m.group(1))
+            if ctype is None:
+                fail(f"declaration of {name}", f"parameter type `{m.group(1)}` is not in the binding's type table")
+            argtypes.append(ctype)
+        sigs[name] = (restype, argtypes)
+    stray = re.search(r"\bapertis_\w+\s*\(", _DECL.sub("", text))
+    if stray:
+        fail(f"declaration of {stray.group()[:-1].strip()}", "starts here but does not parse as `RET apertis_name(ARGS);`")
+    return sigs, consts
+
+
+def _read_header(name):
+    path = os.path.join(INCLUDE_DIR, name)
+    try:
+        with open(path, encoding="utf-8") as f:
+            return parse_header(f.read(), name)
+    except OSError as e:
+        raise ApertisHipError(f"{path}: the C header this binding is read from cannot be opened ({e.strerror}); "
+                              "there is no built-in table") from None
+
+
+# name -> (restype, argtypes), in declaration order: the headers ARE the tables (read once, here, at import).  EXT_SIGNATURES holds
+# the entry points added after the 4.12 table (apertis_hip_ext.h): exported by the same library under the same ABI version.
+(SIGNATURES, CONSTANTS), (EXT_SIGNATURES, _ext_consts) = (_read_header(h) for h in HEADERS)
+CONSTANTS.update(_ext_consts)
+ABI_VERSION, F32, BF16 = (CONSTANTS["APERTIS_" + n] for n in ("ABI_VERSION", "F32", "BF16"))
+ACT_NONE, ACT_GELU, ACT_RELU, ACT_SILU = (CONSTANTS["APERTIS_ACT_" + n] for n in ("NONE", "GELU", "RELU", "SILU"))
+ACT_SAVE_GRAD, ACT_MUL_SAVED = CONSTANTS["APERTIS_ACT_SAVE_GRAD"], CONSTANTS["APERTIS_ACT_MUL_SAVED"]   # flags of grouped_gemm_nt's `act`
+OK, ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = (CONSTANTS["APERTIS_" + n] for n in ("OK", "ERR_ARG", "ERR_UNSUPPORTED", "ERR_LAUNCH"))
 
 
 class _Lib:

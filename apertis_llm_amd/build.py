@@ -11,6 +11,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from ._lib import HEADERS, INCLUDE_DIR     # the C headers: one definition of where they are, shared with the binding that reads them
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
@@ -29,7 +31,7 @@ def _hipcc():
 
 def _deps_mtime():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs += [os.path.join(HERE, "..", "include", h) for h in ("apertis_hip.h", "apertis_hip_ext.h")]
+    hdrs += [os.path.join(INCLUDE_DIR, h) for h in HEADERS]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

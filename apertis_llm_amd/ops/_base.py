@@ -8,7 +8,7 @@ import threading
 
 import torch
 
-from .._lib import ApertisHipError, check, dtype_code, ptr, stream_ptr
+from .._lib import ERR_UNSUPPORTED, ApertisHipError, check, dtype_code, ptr, stream_ptr
 
 
 def _f32(t):
@@ -97,7 +97,7 @@ def _launch(name, fn, args, work=0.0, detail=None, nbytes=0.0, unwind=None):
 
 
 def _try_launch(name, fn, args, work=0.0, unwind=None):
-    """_launch for an entry point that may decline the shape: returns False on APERTIS_ERR_UNSUPPORTED (-2) WITHOUT recording
+    """_launch for an entry point that may decline the shape: returns False on APERTIS_ERR_UNSUPPORTED WITHOUT recording
     a timed launch (the caller then takes another form, which records its own), True when the launch went out.  `unwind` runs
     on EVERY non-zero return (declined, or an argument / launch error that check() is about to raise): see _launch."""
     t = _TIMER
@@ -108,7 +108,7 @@ def _try_launch(name, fn, args, work=0.0, unwind=None):
     rc = fn(*args)
     if rc != 0 and unwind is not None:
         unwind()
-    if rc == -2:
+    if rc == ERR_UNSUPPORTED:
         return False
     if timed:
         e.record()

@@ -550,7 +550,7 @@ ATTN_DECODE_FUSED = True
 # on): the eager loop's launch counts are pinned by tests, and flipping the default is a change of its own
 ATTN_DECODE_GRAPH = os.environ.get("APERTIS_MHA_DECODE_GRAPH", "0") == "1"
 
-ATTN_DECODE_MAX_SPLITS = 64          # = APERTIS_ATTN_DECODE_MAX_SPLITS
+ATTN_DECODE_MAX_SPLITS = _lib.CONSTANTS["APERTIS_ATTN_DECODE_MAX_SPLITS"]
 
 
 class KVLayer:

@@ -171,7 +171,7 @@ def decode_inproj(w_in, pre, conv_state, xn=None, boundary=None):
     rc = lib.apertis_decode_inproj(ptr(blk2), ptr(slot), ptr(wk), KK, ptr(res2), ptr(g), ptr(b), float(eps), ptr(y), ptr(x2), ptr(wc),
                                    wc.shape[-1], None, ptr(pre), ptr(conv_state), conv_state.shape[-1] + 1, ptr(gated), S, H, N, Dn,
                                    stream_ptr())
-    if rc == -2:
+    if rc == _lib.ERR_UNSUPPORTED:
         return None
     check(rc, "apertis_decode_inproj")
     return gated if xn is not None else (y.reshape(boundary[1].shape), gated)

@@ -184,7 +184,7 @@ def _nt_queue(device):
     key = (device, torch.cuda.current_stream(device).cuda_stream)
     q = _NT_QUEUE.get(key)
     if q is None:
-        q = _NT_QUEUE[key] = torch.zeros(512, device=device, dtype=torch.int32)     # APERTIS_NT_QUEUE_INTS: one counter per XCD
+        q = _NT_QUEUE[key] = torch.zeros(_lib.CONSTANTS["APERTIS_NT_QUEUE_INTS"], device=device, dtype=torch.int32)   # one counter per XCD
     return q
 
 

@@ -120,7 +120,7 @@ class _LinearCrossEntropy(torch.autograd.Function):
             if fused:
                 rc = lib.apertis_cross_entropy_fwd_bwd(ptr(logits), ptr(lab), ptr(lse), ptr(row_loss), ptr(gscale), ptr(logits), n,
                                                        L, V, labels.shape[1], n_pos, ignore_index, code, stream_ptr())
-                if rc == -2:
+                if rc == _lib.ERR_UNSUPPORTED:
                     fused = False
                 else:
                     check(rc, "apertis_cross_entropy_fwd_bwd")

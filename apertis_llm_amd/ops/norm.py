@@ -219,7 +219,7 @@ class _DropoutAddLN(torch.autograd.Function):
             rc = lib.apertis_layernorm_combine_bwd(ptr(y), ptr(g), ptr(mean), ptr(rstd), ptr(dxn2), ptr(dres), ptr(dx), p, seed,
                                                    ptr(part), ptr(dg), ptr(db), ptr(plan.slot_of), ptr(wf), ptr(yr), ptr(dyr), ptr(dw),
                                                    T, H, plan.K, dtype_code(y), dtype_code(dxn2), stream_ptr())
-            if rc != -2:
+            if rc != _lib.ERR_UNSUPPORTED:
                 check(rc, "apertis_layernorm_combine_bwd")
                 blkdt, blkshape = ctx.cfg[5], ctx.cfg[7]
                 return dyr.reshape(blkshape).to(blkdt), dx.reshape(shape), dg.to(wdt), db.to(bdt), None, None, None, None, dw, None
@@ -297,7 +297,7 @@ class _DropoutAddLNRouter(torch.autograd.Function):
                                                  ptr(xn), ptr(rg), ptr(rbe), ptr(rmean), ptr(rrstd), ptr(rw),
                                                  ptr(dlogits.float().contiguous()), ptr(rows), ptr(slot_of), KS or 0, ptr(part),
                                                  ptr(out), ptr(dg), ptr(db), T, H, N, dtype_code(y), dtype_code(xn), stream_ptr())
-            if rc != -2:                 # (-2 = APERTIS_ERR_UNSUPPORTED: the two calls below)
+            if rc != _lib.ERR_UNSUPPORTED:           # (declined: the two calls below)
                 check(rc, "apertis_boundary_router_bwd")
                 global FUSED_ROUTER_BWD_CALLS
                 FUSED_ROUTER_BWD_CALLS += 1

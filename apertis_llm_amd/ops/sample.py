@@ -16,8 +16,8 @@ from ._base import _launch, _require_gpu
 SAMPLE_FUSED = True
 # test hook: a [B, steps] tensor of uniforms in [0, 1) that replaces the counter hash, u = SAMPLE_UNIFORMS[b, step]
 SAMPLE_UNIFORMS = None
-SAMPLE_MAX_VOCAB = 262144                 # = APERTIS_SAMPLE_MAX_VOCAB of include/apertis_hip.h
-SAMPLE_MAX_ROWS = 65535                   # = APERTIS_SAMPLE_MAX_ROWS (the occurrence table's launch)
+SAMPLE_MAX_VOCAB = _lib.CONSTANTS["APERTIS_SAMPLE_MAX_VOCAB"]
+SAMPLE_MAX_ROWS = _lib.CONSTANTS["APERTIS_SAMPLE_MAX_ROWS"]          # (the occurrence table's launch)
 ERR_NOT_FINITE, ERR_UNIFORMS, ERR_TOKEN_ID = 1, 2, 4
 
 

@@ -302,7 +302,7 @@ class _ScanGateDt(torch.autograd.Function):
         part = torch.empty(nblk, N * K + N, device=xr.device, dtype=torch.float32)
         out = torch.empty(N * K + N, device=xr.device, dtype=torch.float32)
         check(lib.apertis_tiny_linear_bwd_pad(ptr(xr), ldx, ptr(w), ptr(d_dlt), ptr(dxp), Kp, ptr(part), ptr(out), T, K, N, zero_to,
-                                              dtype_code(xr), stream_ptr()), "apertis_tiny_linear_bwd")
+                                              dtype_code(xr), stream_ptr()), "apertis_tiny_linear_bwd_pad")
         return (dx, out[:N * K].reshape(N, K).to(wdt), (out[N * K:].to(bdt) if bdt is not None else None),
                 dA, dBt, dC, dxc, dz, dD, None, None, None, None)
 
@@ -371,16 +371,16 @@ def _scan_gate_forward(ctx, dlt, A_log, Bt, C, xc, z, D, h0, delta_softplus, ret
                 out.stride(-2), ptr(h_last), ptr(agg), ptr(h_in), ptr(ckpt), B, L, h, N, int(delta_softplus), stream_ptr())
         if dtp is not None and SCAN_DT_FUSED and dtp[0].dtype == torch.bfloat16:
             xr, ldx, w, b, R, _ = dtp          # (never under a layout: _ScanGateDt.forward refuses the pair)
-            _launch("apertis_scan_gate_fwd", lambda *a: rc.append(lib.apertis_scan_lean_fwd_dt(*a)) or (0 if rc[-1] == -2 else rc[-1]),
+            _launch("apertis_scan_gate_fwd", lambda *a: rc.append(lib.apertis_scan_lean_fwd_dt(*a)) or (0 if rc[-1] == _lib.ERR_UNSUPPORTED else rc[-1]),
                     (ptr(xr), ldx, ptr(w), ptr(b), R, ptr(dlt)) + tail, work + B * L * (2 * R + 4 * h))
             dt_done = lean = rc[-1] == 0
         if not lean:
             if not dt_done:
                 _tiny_linear_into(lib, dtp, dlt)
                 dt_done = True
-            _launch("apertis_scan_gate_fwd", lambda *a: rc.append(lib.apertis_scan_lean_fwd(*a)) or (0 if rc[-1] == -2 else rc[-1]),
+            _launch("apertis_scan_gate_fwd", lambda *a: rc.append(lib.apertis_scan_lean_fwd(*a)) or (0 if rc[-1] == _lib.ERR_UNSUPPORTED else rc[-1]),
                     (ptr(dlt),) + tail, work)
-            lean = rc[-1] == 0                   # (-2 = APERTIS_ERR_UNSUPPORTED: alignment / size - the staged kernels below)
+            lean = rc[-1] == 0                   # (APERTIS_ERR_UNSUPPORTED: alignment / size - the staged kernels below)
     if not dt_done:
         _tiny_linear_into(lib, dtp, dlt)
     if not lean:
@@ -448,7 +448,7 @@ def _scan_gate_backward(ctx, dout):
         agg = torch.empty(B, nch, Dn, 2, device=dev, dtype=torch.float32)
         mu_in = torch.empty(B, nch, Dn, device=dev, dtype=torch.float32)
         rc = []
-        _launch("apertis_scan_gate_bwd", lambda *a: rc.append(lib.apertis_scan_lean_bwd(*a)) or (0 if rc[-1] == -2 else rc[-1]),
+        _launch("apertis_scan_gate_bwd", lambda *a: rc.append(lib.apertis_scan_lean_bwd(*a)) or (0 if rc[-1] == _lib.ERR_UNSUPPORTED else rc[-1]),
                 (ptr(dlt), ptr(A_log), ptr(Bt), Bt.stride(-2), ptr(C), C.stride(-2), ptr(xc), xc.stride(-2), ptr(z), z.stride(-2),
                  ptr(Df), ptr(dout), do_rs, ptr(ckpt), ptr(dBt), dbt_rs, ptr(dC), dc_rs, wB, ptr(dxc), dxc_rs, ptr(dz), dz_rs,
                  ptr(d_dlt), ptr(dA_dD), ptr(agg), ptr(mu_in), ptr(fold), ptr(part), B, L, h, N, int(sp), stream_ptr()), work)

@@ -138,7 +138,7 @@ class _DwConvSilu(torch.autograd.Function):
         ins = (ptr(x), x.stride(-2), ptr(w2), ptr(b2), ptr(dout), Dn, ptr(dout2), Dn)
         outs = (ptr(dx), dx_rs, ptr(dw_part), ptr(db_part), ptr(dw), ptr(db), B, L, Dn, k, dtype_code(x), stream_ptr())
         if not bounds:
-            check(lib.apertis_dwconv_silu_bwd2(*ins, *outs), "apertis_dwconv_silu_bwd")
+            check(lib.apertis_dwconv_silu_bwd2(*ins, *outs), "apertis_dwconv_silu_bwd2")
         else:
             check(lib.apertis_dwconv_silu_doc_bwd(*ins, ptr(bounds[0]), ptr(bounds[1]), *outs), "apertis_dwconv_silu_doc_bwd")
         return dx, dw.reshape(ctx.wshape), db, None, None

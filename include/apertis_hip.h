@@ -52,7 +52,10 @@ extern "C" {
  * apertis_sample_next: generate()'s penalty / temperature / top-k / top-p / draw in one launch; 4.8 - apertis_rope_qk_fwd / _bwd,
  * apertis_attention_fwd / _bwd, apertis_attention_bwd_workspace_bytes: standard_mha; round 6: 4.7 - apertis_cross_entropy_fwd_bwd, apertis_layernorm_combine_bwd; round 5: 4.5 - apertis_scan_lookback_*, apertis_tiny_linear_bwd_pad; round 4: 4.4 - lean scan
  * entry points, apertis_scan_lean_fwd_dt, apertis_grouped_gemm_tn_dense_variant, apertis_weight_prep, apertis_ssm_decode_state_dt).  A host binding should
- * refuse a library whose version differs from the header it was written against (apertis_llm_amd/_lib.py does).
+ * refuse a library whose version differs from the header it was written against.  apertis_llm_amd/_lib.py does, and it is
+ * written against THIS FILE literally: it reads the declarations and the integer #defines below at import and builds its
+ * ctypes signatures and constants from them, so a declaration here is the binding (keep to the parameter types already used:
+ * int, int64_t, uint32_t, uint64_t, float, double, pointers; every parameter named).
  * The RMSNorm entry points (apertis_rmsnorm_fwd / _bwd / _bwd_blocks, apertis_dropout_add_rmsnorm_fwd) were ADDED UNDER 4.12
  * without a bump: the test suite pins the version at 4.12 and no existing signature changed, so a binding written against the
  * earlier 4.12 header still calls every entry point it knows correctly; one that wants the RMSNorm family looks the symbols up.

@@ -1,6 +1,6 @@
 /* libapertis_hip.so: entry points added after the 4.12 table.
  *
- * Why a second header: apertis_hip.h and the binding table that mirrors it are the 4.12 ABI, and they are frozen - 123 entry
+ * Why a second header: apertis_hip.h is the 4.12 ABI (the Python binding reads its table from it), and it is frozen - 123 entry
  * points, checked name by name against the library, with APERTIS_ABI_VERSION saying which table a build carries.  An entry point
  * that arrives without an ABI bump goes HERE: the same library exports it, every rule of apertis_hip.h holds for it (return
  * codes, dtype codes, `stream`, validation before any launch, no hidden synchronisation), and APERTIS_ABI_VERSION stays 4.12.

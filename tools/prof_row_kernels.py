@@ -1,7 +1,7 @@
 """Target of `rocprofv3 --kernel-trace --stats`: the ROW kernels of one MoE layer boundary pair at the bench's full per-GPU size
 (T = 44 x 4096 tokens, H = 704, 8 experts top-2 with the training capacity) called one by one on valid synthetic inputs - each
-op's outputs are consumed by nothing else, so a probe build of the library whose row kernels compile their data stores out
-(-DROW_PROBE_NOSTORE) can be timed next to the real one.    python tools/prof_row_kernels.py [reps] [batch]"""
+op's outputs are consumed by nothing else, so the per-kernel statistics are those of each row kernel alone.
+    python tools/prof_row_kernels.py [reps] [batch]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
