@@ -50,34 +50,27 @@ __device__ __forceinline__ void ce_merge(float &m, float &s, float m2, float s2)
   m = mn;
 }
 
-// target of logits row (b, l) is labels[b, l + 1]; rows l >= n_pos carry no loss
-template <typename T>
-__global__ void __launch_bounds__(CE_NT)
-ce_fwd_k(const T *__restrict__ logits, const int64_t *__restrict__ labels, float *__restrict__ lse,
-         float *__restrict__ row_loss, int L, int V, int label_stride, int n_pos, int64_t ignore_index) {
+// what a chunk's exponents are taken against: its maximum cm, or 0 for a chunk of -inf only (masked logits), whose
+// -inf - (-inf) would be NaN - it then contributes (-inf, 0), which ce_merge folds into a finite pair as nothing
+__device__ __forceinline__ float ce_chunk_base(float cm) { return cm == -INFINITY ? 0.f : cm; }
+
+// one 16-byte chunk of a row into a thread's running (m, s)
+template <typename T> __device__ __forceinline__ void ce_add_chunk(const uint4 &raw, float &m, float &s) {
   constexpr int VN = ce_vec<T>::N;
-  const int64_t row = blockIdx.x;
-  const int b = (int)(row / L), l = (int)(row - (int64_t)b * L);
-  int64_t target = ignore_index;
-  if (l < n_pos) target = labels[(int64_t)b * label_stride + l + 1];
-  if (target == ignore_index || target < 0 || target >= V) {   // uniform per work-group
-    if (threadIdx.x == 0) { lse[row] = 0.f; row_loss[row] = 0.f; }
-    return;
-  }
-  const T *x = logits + row * (int64_t)V;
-  float m = -INFINITY, s = 0.f;
-  for (int c = threadIdx.x; c < V / VN; c += CE_NT) {
-    float v[VN];
-    ce_unpack<T>(*reinterpret_cast<const uint4 *>(x + (int64_t)c * VN), v);
-    float cm = v[0];
+  float v[VN];
+  ce_unpack<T>(raw, v);
+  float cm = v[0];
 #pragma unroll
-    for (int i = 1; i < VN; ++i) cm = fmaxf(cm, v[i]);
-    float cs = 0.f;
+  for (int i = 1; i < VN; ++i) cm = fmaxf(cm, v[i]);
+  const float cb = ce_chunk_base(cm);
+  float cs = 0.f;
 #pragma unroll
-    for (int i = 0; i < VN; ++i) cs += __builtin_amdgcn_exp2f((v[i] - cm) * LOG2E_F);
-    ce_merge(m, s, cm, cs);
-  }
-  // wave, then work-group, in a fixed order
+  for (int i = 0; i < VN; ++i) cs += __builtin_amdgcn_exp2f((v[i] - cb) * LOG2E_F);
+  ce_merge(m, s, cm, cs);
+}
+
+// the threads' (m, s) into the row's, left in thread 0: wave, then work-group, in a fixed order (one barrier)
+__device__ __forceinline__ void ce_block_merge(float &m, float &s) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float m2 = __shfl_xor(m, off), s2 = __shfl_xor(s, off);
@@ -87,19 +80,69 @@ ce_fwd_k(const T *__restrict__ logits, const int64_t *__restrict__ labels, float
   if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = m; ss[threadIdx.x >> 6] = s; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
-    for (int w = 1; w < CE_NT / 64; ++w) ce_merge(M, S, sm[w], ss[w]);
-    const float r = M + logf(S);
-    lse[row] = r;
-    row_loss[row] = r - to_f32(x[target]);
+    m = sm[0], s = ss[0];
+    for (int w = 1; w < CE_NT / 64; ++w) ce_merge(m, s, sm[w], ss[w]);
   }
 }
 
-// dlogits[row] = (softmax(row) - onehot(target)) * gscale for rows with a target, 0 for the others
+// (M, S) of a row in thread 0, thread t walking chunks t, t + 256, ... in order: ce_fwd_k's sweep, which ce_bwd_k repeats
+// for a row in the pair regime (below) and gets the same bits
+template <typename T> __device__ __forceinline__ void ce_row_max_sum(const T *x, int V, float &m, float &s) {
+  constexpr int VN = ce_vec<T>::N;
+  m = -INFINITY, s = 0.f;
+  for (int c = threadIdx.x; c < V / VN; c += CE_NT) ce_add_chunk<T>(*reinterpret_cast<const uint4 *>(x + (int64_t)c * VN), m, s);
+  ce_block_merge(m, s);
+}
+
+// lse = M + log S as ONE fp32 is spaced 2^-20 or finer while |lse| < 16: row loss lse - x[t] and softmax exp(x - lse) are then
+// taken from it, as they always were.  From 16 on its spacing (9.8e-4 next to 1e4) would be the error of the loss and the
+// relative error of every softmax value, so the row is in the PAIR regime: loss (M - x[t]) + log S, softmax
+// exp((x - M) - log S) - differences of logits are exact or nearly so, and log S is small.  The backward kernel of such a
+// row sums it again: a second read of the row by the work-group that is about to read it anyway, whose cost has not been
+// measured (no training step of bench.py has a row in this regime); lse[row] itself is the same number in both.
+constexpr float CE_PAIR_FROM = 16.f;
+__device__ __forceinline__ bool ce_pair(float r) { return !(fabsf(r) < CE_PAIR_FROM); }
+
+// thread 0, from the row's (M, S): lse[row] and row_loss[row]; (base, sub) such that softmax = exp((x - base) - sub)
+template <typename T>
+__device__ __forceinline__ void ce_row_finish(float M, float S, const T *x, int64_t target, float *lse_row, float *loss_row,
+                                              float &base, float &sub) {
+  const float ls = logf(S), r = M + ls, xt = to_f32(x[target]);
+  const bool pair = ce_pair(r);
+  *lse_row = r;
+  *loss_row = pair ? (M - xt) + ls : r - xt;
+  base = pair ? M : r;
+  sub = pair ? ls : 0.f;
+}
+
+// target of logits row (b, l) is labels[b, l + 1]; rows l >= n_pos carry no loss
 template <typename T>
 __global__ void __launch_bounds__(CE_NT)
-ce_bwd_k(const T *__restrict__ logits, const int64_t *__restrict__ labels, const float *__restrict__ lse,
-         const float *__restrict__ gscale, T *__restrict__ dlogits, int L, int V, int label_stride, int n_pos,
+ce_fwd_k(const T *__restrict__ logits, const int64_t *__restrict__ labels, float *__restrict__ lse,
+         float *__restrict__ row_loss, int L, int V, int label_stride, int n_pos, int64_t ignore_index) {
+  const int64_t row = blockIdx.x;
+  const int b = (int)(row / L), l = (int)(row - (int64_t)b * L);
+  int64_t target = ignore_index;
+  if (l < n_pos) target = labels[(int64_t)b * label_stride + l + 1];
+  if (target == ignore_index || target < 0 || target >= V) {   // uniform per work-group
+    if (threadIdx.x == 0) { lse[row] = 0.f; row_loss[row] = 0.f; }
+    return;
+  }
+  const T *x = logits + row * (int64_t)V;
+  float m, s;
+  ce_row_max_sum<T>(x, V, m, s);
+  if (threadIdx.x == 0) {
+    float base, sub;
+    ce_row_finish<T>(m, s, x, target, lse + row, row_loss + row, base, sub);
+  }
+}
+
+// dlogits[row] = (softmax(row) - onehot(target)) * gscale for rows with a target, 0 for the others; dlogits may alias logits
+// (ops.linear_cross_entropy runs it in place on a chunk's logits), so neither carries __restrict__
+template <typename T>
+__global__ void __launch_bounds__(CE_NT)
+ce_bwd_k(const T *logits, const int64_t *__restrict__ labels, const float *__restrict__ lse,
+         const float *__restrict__ gscale, T *dlogits, int L, int V, int label_stride, int n_pos,
          int64_t ignore_index) {
   constexpr int VN = ce_vec<T>::N;
   const int64_t row = blockIdx.x;
@@ -113,14 +156,23 @@ ce_bwd_k(const T *__restrict__ logits, const int64_t *__restrict__ labels, const
     for (int c = threadIdx.x; c < V / VN; c += CE_NT) *reinterpret_cast<uint4 *>(dx + (int64_t)c * VN) = make_uint4(0, 0, 0, 0);
     return;
   }
-  const float g = gscale[0], r = lse[row];
+  const float g = gscale[0];
+  float base = lse[row], sub = 0.f;
+  if (ce_pair(base)) {   // uniform per work-group: the row's (M, log S) again, before any thread overwrites the row
+    __shared__ float sp[2];
+    float m, s;
+    ce_row_max_sum<T>(x, V, m, s);
+    if (threadIdx.x == 0) { sp[0] = m; sp[1] = logf(s); }
+    __syncthreads();
+    base = sp[0], sub = sp[1];
+  }
   const int tc = (int)(target / VN), ti = (int)(target - (int64_t)tc * VN);
   for (int c = threadIdx.x; c < V / VN; c += CE_NT) {
     float v[VN];
     ce_unpack<T>(*reinterpret_cast<const uint4 *>(x + (int64_t)c * VN), v);
 #pragma unroll
     for (int i = 0; i < VN; ++i) {
-      float p = __builtin_amdgcn_exp2f((v[i] - r) * LOG2E_F);
+      float p = __builtin_amdgcn_exp2f(((v[i] - base) - sub) * LOG2E_F);
       if (c == tc && i == ti) p -= 1.f;
       v[i] = p * g;
     }
@@ -160,35 +212,15 @@ ce_fwd_bwd_k(const T *logits, const int64_t *__restrict__ labels, float *__restr
     const int c = (int)threadIdx.x + k * CE_NT;
     if (c < nch) {
       keep[k] = *reinterpret_cast<const uint4 *>(x + (int64_t)c * VN);
-      float v[VN];
-      ce_unpack<T>(keep[k], v);
-      float cm = v[0];
-#pragma unroll
-      for (int i = 1; i < VN; ++i) cm = fmaxf(cm, v[i]);
-      float cs = 0.f;
-#pragma unroll
-      for (int i = 0; i < VN; ++i) cs += __builtin_amdgcn_exp2f((v[i] - cm) * LOG2E_F);
-      ce_merge(m, s, cm, cs);
+      ce_add_chunk<T>(keep[k], m, s);
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float m2 = __shfl_xor(m, off), s2 = __shfl_xor(s, off);
-    ce_merge(m, s, m2, s2);
-  }
-  __shared__ float sm[CE_NT / 64], ss[CE_NT / 64], sr;
-  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = m; ss[threadIdx.x >> 6] = s; }
+  ce_block_merge(m, s);
+  __shared__ float sp[2];
+  if (threadIdx.x == 0)   // (x[target] is read before any thread overwrites the row: the barrier below)
+    ce_row_finish<T>(m, s, x, target, lse + row, row_loss + row, sp[0], sp[1]);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
-    for (int w = 1; w < CE_NT / 64; ++w) ce_merge(M, S, sm[w], ss[w]);
-    const float r0 = M + logf(S);
-    lse[row] = r0;
-    row_loss[row] = r0 - to_f32(x[target]);   // (read before any thread overwrites the row: the barrier below)
-    sr = r0;
-  }
-  __syncthreads();
-  const float g = gscale[0], r = sr;
+  const float g = gscale[0], base = sp[0], sub = sp[1];
   const int tc = (int)(target / VN), ti = (int)(target - (int64_t)tc * VN);
 #pragma unroll
   for (int k = 0; k < CE_KEEP; ++k) {
@@ -198,7 +230,7 @@ ce_fwd_bwd_k(const T *logits, const int64_t *__restrict__ labels, float *__restr
       ce_unpack<T>(keep[k], v);
 #pragma unroll
       for (int i = 0; i < VN; ++i) {
-        float p = __builtin_amdgcn_exp2f((v[i] - r) * LOG2E_F);
+        float p = __builtin_amdgcn_exp2f(((v[i] - base) - sub) * LOG2E_F);
         if (c == tc && i == ti) p -= 1.f;
         v[i] = p * g;
       }
