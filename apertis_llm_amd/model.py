@@ -294,6 +294,10 @@ DECODE_GRAPH = os.environ.get("APERTIS_DECODE_GRAPH", "1") == "1"
 DECODE_GRAPH_MIN_STEPS = 24
 # APERTIS_DECODE_PREPASS=0: every layer runs its whole single-token SSM step itself (conv, x_param_proj, state update inside the layer loop)
 DECODE_PREPASS = os.environ.get("APERTIS_DECODE_PREPASS", "1") == "1"
+# generate_many(): rows of the decode batch at most (the bound of ops.decode_dense_gemv and ops.moe_enter_small), and replayed
+# token steps between two host reads at most (the cadence of generate()'s graph tail)
+GENERATE_MANY_MAX_SLOTS = 16
+GENERATE_MANY_BURST = 16
 
 
 def _mfma_linear(x, weight, bias=None):
@@ -2036,16 +2040,8 @@ class ApertisForCausalLM(nn.Module):
         """Warm-up, capture and replay of `body` for `left` steps.  `state`: the tensors the body updates in place (token, alive
         flags, caches, the sampler's occurrence table and error word, a KVCache's step state); `outputs`: the step counter,
         the tokens and the per-step alive maximum, which start from zero / pad / one."""
-        dev = tokens.device
         s_idx, s_out, s_any = outputs
-        # warm-up on a side stream (lazy bindings, prepared-weight cache, allocator), then restore the state it advanced
         keep = [t.clone() for t in state]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(side)
 
         def restore():
             for t, k in zip(state, keep):
@@ -2054,11 +2050,7 @@ class ApertisForCausalLM(nn.Module):
             s_out.fill_(pad)
             s_any.fill_(1)
 
-        restore()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):    # (another thread's GPU work - a trainer thread beside chat - must not fail on this capture)
-            body()
-        restore()
+        graph = self._capture_step(body, restore, tokens.device)
         done = left
         for i in range(left):
             graph.replay()
@@ -2078,6 +2070,244 @@ class ApertisForCausalLM(nn.Module):
                     done = stop + 1
                     break
         return torch.cat([tokens, s_out[:, :done]], dim=-1)
+
+    @staticmethod
+    def _capture_step(body, restore, dev):
+        """`body` as a captured graph: warm-up on a side stream (lazy bindings, prepared-weight cache, allocator), `restore()`
+        of the state it advanced, the capture, `restore()` again."""
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                body()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        restore()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):    # (another thread's GPU work - a trainer thread beside chat - must not fail on this capture)
+            body()
+        restore()
+        return graph
+
+    @torch.no_grad()
+    def generate_many(self, prompts, max_new_tokens=20, slots: int = 16, do_sample: bool = False, temperature: float = 1.0,
+                      top_k: int = 50, top_p: float = 1.0, repetition_penalty: float = 1.0, eos_token_id=None,
+                      pad_token_id=None, return_stats: bool = False, pixel_values=None):
+        """generate() for many prompts of a selective_ssm model on ONE decode batch of `slots` rows whose finished rows are
+        refilled: a prompt is prefilled alone (the call generate() makes for it), its conv windows and SSM states are copied
+        into a free row of the static decode state, and the token step - the graph-replayed one where generate() would
+        replay - runs over all rows until nothing waits and no row is live.  No padding is computed, prompts need not be
+        equally long, and a row that ends early makes room for the next prompt.
+
+        prompts: 1-D int64 tensors on the model's GPU, or lists of ids, of any lengths >= 1; max_new_tokens: one integer or
+        one per prompt; slots: 1...16 (the row bound of the small-step kernels).  Returns a list of 1-D int64 tensors in the
+        order of `prompts`: the prompt and its new tokens, up to and with its first eos or `max_new_tokens` of them, never
+        padded - what generate(prompts[i][None], max_new_tokens=m_i, ...) returns for it alone, cut after the first eos.
+        Greedy decoding (with or without a repetition penalty) is token-equal to those alone runs.  With do_sample=True every
+        row is drawn from the distribution it would be drawn from alone, but with the draw counter of this call's one
+        ops.Sampler - (seed, slot row, step of the call) - so a sampled run is NOT token-equal to the alone run under the
+        same torch seed.  There is no min_new_tokens (in generate() it is a condition on the batch, not a per-row rule).
+
+        A prompt shorter than ssm_conv_kernel - 1 tokens has no full conv window to install: it runs through generate()
+        alone when its turn comes.  standard_mha models, absolute position embeddings, pixel_values, output_attentions,
+        training mode and CPU tensors raise ValueError before any GPU work.
+
+        return_stats=True: (outputs, stats) with stats = {"steps": token steps run, "replays": of them graph replays,
+        "graphs": graphs captured, "prefills": batch-1 prefills into slots, "live_slot_steps": sum over steps of the rows
+        whose token was kept, "slot_steps": steps * slots, "fallbacks": indices of the prompts that ran through
+        generate()}."""
+        cfg = self.config
+        if cfg.attention_type == "standard_mha":
+            raise ValueError("generate_many(): slots serve selective_ssm models; a standard_mha model batches through "
+                             "generate(past_key_values=...) with a KVCache, or one left-padded generate() batch")
+        if cfg.position_embedding_type == "absolute":
+            raise ValueError("generate_many(): absolute position embeddings (a slot's position would differ per row)")
+        if pixel_values is not None:
+            raise ValueError("generate_many(): pixel_values (an image prefix is not part of a slot's state)")
+        if self.training:
+            raise ValueError("generate_many(): the model is in training mode (call .eval())")
+        if cfg.output_attentions:
+            raise ValueError("generate_many(): output_attentions")
+        if cfg.ssm_conv_kernel < 2:
+            raise ValueError("generate_many(): ssm_conv_kernel < 2 (the single-token step needs a conv window)")
+        if not 1 <= slots <= GENERATE_MANY_MAX_SLOTS:
+            raise ValueError(f"generate_many(): slots = {slots}, the small-step kernels take 1...{GENERATE_MANY_MAX_SLOTS} rows")
+        prompts = list(prompts)
+        budgets = [max_new_tokens] * len(prompts) if isinstance(max_new_tokens, int) else [int(m) for m in max_new_tokens]
+        if len(budgets) != len(prompts):
+            raise ValueError(f"generate_many(): {len(budgets)} max_new_tokens for {len(prompts)} prompts")
+        dev = self.lm_head.weight.device
+        if dev.type != "cuda":
+            raise ValueError("generate_many(): the model is not on a GPU (there is no CPU path)")
+        for i, p in enumerate(prompts):
+            if isinstance(p, torch.Tensor) and (not p.is_cuda or p.dim() != 1 or p.dtype != torch.int64):
+                raise ValueError(f"generate_many(): prompt {i} is a {p.dtype} tensor of shape {tuple(p.shape)} on {p.device}, "
+                                 "expected 1-D int64 on the model's GPU")
+            if len(p) == 0:
+                raise ValueError(f"generate_many(): prompt {i} is empty")
+        ids = [p if isinstance(p, torch.Tensor) else torch.tensor(list(p), dtype=torch.int64, device=dev) for p in prompts]
+        with ops.prep_cache_scope(), ops.device_guard(self.lm_head.weight):
+            outs, stats = self._generate_many(ids, budgets, slots, do_sample, temperature, top_k, top_p, repetition_penalty,
+                                              eos_token_id, pad_token_id)
+        return (outs, stats) if return_stats else outs
+
+    def _slot_state(self, past, S):
+        """Zeroed decode state for S rows, shaped after one prefill's per-layer (conv window [1, Dn, k-1], state [1, h, N]): the
+        stacked form the graph tail builds (_StackedPast: the cache-only half of a step runs for all layers at once) under
+        its condition, else one pair of buffers per layer.  Returns (state, the tensors a step updates in place)."""
+        c0, st0 = past[0]
+        if (DECODE_PREPASS and all(c.dim() == 3 and st.dim() == 3 and st.dtype == torch.float32 and c.shape == c0.shape
+                                   and st.shape == st0.shape and c.dtype == c0.dtype for c, st in past)):
+            conv_all = torch.zeros((len(past), S) + tuple(c0.shape[1:]), dtype=c0.dtype, device=c0.device)
+            state_all = torch.zeros(len(past), S, st0.shape[1] * st0.shape[2], dtype=torch.float32, device=c0.device)
+            return _StackedPast(conv_all, state_all, st0.shape[1], st0.shape[2], inplace=True), [conv_all, state_all]
+        state = [_SsmLayerPast(torch.zeros((S,) + tuple(c.shape[1:]), dtype=c.dtype, device=c.device),
+                               torch.zeros((S,) + tuple(st.shape[1:]), dtype=st.dtype, device=st.device), inplace=True)
+                 for c, st in past]
+        return state, [t for pair in state for t in pair]
+
+    def _generate_many(self, ids, budgets, S, do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id,
+                       pad_token_id):
+        from .serving import SlotSchedule
+        cfg, dev = self.config, self.lm_head.weight.device
+        eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
+        eos = [] if eos is None else (eos if isinstance(eos, list) else [eos])
+        eos_set = frozenset(int(e) for e in eos if e is not None)
+        pad = pad_token_id if pad_token_id is not None else cfg.pad_token_id
+        pad = 0 if pad is None else pad
+        window = cfg.ssm_conv_kernel - 1
+        sched = SlotSchedule(len(ids), budgets, S)
+        stats = {"steps": 0, "replays": 0, "graphs": 0, "prefills": 0, "live_slot_steps": 0, "slot_steps": 0, "fallbacks": []}
+        s_tok = torch.full((S, 1), pad, dtype=torch.long, device=dev)
+        s_alive = torch.zeros(S, dtype=torch.long, device=dev)
+        s_idx = torch.zeros(1, dtype=torch.long, device=dev)            # column of s_out: zeroed before every burst
+        s_step = torch.zeros(1, dtype=torch.long, device=dev)           # steps of the whole call: the sampler's draw counter
+        burst = max(int(GENERATE_MANY_BURST), 1)
+        s_out = torch.full((S, max(burst, 2)), pad, dtype=torch.long, device=dev)      # (the capture's warm-up runs two steps)
+        s_nxt = torch.empty(S, dtype=torch.long, device=dev)
+        s_one = torch.ones(1, dtype=torch.long, device=dev)             # an install's one-row alive flag, and where its
+        s_end = torch.empty(1, dtype=torch.long, device=dev)            # kernel puts the flag after the token (the host decides)
+        want_sampler = do_sample or repetition_penalty != 1.0
+        sampler = state = graph = None
+        in_place = [s_tok, s_alive, s_idx, s_step, s_out]               # what a step writes: restored around the capture
+
+        def install(i, b):
+            """Prompt i's prefill and first token (a host integer); its caches go into row b if the slot then is live."""
+            nonlocal sampler, state
+            prompt = ids[i]
+            out = self(input_ids=prompt[None], use_cache=True)
+            stats["prefills"] += 1
+            logits, past = out[1][:, -1, :], out[4]
+            if state is None:
+                state, bufs = self._slot_state(past, S)
+                in_place.extend(bufs)
+            if want_sampler and sampler is None:
+                if not (ops.SAMPLE_FUSED and ops.sample_supported(logits)):
+                    raise ops.ApertisHipError("generate_many(): sampling and the repetition penalty run on the fused sampler "
+                                              f"(ops.SAMPLE_FUSED, logits {tuple(logits.shape)} {logits.dtype}); there is no "
+                                              "stock path over slots")
+                # (ids >= V are skipped by the occurrence table: it starts at zero, a row is rebuilt when a prompt moves in)
+                none = torch.full((S, 1), logits.shape[-1], dtype=torch.long, device=dev)
+                sampler = ops.Sampler(logits.expand(S, -1), none, do_sample=do_sample, temperature=temperature, top_k=top_k,
+                                      top_p=top_p, repetition_penalty=repetition_penalty, eos=eos, pad=pad)
+                if sampler.uniforms is not None:
+                    raise ops.ApertisHipError("generate_many(): ops.sample.SAMPLE_UNIFORMS is generate()'s test hook")
+                in_place.extend(t for t in (sampler.counts, sampler.err) if t is not None)
+            if sampler is None:
+                nxt, _ = _select_tokens(logits.float(), s_one, eos, pad)
+                first = int(nxt)
+            else:
+                counts = None
+                if sampler.counts is not None:
+                    sampler.counts[b].copy_(ops.token_counts(prompt[None], logits.shape[-1], sampler.err)[0])
+                    counts = sampler.counts[b:b + 1]
+                # (the kernel sees row 0 here: the draw counters of the installs lie above every step of the call)
+                nxt = ops.sample_next(logits, s_one, sampler.err, do_sample=sampler.do_sample, temperature=sampler.temp,
+                                      top_k=sampler.top_k, top_p=sampler.top_p, repetition_penalty=sampler.penalty,
+                                      counts=counts, eos=sampler.eos, pad=sampler.pad, seed=sampler.seed,
+                                      step=sampler.zero_step, step_off=(1 << 40) + stats["prefills"],
+                                      alive_out=s_end, out=s_nxt[b:b + 1])
+                first, code = torch.cat((nxt, sampler.err.to(nxt.dtype))).tolist()
+                sampler.check(code)
+            if sched.place(b, first, eos_set):
+                moved.append(b)
+                s_tok[b].copy_(nxt)
+                if isinstance(state, _StackedPast):
+                    state.conv_all[:, b].copy_(torch.stack([c[0] for c, _ in past]))
+                    state.state_all[:, b].copy_(torch.stack([st[0].reshape(-1) for _, st in past]))
+                else:
+                    for (sc, ss), (c, st) in zip(state, past):
+                        sc[b].copy_(c[0])
+                        ss[b].copy_(st[0])
+
+        def body():
+            out = self(input_ids=s_tok, past_key_values=state, use_cache=True)
+            if sampler is None:
+                nxt, al = _select_tokens(out[1][:, -1, :].float(), s_alive, eos, pad)
+                s_alive.copy_(al)
+            else:
+                sampler.step(out[1][:, -1, :], s_alive, 0, step=s_step, alive_out=s_alive, out=s_nxt)
+                nxt = s_nxt
+            s_out.scatter_(1, s_idx.expand(S, 1), nxt.unsqueeze(1))
+            s_idx.add_(1)
+            s_step.add_(1)
+            s_tok.copy_(nxt.unsqueeze(1))
+            for (sc, ss), (nc, ns) in zip(state, out[4]):
+                if nc.data_ptr() != sc.data_ptr():         # (both updated in place by the step: the views say `inplace`)
+                    sc.copy_(nc)
+                if ns.data_ptr() != ss.data_ptr():
+                    ss.copy_(ns)
+
+        slotted = [m for p, m in zip(ids, budgets) if len(p) >= window]
+        want_graph = DECODE_GRAPH and bool(slotted) and max(slotted) - 1 >= DECODE_GRAPH_MIN_STEPS
+        moved = [None]                 # slots filled or freed since s_alive was last written (None: not written yet)
+        while not sched.finished():
+            # every free slot takes the next prompts in arrival order until one stays (or none waits)
+            for b in sched.free():
+                while sched.head() is not None and sched.slot[b] is None:
+                    i = sched.head()
+                    if len(ids[i]) < window:
+                        # (its prefill hands back a shorter window, which no token step takes in place: generate()'s own loop)
+                        alone = self.generate(input_ids=ids[i][None], max_new_tokens=budgets[i], do_sample=do_sample,
+                                              temperature=temperature, top_k=top_k, top_p=top_p,
+                                              repetition_penalty=repetition_penalty, eos_token_id=eos_token_id,
+                                              pad_token_id=pad_token_id)
+                        sched.complete(alone[0, len(ids[i]):].tolist(), eos_set)
+                        stats["fallbacks"].append(i)
+                    else:
+                        install(i, b)
+            live = sched.live()
+            if not live:
+                continue
+            if moved:
+                # (a row that ran out of budget is still alive on the device, one refilled after its eos is not)
+                s_alive.copy_(torch.tensor([int(b in live) for b in range(S)], dtype=torch.long))
+                del moved[:]
+            if want_graph and graph is None and self._decode_graph_ok(s_tok, do_sample, repetition_penalty, sampler):
+                keep = [t.clone() for t in in_place]
+                graph = self._capture_step(body, lambda: [t.copy_(k) for t, k in zip(in_place, keep)], dev)
+                stats["graphs"] += 1
+            n = sched.burst(burst if graph is not None else 1)
+            s_idx.zero_()
+            for _ in range(n):
+                if graph is not None:
+                    graph.replay()
+                else:
+                    body()
+            stats["steps"] += n
+            stats["replays"] += n if graph is not None else 0
+            stats["slot_steps"] += n * S
+            # the one host read of the burst: its tokens, with the sampler's error word
+            if sampler is None:
+                got = s_out[:, :n].tolist()
+            else:
+                *flat, code = torch.cat((s_out[:, :n].reshape(-1), sampler.err.to(s_out.dtype))).tolist()
+                sampler.check(code)
+                got = [flat[b * n:(b + 1) * n] for b in range(S)]
+            moved.extend(sched.feed(got, eos_set))
+        stats["live_slot_steps"] = sched.fed
+        new = torch.tensor([t for row in sched.tokens for t in row], dtype=torch.long, device=dev)
+        new = torch.split(new, [len(row) for row in sched.tokens])
+        return [torch.cat((p, t)) for p, t in zip(ids, new)], stats
 
 
 # ----------------------------------------------------------------------------------------------
