@@ -912,14 +912,16 @@ class ApertisAttention(nn.Module):
         A cache whose DEVICE step state is active (att_mask.step_cache; a captured graph replays such a step) brings length,
         position and key validity in device buffers: no host position, no host length, and the room in the cache and in the
         rotary table is the kernel's check (ops.kv_append_rope_at).  Its host lengths are stale, so a call the kernels do not
-        take cannot fall back on the views: it raises."""
-        step = isinstance(past_kv, ops.KVLayer) and past_kv.cache.step_active
+        take cannot fall back on the views: it raises.  A cache in SLOT mode (KVCache.slots_begin: a length per row) is the
+        same case: the state is on the device, the host lengths are stale."""
+        step = isinstance(past_kv, ops.KVLayer) and (past_kv.cache.step_active or past_kv.cache.slot_active)
         ok = (self._cache_step_ok(q, att_mask, past_kv, output_att, use_c) and q.shape[1] == 1
               and (att_mask.step_cache is past_kv.cache if step else att_mask.pos_host is not None))
         if step:
             if not ok:
-                raise ops.ApertisHipError("a KVCache whose device step state is active takes single-token inference steps on the "
-                                          "decode kernels only (its host lengths are stale): KVCache.step_state_end() first")
+                raise ops.ApertisHipError("a KVCache whose device step state is active, or one in slot mode, takes single-token "
+                                          "inference steps on the decode kernels only (its host lengths are stale): "
+                                          "KVCache.step_state_end() / slots_end() first")
             return True
         if not ok:
             return False
@@ -930,7 +932,10 @@ class ApertisAttention(nn.Module):
     def _decode_attention(self, q, k, v, att_mask, past_kv):
         cache, layer = past_kv.cache, past_kv.layer
         cos, sin = self._rope_tables()
-        if cache.step_active:
+        if cache.slot_active:                    # (a row and a position per sequence: generate_many()'s slots)
+            q = ops.kv_append_rope_slots(q, k, v, cache, layer, cos, sin)
+            ctxv = ops.attention_decode_slots(q, cache, layer, self.num_attention_heads)
+        elif cache.step_active:
             q = ops.kv_append_rope_at(q, k, v, cache, layer, cos, sin)
             ctxv = ops.attention_decode_at(q, cache, layer, self.num_attention_heads)
         else:
@@ -1430,10 +1435,10 @@ class ApertisModel(nn.Module):
         ssm = cfg.attention_type != "standard_mha"
         past_len = 0
         kv_cache = past_key_values if isinstance(past_key_values, ops.KVCache) else None
-        dev_step = kv_cache is not None and kv_cache.step_active
+        dev_step = kv_cache is not None and (kv_cache.step_active or kv_cache.slot_active)
         if dev_step and (Lq != 1 or position_ids is not None or attention_mask is not None):
-            raise ops.ApertisHipError("a KVCache whose device step state is active takes one token per step, with its own "
-                                      "positions and key validity (no position_ids, no attention_mask)")
+            raise ops.ApertisHipError("a KVCache whose device step state is active, or one in slot mode, takes one token per "
+                                      "step, with its own positions and key validity (no position_ids, no attention_mask)")
         if kv_cache is not None:
             past_len = kv_cache.length            # (stale under a device step state: nothing below may depend on it then)
         elif past_key_values is not None and past_key_values[0] is not None and not ssm:
@@ -1916,13 +1921,15 @@ class ApertisForCausalLM(nn.Module):
                 and isinstance(past[0], tuple) and len(past[0]) == 2 and past[0][0].dim() == 3
                 and ops.attention_decode_supported(past[0][0], cfg.num_attention_heads))
 
-    def _decode_graph_ok(self, tokens, do_sample, repetition_penalty, sampler=None, past=None, left=0, mask=None):
+    def _decode_graph_ok(self, tokens, do_sample, repetition_penalty, sampler=None, past=None, left=0, mask=None, slots=False):
+        """slots: generate_many()'s step over KV-cache slots - device-state by construction, so the standard_mha conditions of
+        generate()'s tail (_mha_graph_ok, ops.ATTN_DECODE_GRAPH) do not apply."""
         cfg = self.config
         # (sampling and the penalty replay too when the fused sampler selects the tokens: its kernel reads the step counter
         #  and the occurrence table from device buffers)
         ok = (DECODE_GRAPH and tokens.is_cuda and (sampler is not None or (not do_sample and repetition_penalty == 1.0))
               and not torch.is_grad_enabled() and cfg.position_embedding_type != "absolute" and not self.training)
-        if cfg.attention_type != "standard_mha":
+        if cfg.attention_type != "standard_mha" or slots:
             return ok
         return ok and self._mha_graph_ok(tokens, past, left, mask)
 
@@ -2111,14 +2118,24 @@ class ApertisForCausalLM(nn.Module):
         alone when its turn comes.  standard_mha models, absolute position embeddings, pixel_values, output_attentions,
         training mode and CPU tensors raise ValueError before any GPU work.
 
+        standard_mha under ops.ATTN_SLOTS (opt-in, APERTIS_MHA_SLOTS=1): the same call on KV-cache slots - one ops.KVCache of
+        `slots` rows in slot mode, a length per row.  A prompt of any length >= 1 is prefilled alone
+        and installed; there is no fallback, `stats["fallbacks"]` stays empty.  The step replays as a graph under
+        DECODE_GRAPH / DECODE_GRAPH_MIN_STEPS exactly like the SSM slots (ops.ATTN_DECODE_GRAPH is generate()'s switch and
+        is not consulted).  Refused on top of the list above, before any GPU work (_mha_slots_refusals): a head dim other
+        than 64 / 128 or a dtype other than fp32 / bf16, an active sliding window, ops.ATTN_FUSED or ops.ATTN_DECODE_FUSED
+        off, a prompt whose length + budget - 1 exceeds the rotary table.
+
         return_stats=True: (outputs, stats) with stats = {"steps": token steps run, "replays": of them graph replays,
         "graphs": graphs captured, "prefills": batch-1 prefills into slots, "live_slot_steps": sum over steps of the rows
         whose token was kept, "slot_steps": steps * slots, "fallbacks": indices of the prompts that ran through
         generate()}."""
         cfg = self.config
-        if cfg.attention_type == "standard_mha":
+        mha = cfg.attention_type == "standard_mha"
+        if mha and not ops.ATTN_SLOTS:
             raise ValueError("generate_many(): slots serve selective_ssm models; a standard_mha model batches through "
-                             "generate(past_key_values=...) with a KVCache, or one left-padded generate() batch")
+                             "generate(past_key_values=...) with a KVCache, or one left-padded generate() batch (KV-cache "
+                             "slots are opt-in: ops.ATTN_SLOTS / APERTIS_MHA_SLOTS=1)")
         if cfg.position_embedding_type == "absolute":
             raise ValueError("generate_many(): absolute position embeddings (a slot's position would differ per row)")
         if pixel_values is not None:
@@ -2127,7 +2144,7 @@ class ApertisForCausalLM(nn.Module):
             raise ValueError("generate_many(): the model is in training mode (call .eval())")
         if cfg.output_attentions:
             raise ValueError("generate_many(): output_attentions")
-        if cfg.ssm_conv_kernel < 2:
+        if not mha and cfg.ssm_conv_kernel < 2:
             raise ValueError("generate_many(): ssm_conv_kernel < 2 (the single-token step needs a conv window)")
         if not 1 <= slots <= GENERATE_MANY_MAX_SLOTS:
             raise ValueError(f"generate_many(): slots = {slots}, the small-step kernels take 1...{GENERATE_MANY_MAX_SLOTS} rows")
@@ -2144,11 +2161,43 @@ class ApertisForCausalLM(nn.Module):
                                  "expected 1-D int64 on the model's GPU")
             if len(p) == 0:
                 raise ValueError(f"generate_many(): prompt {i} is empty")
+        if mha:
+            self._mha_slots_refusals([len(p) for p in prompts], budgets)
         ids = [p if isinstance(p, torch.Tensor) else torch.tensor(list(p), dtype=torch.int64, device=dev) for p in prompts]
         with ops.prep_cache_scope(), ops.device_guard(self.lm_head.weight):
             outs, stats = self._generate_many(ids, budgets, slots, do_sample, temperature, top_k, top_p, repetition_penalty,
                                               eos_token_id, pad_token_id)
         return (outs, stats) if return_stats else outs
+
+    def _mha_slot_dtype(self):
+        """The dtype the projections produce, and with it a prefill's (k, v) and the slot cache (_mha_graph_ok's rule)."""
+        return (torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda")
+                else self.model.layers[0].attention.q_proj.weight.dtype)
+
+    def _mha_slots_refusals(self, lens, budgets):
+        """What generate_many() refuses of a standard_mha model under ops.ATTN_SLOTS beyond the common list, before any
+        forward (each a ValueError): a head dim or dtype the decode kernels do not take; an active sliding window (the window
+        form of the device-length attention measures its window from the ONE length it reads, which is wrong for every row
+        but the longest); ops.ATTN_FUSED or ops.ATTN_DECODE_FUSED off (there is no stock step over slots); a prompt whose
+        last step would be positioned beyond the rotary table (serving.mha_slot_overrun)."""
+        from .serving import mha_slot_overrun
+        cfg, attn = self.config, self.model.layers[0].attention
+        if attn.attention_head_size not in (64, 128) or cfg.hidden_size != attn.attention_head_size * attn.num_attention_heads:
+            raise ValueError(f"generate_many(): head dim {attn.attention_head_size} (the KV-cache decode kernels take 64 or 128)")
+        if self._mha_slot_dtype() not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"generate_many(): dtype {self._mha_slot_dtype()} (the KV-cache decode kernels take fp32 or bf16)")
+        if _active_window(cfg) is not None:
+            raise ValueError("generate_many(): sliding_window under ops.ATTN_WINDOW (a slot's window would be measured from "
+                             "the longest slot's length)")
+        if not (ops.ATTN_FUSED and ops.ATTN_DECODE_FUSED):
+            raise ValueError("generate_many(): KV-cache slots run on the decode kernels (ops.ATTN_FUSED and "
+                             "ops.ATTN_DECODE_FUSED); there is no stock step over slots")
+        if attn.rope is not None:
+            max_pos = attn.rope.cos_cached.shape[0]
+            i = mha_slot_overrun(lens, budgets, max_pos)
+            if i is not None:
+                raise ValueError(f"generate_many(): prompt {i} of {lens[i]} tokens with {budgets[i]} new ones runs past the "
+                                 f"rotary table ({max_pos} positions)")
 
     def _slot_state(self, past, S):
         """Zeroed decode state for S rows, shaped after one prefill's per-layer (conv window [1, Dn, k-1], state [1, h, N]): the
@@ -2167,14 +2216,21 @@ class ApertisForCausalLM(nn.Module):
 
     def _generate_many(self, ids, budgets, S, do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id,
                        pad_token_id):
-        from .serving import SlotSchedule
+        """generate_many()'s loop.  The slot state is the SSM layers' conv windows and states (_slot_state), or - standard_mha
+        under ops.ATTN_SLOTS - ONE ops.KVCache in slot mode with serving.mha_slot_capacity rows per slot, allocated once per
+        call: a prompt's batch-1 prefill is installed with KVCache.slot_install, a freed row is emptied with slot_free where
+        the alive flags are rewritten, the step body is bracketed by slots_step_begin / slots_step_end, and the cache's error
+        word rides in the burst's host read.  Everything else - the schedule, the burst rule, the sampler's handling, the
+        capture - is one code for both."""
+        from .serving import SlotSchedule, mha_slot_capacity
         cfg, dev = self.config, self.lm_head.weight.device
+        mha = cfg.attention_type == "standard_mha"
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
         eos = [] if eos is None else (eos if isinstance(eos, list) else [eos])
         eos_set = frozenset(int(e) for e in eos if e is not None)
         pad = pad_token_id if pad_token_id is not None else cfg.pad_token_id
         pad = 0 if pad is None else pad
-        window = cfg.ssm_conv_kernel - 1
+        window = 0 if mha else cfg.ssm_conv_kernel - 1        # (any prompt fits a KV-cache slot: no fallback there)
         sched = SlotSchedule(len(ids), budgets, S)
         stats = {"steps": 0, "replays": 0, "graphs": 0, "prefills": 0, "live_slot_steps": 0, "slot_steps": 0, "fallbacks": []}
         s_tok = torch.full((S, 1), pad, dtype=torch.long, device=dev)
@@ -2189,6 +2245,14 @@ class ApertisForCausalLM(nn.Module):
         want_sampler = do_sample or repetition_penalty != 1.0
         sampler = state = graph = None
         in_place = [s_tok, s_alive, s_idx, s_step, s_out]               # what a step writes: restored around the capture
+        cache = None
+        if mha:
+            # (no KV buffer is cloned around the capture, as in _generate_graph_tail: the warm-up writes rows at or beyond
+            #  each slot's length, and a replayed step rewrites a row before its validity column is set)
+            cap = mha_slot_capacity([len(p) for p in ids], budgets)
+            cache = state = ops.KVCache.empty(cfg.num_hidden_layers, S, cap, cfg.hidden_size, self._mha_slot_dtype(), dev)
+            cache.slots_begin(cfg.num_attention_heads, L_end=cap)
+            in_place.extend([cache.dev_lens, cache.dev_len, cache.dev_valid, cache.dev_err])
 
         def install(i, b):
             """Prompt i's prefill and first token (a host integer); its caches go into row b if the slot then is live."""
@@ -2231,7 +2295,9 @@ class ApertisForCausalLM(nn.Module):
             if sched.place(b, first, eos_set):
                 moved.append(b)
                 s_tok[b].copy_(nxt)
-                if isinstance(state, _StackedPast):
+                if cache is not None:
+                    cache.slot_install(b, past)
+                elif isinstance(state, _StackedPast):
                     state.conv_all[:, b].copy_(torch.stack([c[0] for c, _ in past]))
                     state.state_all[:, b].copy_(torch.stack([st[0].reshape(-1) for _, st in past]))
                 else:
@@ -2240,6 +2306,8 @@ class ApertisForCausalLM(nn.Module):
                         ss[b].copy_(st[0])
 
         def body():
+            if cache is not None:
+                cache.slots_step_begin()
             out = self(input_ids=s_tok, past_key_values=state, use_cache=True)
             if sampler is None:
                 nxt, al = _select_tokens(out[1][:, -1, :].float(), s_alive, eos, pad)
@@ -2251,6 +2319,12 @@ class ApertisForCausalLM(nn.Module):
             s_idx.add_(1)
             s_step.add_(1)
             s_tok.copy_(nxt.unsqueeze(1))
+            if cache is not None:
+                if out[4] is not cache:
+                    raise ops.ApertisHipError("generate_many(): a token step left the slot cache (the decode kernels did not "
+                                              "take it)")
+                cache.slots_step_end(s_alive)
+                return
             for (sc, ss), (nc, ns) in zip(state, out[4]):
                 if nc.data_ptr() != sc.data_ptr():         # (both updated in place by the step: the views say `inplace`)
                     sc.copy_(nc)
@@ -2281,8 +2355,14 @@ class ApertisForCausalLM(nn.Module):
             if moved:
                 # (a row that ran out of budget is still alive on the device, one refilled after its eos is not)
                 s_alive.copy_(torch.tensor([int(b in live) for b in range(S)], dtype=torch.long))
+                if cache is not None:
+                    for b in moved:
+                        if b is not None and b not in live:
+                            cache.slot_free(b)
                 del moved[:]
-            if want_graph and graph is None and self._decode_graph_ok(s_tok, do_sample, repetition_penalty, sampler):
+            # (the slot step of a standard_mha model is device-state by construction: generate()'s ops.ATTN_DECODE_GRAPH and
+            #  _mha_graph_ok are not consulted)
+            if want_graph and graph is None and self._decode_graph_ok(s_tok, do_sample, repetition_penalty, sampler, slots=mha):
                 keep = [t.clone() for t in in_place]
                 graph = self._capture_step(body, lambda: [t.copy_(k) for t, k in zip(in_place, keep)], dev)
                 stats["graphs"] += 1
@@ -2296,12 +2376,18 @@ class ApertisForCausalLM(nn.Module):
             stats["steps"] += n
             stats["replays"] += n if graph is not None else 0
             stats["slot_steps"] += n * S
-            # the one host read of the burst: its tokens, with the sampler's error word
-            if sampler is None:
+            # the one host read of the burst: its tokens, with the sampler's and the slot cache's error words
+            errs = [t for t in (sampler.err if sampler is not None else None, cache.dev_err if cache is not None else None)
+                    if t is not None]
+            if not errs:
                 got = s_out[:, :n].tolist()
             else:
-                *flat, code = torch.cat((s_out[:, :n].reshape(-1), sampler.err.to(s_out.dtype))).tolist()
-                sampler.check(code)
+                flat = torch.cat([s_out[:, :n].reshape(-1)] + [e.to(s_out.dtype) for e in errs]).tolist()
+                if cache is not None and flat.pop():
+                    raise ops.ApertisHipError("generate_many(): a KV-cache slot step ran past its slot or the rotary table; "
+                                              "nothing was written by that step")
+                if sampler is not None:
+                    sampler.check(flat.pop())
                 got = [flat[b * n:(b + 1) * n] for b in range(S)]
             moved.extend(sched.feed(got, eos_set))
         stats["live_slot_steps"] = sched.fed

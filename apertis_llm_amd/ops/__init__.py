@@ -38,7 +38,8 @@ _FORWARDED = {
     "TRAIN_PREP": prep, "WEIGHT_EPOCH": prep, "_ACTIVE_TRAIN_PREP": prep, "_prep_scope_depth": prep,
     "_TIMER": _base,
     "ATTN_FUSED": attention, "ATTN_DECODE_FUSED": attention, "ATTN_DECODE_GRAPH": attention,
-    "ATTN_LEFT_PAD": attention, "ATTN_WINDOW": attention, "ATTN_WINDOW_CACHE": attention, "VIT_FUSED": attention,
+    "ATTN_LEFT_PAD": attention, "ATTN_WINDOW": attention, "ATTN_WINDOW_CACHE": attention, "ATTN_SLOTS": attention,
+    "VIT_FUSED": attention,
     "SAMPLE_FUSED": sample, "SAMPLE_UNIFORMS": sample,
     "SWIGLU_FUSED": swiglu,
 }

@@ -6,7 +6,8 @@ bidirectional attention (full_attention, full_attention_qkv: the same kernels wi
 Sliding windows, opt-in (ATTN_WINDOW; window_attention, window_layout, attention_decode(window=): the causal kernels with
 bounds computed from the query index, packed rows on a clipped layout, a decode step that reads the last W cache rows; and,
 under ATTN_WINDOW_CACHE on top, the device-length step and the chunk step past the window: KVCache.step_state_begin(window=),
-attention_chunk(window=)).
+attention_chunk(window=)).  KV-cache slots with a length per row, opt-in (ATTN_SLOTS; KVCache.slots_begin,
+kv_append_rope_slots, attention_decode_slots: generate_many() of a standard_mha model).
 
 Part of apertis_llm_amd.ops.  torch is used for device memory, streams and autograd bookkeeping only; every computation is a
 HIP kernel launch through apertis_llm_amd._lib (csrc/attention.hip, csrc/attention_decode.hip, csrc/attention_deadrows.hip).
@@ -549,6 +550,10 @@ ATTN_DECODE_FUSED = True
 # _generate_graph_tail; kv_append_rope_at / attention_decode_at below).  OFF by default (APERTIS_MHA_DECODE_GRAPH=1 turns it
 # on): the eager loop's launch counts are pinned by tests, and flipping the default is a change of its own
 ATTN_DECODE_GRAPH = os.environ.get("APERTIS_MHA_DECODE_GRAPH", "0") == "1"
+# generate_many() serves a standard_mha model on KV-cache SLOTS - one row of the decode batch per prompt, every row with a
+# length of its own (KVCache.slots_begin; kv_append_rope_slots / attention_decode_slots below).  OFF by default
+# (APERTIS_MHA_SLOTS=1 turns it on): without it generate_many() refuses such a model as it always did
+ATTN_SLOTS = os.environ.get("APERTIS_MHA_SLOTS", "0") == "1"
 
 ATTN_DECODE_MAX_SPLITS = _lib.CONSTANTS["APERTIS_ATTN_DECODE_MAX_SPLITS"]
 
@@ -595,6 +600,14 @@ class KVCache:
     host read, or from the length its caller knows - and the by-value steps may go on.  Still one continuation per cache.
     step_state_begin(window=W) also keeps `step_window`: while it is set, attention_decode_at attends the newest W rows only.
 
+    SLOTS (opt-in, generate_many() of a standard_mha model: every row of the batch is a sequence of its own, installed and
+    freed while the others go on).  slots_begin() allocates `dev_lens` int64 [B] (the rows each slot holds), `dev_len`
+    int64[1] (their maximum: the one length the attention launch reads), `dev_valid` int64 [B, capacity], ZEROS - column j
+    of row b is nonzero iff j <= dev_lens[b] once the step's helper has run; the rows of a slot beyond its length hold the
+    previous occupant's keys and must stay masked - and `dev_err`.  slot_install / slot_free move a sequence in and out,
+    kv_append_rope_slots / attention_decode_slots are the step, slots_step_begin / slots_step_end bracket it once per token
+    step.  The host `lengths` are stale throughout, and the device step state and the slots exclude each other.
+
     `multi_token` (a flag, default False): a forward of several tokens extends this cache in place on the chunk kernels
     (kv_append_rope_chunk, attention_chunk) and hands the same object back, as a single-token step does; without the flag such
     a forward runs the stock branch on the cache's views, returns plain tensors and leaves the cache as it was."""
@@ -612,8 +625,9 @@ class KVCache:
         self.lengths = [int(length)] * len(self.k)
         self.multi_token = bool(multi_token)
         self._ws = None
-        self.dev_len = self.dev_valid = self.dev_err = None
+        self.dev_len = self.dev_valid = self.dev_err = self.dev_lens = None
         self.step_active, self.step_splits, self.step_window = False, 1, None
+        self.slot_active = False
 
     @classmethod
     def empty(cls, layers, B, capacity, W, dtype=torch.float32, device=None, multi_token=False):
@@ -662,21 +676,18 @@ class KVCache:
         keys, the most a step reads.  step_state_end() clears it."""
         if window is not None:
             window = _window("KVCache.step_state_begin", window)
+        if self.slot_active:
+            raise ApertisHipError("KVCache.step_state_begin: the cache is in slot mode (KVCache.slots_end() first)")
         if len(set(self.lengths)) != 1:
             raise ApertisHipError(f"KVCache.step_state_begin: the layers disagree on the length ({self.lengths})")
         B, cap, W = self.k[0].shape
         dev = self.k[0].device
         if W % heads:
             raise ApertisHipError(f"KVCache.step_state_begin: width {W} with {heads} heads")
-        lib = _lib.load()
         keys = min(max(int(L_end if L_end is not None else cap), 1), cap)
         if window is not None:
             keys = min(keys, window)
-        n = int(splits) if splits is not None else int(lib.apertis_attention_decode_splits(max(B, 1), heads, keys, W // heads))
-        nbytes = int(lib.apertis_attention_decode_workspace_bytes(B, heads, W // heads, n))
-        if nbytes < 0:
-            raise ApertisHipError(f"KVCache.step_state_begin: {n} splits outside [1, {ATTN_DECODE_MAX_SPLITS}]")
-        self._workspace(nbytes)
+        n = self._fixed_splits("KVCache.step_state_begin", heads, keys, splits)
         valid = torch.ones(B, cap, dtype=torch.int64, device=dev)
         if key_valid is not None:
             if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] > cap:
@@ -700,6 +711,95 @@ class KVCache:
             raise ApertisHipError(f"KVCache.step_state_end: length {length} outside [0, {self.capacity}]")
         self.lengths = [int(length)] * len(self.k)
         self.step_active, self.step_window = False, None
+
+    def _fixed_splits(self, what, heads, keys, splits):
+        """The split count of a run of device-length steps, fixed once (`splits`, or the library's choice at `keys` keys),
+        with the workspace sized for it."""
+        B, _, W = self.k[0].shape
+        lib = _lib.load()
+        n = int(splits) if splits is not None else int(lib.apertis_attention_decode_splits(max(B, 1), heads, keys, W // heads))
+        nbytes = int(lib.apertis_attention_decode_workspace_bytes(B, heads, W // heads, n))
+        if nbytes < 0:
+            raise ApertisHipError(f"{what}: {n} splits outside [1, {ATTN_DECODE_MAX_SPLITS}]")
+        self._workspace(nbytes)
+        return n
+
+    # ---- slots (class docstring) ----------------------------------------------------------------------------------------
+    def slots_begin(self, heads, L_end=None, splits=None):
+        """Slot mode: every row of the batch empty (`dev_lens` zeros, `dev_valid` ZEROS - the step state's default is ones;
+        here a column beyond a row's length must be 0).  The split count of attention_decode_slots is fixed here, once, at
+        `L_end` keys (default: the capacity) and B = the number of slots, unless `splits` gives it, and the workspace is
+        sized for it.  Refuses a cache whose device step state is active."""
+        if self.step_active:
+            raise ApertisHipError("KVCache.slots_begin: the device step state is active (KVCache.step_state_end() first)")
+        S, cap, W = self.k[0].shape
+        dev = self.k[0].device
+        if S < 1 or W % heads:
+            raise ApertisHipError(f"KVCache.slots_begin: {S} slots of width {W} with {heads} heads")
+        keys = min(max(int(L_end if L_end is not None else cap), 1), cap)
+        self.step_splits = self._fixed_splits("KVCache.slots_begin", heads, keys, splits)
+        self.dev_lens = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.dev_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.dev_valid = torch.zeros(S, cap, dtype=torch.int64, device=dev)
+        self.dev_err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._cols = torch.arange(cap, dtype=torch.int64, device=dev)
+        self.step_window, self.slot_active = None, True
+
+    def slots_end(self):
+        """Leaves slot mode; the device buffers stay readable.  The host `lengths` are what they were before slots_begin."""
+        if not self.slot_active:
+            raise ApertisHipError("KVCache.slots_end: the cache is not in slot mode")
+        self.slot_active = False
+
+    def _slot(self, what, b):
+        if not self.slot_active:
+            raise ApertisHipError(f"{what}: the cache is not in slot mode (KVCache.slots_begin)")
+        if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < self.k[0].shape[0]:
+            raise ApertisHipError(f"{what}: slot {b!r} outside [0, {self.k[0].shape[0]})")
+
+    def slot_install(self, b, past):
+        """A batch-1 prefill's `past_key_values` (per layer (k, v), [1, L, W]) into slot b: rows [0, L) of every layer are
+        copied, `dev_lens[b]` = L, `dev_valid[b]` = (column < L).  The slot's next step appends row L at rotary position L."""
+        self._slot("KVCache.slot_install", b)
+        _, cap, W = self.k[0].shape
+        if len(past) != len(self.k):
+            raise ApertisHipError(f"KVCache.slot_install: a prefill of {len(past)} layers for a cache of {len(self.k)}")
+        L = past[0][0].shape[1] if past[0][0].dim() == 3 else -1
+        for k, v in past:
+            if tuple(k.shape) != (1, L, W) or tuple(v.shape) != (1, L, W) or k.dtype != self.dtype or v.dtype != self.dtype:
+                raise ApertisHipError(f"KVCache.slot_install: k {tuple(k.shape)} {k.dtype}, v {tuple(v.shape)} {v.dtype} for a "
+                                      f"slot of [{cap}, {W}] {self.dtype} (one [1, L, {W}] pair per layer)")
+        if L > cap:
+            raise ApertisHipError(f"KVCache.slot_install: {L} rows do not fit a slot of {cap}")
+        for i, (k, v) in enumerate(past):
+            self.k[i][b, :L].copy_(k[0])
+            self.v[i][b, :L].copy_(v[0])
+        self.dev_lens[b] = L
+        self.dev_valid[b].copy_(self._cols < L)
+
+    def slot_free(self, b):
+        """Slot b empty: `dev_lens[b]` = 0 and `dev_valid[b]` = 0, so that a free row does not hold `dev_len` (the maximum,
+        the keys every row's work-groups walk) up.  Its K and V rows stay as they are: nothing reads them."""
+        self._slot("KVCache.slot_free", b)
+        self.dev_lens[b] = 0
+        self.dev_valid[b].zero_()
+
+    def slots_step_begin(self):
+        """Once per token step, BEFORE the forward: the validity column of the row each slot is about to append
+        (`dev_valid[b, dev_lens[b]]` = 1 - attention_decode_slots counts the new token's own key) and `dev_len` = the largest
+        `dev_lens`.  Device work only (a captured graph replays it).  A FULL slot (slot_install of `capacity` rows) has no
+        row to append: its step writes nothing and sets `dev_err` (kv_append_rope_slots); the index is clamped here so that
+        the scatter stays inside the buffer for it too."""
+        self.dev_valid.scatter_(1, self.dev_lens.clamp(max=self.capacity - 1).unsqueeze(1), 1)
+        torch.amax(self.dev_lens, 0, keepdim=True, out=self.dev_len)
+
+    def slots_step_end(self, alive):
+        """Once per token step, AFTER the selection: `dev_lens` = min(dev_lens + alive, capacity - 1), `alive` int64 [B] of
+        0 / 1.  THE CLAMP IS REQUIRED: inside a burst a row that has used up its budget is still alive on the device until
+        the host reads the burst; such a row must neither trip `dev_err` nor write outside its slot, so it rewrites its own
+        last row, and the host discards its tokens.  A row that is not alive (free, or past its eos) stays where it is and
+        rewrites that row."""
+        self.dev_lens.add_(alive).clamp_(max=self.capacity - 1)
 
     def _workspace(self, nbytes):
         if nbytes and (self._ws is None or self._ws.numel() * 4 < nbytes):
@@ -932,21 +1032,16 @@ def kv_append_rope_at(q, k, v, cache, layer, cos=None, sin=None, pos_offset=0):
     return qo
 
 
-def attention_decode_at(q, cache, layer, heads, splits=None):
-    """attention_decode over Lk = min(dev_len[0] + 1, capacity) keys, read by the kernel (after kv_append_rope_at and BEFORE
-    `dev_len` moves: the new token's own key included), under the cache's `dev_valid`.  splits: the FIXED number of pieces,
-    1..ATTN_DECODE_MAX_SPLITS, not bounded by Lk (default: what step_state_begin chose) - grid and workspace depend on it
-    alone, an empty piece contributes nothing.  The same bits as attention_decode(..., splits=n) for the same Lk.
-    With `cache.step_window` set (step_state_begin(window=)) the launch is apertis_attention_decode_window_at: only keys
-    [max(Lk - window, 0), Lk) are cut into the pieces and read - the bits of attention_decode(..., window=, splits=n)."""
-    _step_state(cache, "attention_decode_at")
+def _decode_dev(what, q, cache, layer, heads, splits, win):
+    """The launch attention_decode_at and attention_decode_slots share: `dev_len`, `dev_valid` and the fixed split count of
+    `cache`, under a window `win` or None."""
     _require_gpu(q, cache.k[layer])
     lib = _lib.load()
     kc, vc = cache.k[layer], cache.v[layer]
     B, cap, W = kc.shape
     n = cache.step_splits if splits is None else int(splits)
-    q, q_rs, D, ws, out = _decode_operands("attention_decode_at", lib, q, cache, layer, heads, n)
-    kv, win = cache.dev_valid, cache.step_window
+    q, q_rs, D, ws, out = _decode_operands(what, lib, q, cache, layer, heads, n)
+    kv = cache.dev_valid
     if win is None:
         _launch("apertis_attention_decode_at", lib.apertis_attention_decode_at,
                 (ptr(q), q_rs, ptr(kc), kc.stride(1), kc.stride(0), ptr(vc), vc.stride(1), vc.stride(0), cap, ptr(cache.dev_len),
@@ -959,3 +1054,60 @@ def attention_decode_at(q, cache, layer, heads, splits=None):
                  win, ptr(kv), kv.stride(0), ptr(out), W, ptr(ws), B, heads, D, n, dtype_code(q), stream_ptr()),
                 work=4.0 * B * keys * W, detail=f"{B}x{heads}x{D}", nbytes=2.0 * B * keys * W * q.element_size())
     return out
+
+
+def attention_decode_at(q, cache, layer, heads, splits=None):
+    """attention_decode over Lk = min(dev_len[0] + 1, capacity) keys, read by the kernel (after kv_append_rope_at and BEFORE
+    `dev_len` moves: the new token's own key included), under the cache's `dev_valid`.  splits: the FIXED number of pieces,
+    1..ATTN_DECODE_MAX_SPLITS, not bounded by Lk (default: what step_state_begin chose) - grid and workspace depend on it
+    alone, an empty piece contributes nothing.  The same bits as attention_decode(..., splits=n) for the same Lk.
+    With `cache.step_window` set (step_state_begin(window=)) the launch is apertis_attention_decode_window_at: only keys
+    [max(Lk - window, 0), Lk) are cut into the pieces and read - the bits of attention_decode(..., window=, splits=n)."""
+    _step_state(cache, "attention_decode_at")
+    return _decode_dev("attention_decode_at", q, cache, layer, heads, splits, cache.step_window)
+
+
+# ------------------------------------------------------------------------------------------------- slots: per-row lengths
+# The library's appends take ONE row and ONE position for all sequences, and its attentions read ONE length.  A slot has a
+# length of its own.  These two ops are the only places that know how that is driven through the entry points as they are;
+# a per-row kernel, once the C ABI has one, replaces their bodies and nothing above them.
+def _slot_state(cache, what):
+    if not cache.slot_active:
+        raise ApertisHipError(f"{what}: the cache is not in slot mode (KVCache.slots_begin)")
+
+
+def kv_append_rope_slots(q, k, v, cache, layer, cos=None, sin=None):
+    """kv_append_rope_at for a cache in slot mode: row b of q, k, v ([S, W] or [S, 1, W]) goes into row `dev_lens[b]` of slot
+    b at rotary position `dev_lens[b]`.  S launches of apertis_rope_kv_append_at with B = 1, each on pointers offset to its
+    row (host arithmetic, no views) and on `&dev_lens[b]` as its length: the same kernel, position and per-thread arithmetic
+    as kv_append_rope on that row alone, so the same bits.  It moves no length (slots_step_end does, once per step).  A row
+    outside the slot or a position outside the rotary table writes nothing and sets `cache.dev_err`.  Returns the rotated
+    q [S, W], one buffer."""
+    _slot_state(cache, "kv_append_rope_slots")
+    _require_gpu(q, k, v, cache.k[layer], cos, sin)
+    lib = _lib.load()
+    S, cap, W = cache.k[layer].shape
+    (q, q_rs), (k, k_rs), (v, v_rs), cos, sin, max_pos, qo = _append_operands("kv_append_rope_slots", q, k, v, cache, layer, cos,
+                                                                              sin)
+    kc, vc = cache.k[layer], cache.v[layer]
+    es, fn, code, st = q.element_size(), lib.apertis_rope_kv_append_at, dtype_code(q), stream_ptr()
+    qp, kp, vp, qop, kcp, vcp = ptr(q), ptr(k), ptr(v), ptr(qo), ptr(kc), ptr(vc)
+    lens, err, cs, sn = ptr(cache.dev_lens), ptr(cache.dev_err), ptr(cos), ptr(sin)
+    kc_rs, kc_bs, vc_rs, vc_bs = kc.stride(1), kc.stride(0), vc.stride(1), vc.stride(0)
+    for b in range(S):
+        _launch("apertis_rope_kv_append_at", fn,
+                (qp + b * q_rs * es, q_rs, kp + b * k_rs * es, k_rs, vp + b * v_rs * es, v_rs, cs, sn, max_pos, lens + 8 * b, 0,
+                 err, qop + b * W * es, W, kcp + b * kc_bs * es, kc_rs, kc_bs, vcp + b * vc_bs * es, vc_rs, vc_bs, cap, 1, W,
+                 code, st), work=5.0 * W * es)
+    return qo
+
+
+def attention_decode_slots(q, cache, layer, heads, splits=None):
+    """attention_decode for a cache in slot mode, after kv_append_rope_slots: row b attends keys [0, dev_lens[b]] of slot b.
+    ONE apertis_attention_decode_at launch over all slots on `dev_len` (the largest slot length, slots_step_begin) under
+    `dev_valid`: a key past a slot's own length is masked, a masked key is never read and scores -inf exactly like a key out
+    of range - no bit of (m, l, o) moves - and a wave's walk starts at j0 + w * KPW whatever the key count is; so at
+    splits = 1 row b has the bits of attention_decode(..., splits=1) on that row alone with Lk = dev_lens[b] + 1.  splits:
+    the fixed number of pieces (default: what slots_begin chose); the pieces cut the LONGEST row's range."""
+    _slot_state(cache, "attention_decode_slots")
+    return _decode_dev("attention_decode_slots", q, cache, layer, heads, splits, None)

@@ -7,6 +7,19 @@ its budget; whatever a row emitted beyond that before the host looked is dropped
 """
 
 
+def mha_slot_capacity(lens, budgets):
+    """Rows a KV-cache slot needs so that every prompt fits: max_i(len_i + budget_i) - 1, at least 1.  The last kept token
+    of prompt i is selected after the step that appends row len_i + budget_i - 2, so rows [0, len_i + budget_i - 1) are all
+    a slot ever has to hold."""
+    return max([int(n) + int(m) - 1 for n, m in zip(lens, budgets)] + [1])
+
+
+def mha_slot_overrun(lens, budgets, max_pos):
+    """Index of the first prompt whose len_i + budget_i - 1 exceeds a rotary table of `max_pos` positions (its last step
+    would be positioned at len_i + budget_i - 2 >= max_pos, or - budget 1 - its prefill does not fit), None when all fit."""
+    return next((i for i, (n, m) in enumerate(zip(lens, budgets)) if int(n) + int(m) - 1 > max_pos), None)
+
+
 class SlotSchedule:
     """`n_prompts` prompts, `budgets[i]` new tokens at most for prompt i, `slots` rows.  Invariant between calls:
     len(live()) + pending + done == n_prompts."""
