@@ -13,6 +13,7 @@ paths: off-GPU they raise ApertisHipError.
 """
 import functools
 import inspect
+import itertools
 import json
 import logging
 import math
@@ -1198,7 +1199,8 @@ class _AttnMask:
     `layout` (packed rows, `document_ids`): the ops.DocumentLayout of this forward, computed once; the fused path then runs
     ops.document_attention, and the additive mask is the block-diagonal causal one.  `layout_pos`: the positions the layers
     receive are the layout's own (positions within each document, all in [0, L)), so the per-layer RoPE call does not
-    range-check them on the host again.
+    range-check them on the host again; an integer instead of True is their bound (the longest document, known on the host:
+    prefill_packed), which then stands against the rotary table in place of L.
     `window`: the active sliding window (_active_window: None unless ops.ATTN_WINDOW is on and the configuration sets one) -
     a query attends its last `window` keys only.  Every path reads it: ops.window_attention, ops.attention_decode(window=),
     and the stock branch as a band on its additive mask; the chunk kernels and the graph replay decline once it matters.  A
@@ -1409,11 +1411,15 @@ class ApertisModel(nn.Module):
     @_on_input_device
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, pixel_values=None, use_cache=None, output_attentions=None,
-                output_hidden_states=None, return_dict=None, document_ids=None):
+                output_hidden_states=None, return_dict=None, document_ids=None, _packed_kv=None):
         """document_ids: int64 [B, L], non-decreasing along L - PACKED rows (standard_mha, or selective_ssm on a ROCm device
         under ops.SSM_PACKED; no cache): a run of equal ids is one document, a token attends within its document only (an SSM
         layer's conv and state stop at its start) and, with position_ids = None, is positioned within it (the pad tail of a
         row is a document of its own, so no attention_mask goes with it); _packed_layout has the rules.
+        _packed_kv (internal: ApertisForCausalLM.prefill_packed, which has made sure that the layers take the document
+        kernels): the length of the row's longest document, a host integer.  The packed forward then keeps every layer's
+        post-RoPE (k, v) [B, L, W] and returns them in slot 3, and that length - not the row's - is what the rotary table must
+        hold.  Only the use_cache refusal of _packed_layout is skipped; every other check of it applies.
         past_key_values: a prefill's tuple of per-layer pairs (plain tensors in, plain tensors out), or for standard_mha an
         ops.KVCache: a single-token step then appends to it IN PLACE on the decode kernels and hands the same object back
         (position_ids = None: the step's position is the cache's length); a cache with `multi_token` set takes a forward of
@@ -1451,6 +1457,10 @@ class ApertisModel(nn.Module):
             attention_mask = None
             if pos is None:
                 pos = layout.positions
+            if _packed_kv is not None:
+                if ssm or position_ids is not None:
+                    raise ValueError("_packed_kv: standard_mha with the layout's own positions only (prefill_packed)")
+                use_c = True
         if dev_step:
             if cfg.position_embedding_type == "absolute" and self.abs_pos_embeddings is not None:
                 raise ops.ApertisHipError("absolute position embeddings need the step's position on the host: not with a "
@@ -1482,8 +1492,9 @@ class ApertisModel(nn.Module):
             window = _active_window(cfg)
             if window is not None and x.shape[1] > window:        # the documents' bounds clipped to the window, once per forward
                 layout = ops.window_layout(layout, window)
+            # (layout_pos as an integer: the bound of the positions, rope_qk's in_range - the longest document of prefill_packed)
             mask = _AttnMask(None, True, False, lambda: self._document_additive_mask(layout, x.dtype), layout=layout,
-                             layout_pos=own_pos)
+                             layout_pos=int(_packed_kv) if own_pos and _packed_kv is not None else own_pos)
         elif ssm:
             # (the SSM layers read no mask, as in the reference - under ops.SSM_LEFT_PAD the starts of a left-padded prefill)
             mask = self._ssm_left_pad(attention_mask, x, past_key_values, pixel_values, out_att)
@@ -2095,10 +2106,83 @@ class ApertisForCausalLM(nn.Module):
         restore()
         return graph
 
+    _NO_PACKED_SSM_PREFILL = ("a selective_ssm model has no packed prefill: the packed scan returns no per-document end state "
+                              "and no conv window; that needs kernel work and is not offered")
+
+    def _packed_prefill_refusals(self, what):
+        """What keeps a packed prefill off the document kernels, each a ValueError naming the condition, before any GPU
+        work: there is no stock fallback (ApertisAttention._fused_ok would quietly take one)."""
+        cfg, attn = self.config, self.model.layers[0].attention
+        if cfg.attention_type != "standard_mha":
+            raise ValueError(f"{what}: {self._NO_PACKED_SSM_PREFILL}")
+        if self.lm_head.weight.device.type != "cuda":
+            raise ValueError(f"{what}: the model is not on a GPU (there is no CPU path)")
+        if self.training:
+            raise ValueError(f"{what}: the model is in training mode (call .eval())")
+        if cfg.output_attentions:
+            raise ValueError(f"{what}: output_attentions (the document kernels return no attention weights)")
+        if not ops.ATTN_FUSED:
+            raise ValueError(f"{what}: ops.ATTN_FUSED is off (a packed prefill runs on the document kernels only)")
+        if attn.attention_head_size not in (64, 128) or cfg.hidden_size != attn.attention_head_size * attn.num_attention_heads:
+            raise ValueError(f"{what}: head dim {attn.attention_head_size} (the document kernels take 64 or 128)")
+        if self._mha_slot_dtype() not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"{what}: dtype {self._mha_slot_dtype()} (the document kernels take fp32 or bf16)")
+
+    @torch.no_grad()
+    def prefill_packed(self, prompts):
+        """The prefill of n >= 1 prompts of a standard_mha model as ONE forward over a packed row [1, sum L_i]: the prompts
+        are the row's documents 0 ... n-1 in list order (ApertisModel.forward(document_ids=...)), so a token attends within
+        its prompt only and is positioned within it, the attention runs on the document kernels (ops.document_attention:
+        key tiles in front of a query's document are skipped) and no padding is computed.  A token's K and V rows depend on
+        its own document alone, so slicing every layer's post-RoPE (k, v) of the row by document gives each prompt the
+        prefill cache it gets in a row of its own - up to the rounding of projections run at another row count.
+
+        prompts: 1-D int64 tensors on the model's GPU, or lists of ids, each of at least one token and no longer than the
+        rotary table (the row may be longer than the table: the longest prompt is what it must hold).
+        Returns (logits, pasts): logits [n, V], the LM head on the n last-token rows of the final hidden states (gathered
+        before the head: the [sum L_i, V] logits are never formed); pasts[i], a tuple per layer of (k, v), each [1, L_i, W] -
+        VIEWS of the packed row's tensors, not copies, in the form KVCache.slot_install and KVCache.from_prefill take (both
+        copy).  One host read, ops.document_layout's.
+
+        Eval mode, on the GPU, no autograd.  There is no stock fallback: ops.ATTN_FUSED off, a head dim other than 64 / 128,
+        a dtype other than fp32 / bf16, output_attentions, training mode, a CPU model or a selective_ssm model raise
+        ValueError before any GPU work (_packed_prefill_refusals), as do an empty list, an empty prompt and a prompt longer
+        than the rotary table.  The public forward(document_ids=..., use_cache=True) keeps raising: only this method keeps
+        a packed row's (k, v).
+
+        MoE models: the expert capacity limit applies in training mode only (AdaptiveExpertSystem.forward), so in eval mode
+        routing is per token and a packed row changes no document's routing."""
+        self._packed_prefill_refusals("prefill_packed()")
+        cfg, dev = self.config, self.lm_head.weight.device
+        prompts = list(prompts)
+        if not prompts:
+            raise ValueError("prefill_packed(): no prompts")
+        rope = self.model.layers[0].attention.rope
+        max_pos = rope.cos_cached.shape[0] if rope is not None else cfg.max_position_embeddings
+        for i, p in enumerate(prompts):
+            if isinstance(p, torch.Tensor) and (p.device != dev or p.dim() != 1 or p.dtype != torch.int64):
+                raise ValueError(f"prefill_packed(): prompt {i} is a {p.dtype} tensor of shape {tuple(p.shape)} on {p.device}, "
+                                 "expected 1-D int64 on the model's GPU")
+            if len(p) == 0:
+                raise ValueError(f"prefill_packed(): prompt {i} is empty")
+            if len(p) > max_pos:
+                raise ValueError(f"prefill_packed(): prompt {i} of {len(p)} tokens runs past the rotary table ({max_pos} "
+                                 "positions)")
+        lens = [len(p) for p in prompts]
+        ends = list(itertools.accumulate(lens))
+        with ops.prep_cache_scope(), ops.device_guard(self.lm_head.weight):
+            ids = [p if isinstance(p, torch.Tensor) else torch.tensor(list(p), dtype=torch.int64, device=dev) for p in prompts]
+            docs = torch.repeat_interleave(torch.arange(len(lens)), torch.tensor(lens)).to(dev)
+            outs = self.model(input_ids=torch.cat(ids)[None], document_ids=docs[None], _packed_kv=max(lens))
+            last = torch.tensor([e - 1 for e in ends], dtype=torch.int64).to(dev)
+            logits = self.lm_head(outs[0][0].index_select(0, last))
+        pasts = [tuple((k[:, a:b], v[:, a:b]) for k, v in outs[3]) for a, b in zip([0] + ends, ends)]
+        return logits, pasts
+
     @torch.no_grad()
     def generate_many(self, prompts, max_new_tokens=20, slots: int = 16, do_sample: bool = False, temperature: float = 1.0,
                       top_k: int = 50, top_p: float = 1.0, repetition_penalty: float = 1.0, eos_token_id=None,
-                      pad_token_id=None, return_stats: bool = False, pixel_values=None):
+                      pad_token_id=None, return_stats: bool = False, pixel_values=None, prefill_tokens: Optional[int] = None):
         """generate() for many prompts of a selective_ssm model on ONE decode batch of `slots` rows whose finished rows are
         refilled: a prompt is prefilled alone (the call generate() makes for it), its conv windows and SSM states are copied
         into a free row of the static decode state, and the token step - the graph-replayed one where generate() would
@@ -2126,16 +2210,33 @@ class ApertisForCausalLM(nn.Module):
         than 64 / 128 or a dtype other than fp32 / bf16, an active sliding window, ops.ATTN_FUSED or ops.ATTN_DECODE_FUSED
         off, a prompt whose length + budget - 1 exceeds the rotary table.
 
+        prefill_tokens (standard_mha under ops.ATTN_SLOTS only; None, the default: every prompt is prefilled alone, as
+        above): an integer >= 1 makes a refill ROUND of the waiting prompts - in arrival order one per free slot, until the
+        next one would bring the round's prompt tokens past `prefill_tokens`, at least one (serving.prefill_round).  A round
+        of two or more prompts is ONE prefill_packed() call, whose per-document (k, v) views slot_install copies; a round of
+        one prompt is the batch-1 forward of the default.  Every prompt's first token is selected by the calls the default
+        makes for it (the sampled draw has the prompt's prefill ordinal as its counter, so it does not depend on the knob),
+        with one host read per round instead of one per prompt; a prompt that ends at its first token leaves its slot free
+        for the next round.  Greedy runs are token-equal to the alone runs as long as no step's top-2 logits tie within the
+        rounding of projections run at another row count.  Anything but an integer >= 1 (bools included) and a selective_ssm
+        model (its packed scan returns no per-document end state and no conv window) raise ValueError before any forward.
+
         return_stats=True: (outputs, stats) with stats = {"steps": token steps run, "replays": of them graph replays,
-        "graphs": graphs captured, "prefills": batch-1 prefills into slots, "live_slot_steps": sum over steps of the rows
+        "graphs": graphs captured, "prefills": prompts prefilled into slots, "live_slot_steps": sum over steps of the rows
         whose token was kept, "slot_steps": steps * slots, "fallbacks": indices of the prompts that ran through
-        generate()}."""
+        generate()} - and, only when prefill_tokens is not None, "prefill_forwards": the prefill forwards run (batch-1
+        ones plus packed ones)."""
         cfg = self.config
         mha = cfg.attention_type == "standard_mha"
         if mha and not ops.ATTN_SLOTS:
             raise ValueError("generate_many(): slots serve selective_ssm models; a standard_mha model batches through "
                              "generate(past_key_values=...) with a KVCache, or one left-padded generate() batch (KV-cache "
                              "slots are opt-in: ops.ATTN_SLOTS / APERTIS_MHA_SLOTS=1)")
+        if prefill_tokens is not None:
+            if isinstance(prefill_tokens, bool) or not isinstance(prefill_tokens, int) or prefill_tokens < 1:
+                raise ValueError(f"generate_many(): prefill_tokens must be None or an integer >= 1, got {prefill_tokens!r}")
+            if not mha:
+                raise ValueError(f"generate_many(prefill_tokens=...): {self._NO_PACKED_SSM_PREFILL}")
         if cfg.position_embedding_type == "absolute":
             raise ValueError("generate_many(): absolute position embeddings (a slot's position would differ per row)")
         if pixel_values is not None:
@@ -2166,7 +2267,7 @@ class ApertisForCausalLM(nn.Module):
         ids = [p if isinstance(p, torch.Tensor) else torch.tensor(list(p), dtype=torch.int64, device=dev) for p in prompts]
         with ops.prep_cache_scope(), ops.device_guard(self.lm_head.weight):
             outs, stats = self._generate_many(ids, budgets, slots, do_sample, temperature, top_k, top_p, repetition_penalty,
-                                              eos_token_id, pad_token_id)
+                                              eos_token_id, pad_token_id, prefill_tokens)
         return (outs, stats) if return_stats else outs
 
     def _mha_slot_dtype(self):
@@ -2215,14 +2316,15 @@ class ApertisForCausalLM(nn.Module):
         return state, [t for pair in state for t in pair]
 
     def _generate_many(self, ids, budgets, S, do_sample, temperature, top_k, top_p, repetition_penalty, eos_token_id,
-                       pad_token_id):
+                       pad_token_id, prefill_tokens=None):
         """generate_many()'s loop.  The slot state is the SSM layers' conv windows and states (_slot_state), or - standard_mha
         under ops.ATTN_SLOTS - ONE ops.KVCache in slot mode with serving.mha_slot_capacity rows per slot, allocated once per
         call: a prompt's batch-1 prefill is installed with KVCache.slot_install, a freed row is emptied with slot_free where
         the alive flags are rewritten, the step body is bracketed by slots_step_begin / slots_step_end, and the cache's error
         word rides in the burst's host read.  Everything else - the schedule, the burst rule, the sampler's handling, the
-        capture - is one code for both."""
-        from .serving import SlotSchedule, mha_slot_capacity
+        capture - is one code for both.  `prefill_tokens` (standard_mha only, checked by the caller): refill rounds whose
+        two or more prompts are one prefill_packed() forward; a prompt's first token and install are `settle` either way."""
+        from .serving import SlotSchedule, mha_slot_capacity, prefill_round
         cfg, dev = self.config, self.lm_head.weight.device
         mha = cfg.attention_type == "standard_mha"
         eos = cfg.eos_token_id if eos_token_id is None else eos_token_id
@@ -2233,6 +2335,8 @@ class ApertisForCausalLM(nn.Module):
         window = 0 if mha else cfg.ssm_conv_kernel - 1        # (any prompt fits a KV-cache slot: no fallback there)
         sched = SlotSchedule(len(ids), budgets, S)
         stats = {"steps": 0, "replays": 0, "graphs": 0, "prefills": 0, "live_slot_steps": 0, "slot_steps": 0, "fallbacks": []}
+        if prefill_tokens is not None:
+            stats["prefill_forwards"] = 0
         s_tok = torch.full((S, 1), pad, dtype=torch.long, device=dev)
         s_alive = torch.zeros(S, dtype=torch.long, device=dev)
         s_idx = torch.zeros(1, dtype=torch.long, device=dev)            # column of s_out: zeroed before every burst
@@ -2240,7 +2344,8 @@ class ApertisForCausalLM(nn.Module):
         burst = max(int(GENERATE_MANY_BURST), 1)
         s_out = torch.full((S, max(burst, 2)), pad, dtype=torch.long, device=dev)      # (the capture's warm-up runs two steps)
         s_nxt = torch.empty(S, dtype=torch.long, device=dev)
-        s_one = torch.ones(1, dtype=torch.long, device=dev)             # an install's one-row alive flag, and where its
+        s_ones = torch.ones(S, dtype=torch.long, device=dev)            # the alive flags of a refill round's rows
+        s_one = s_ones[:1]                                              # an install's one-row alive flag, and where its
         s_end = torch.empty(1, dtype=torch.long, device=dev)            # kernel puts the flag after the token (the host decides)
         want_sampler = do_sample or repetition_penalty != 1.0
         sampler = state = graph = None
@@ -2255,14 +2360,20 @@ class ApertisForCausalLM(nn.Module):
             in_place.extend([cache.dev_lens, cache.dev_len, cache.dev_valid, cache.dev_err])
 
         def install(i, b):
-            """Prompt i's prefill and first token (a host integer); its caches go into row b if the slot then is live."""
+            """Prompt i's batch-1 prefill; its first token and caches as a round of one (settle)."""
+            out = self(input_ids=ids[i][None], use_cache=True)
+            settle([(i, b)], out[1][:, -1, :], [out[4]])
+
+        def settle(taken, logits, pasts):
+            """The end of a refill round: `taken`, its (prompt, free slot) pairs in arrival order; `logits` [n, V], their
+            last-position rows; `pasts[j]`, the j-th prompt's batch-1 caches (prefill_packed's views are such).  Every
+            first token is selected on the device as a prompt prefilled alone selects it, ONE host read brings them back
+            (with the sampler's error word), and a prompt's caches go into its row if the slot then is live."""
             nonlocal sampler, state
-            prompt = ids[i]
-            out = self(input_ids=prompt[None], use_cache=True)
-            stats["prefills"] += 1
-            logits, past = out[1][:, -1, :], out[4]
+            ordinal = stats["prefills"] + 1                # (of the round's first prompt: prompts prefilled so far, plus one)
+            stats["prefills"] += len(taken)
             if state is None:
-                state, bufs = self._slot_state(past, S)
+                state, bufs = self._slot_state(pasts[0], S)
                 in_place.extend(bufs)
             if want_sampler and sampler is None:
                 if not (ops.SAMPLE_FUSED and ops.sample_supported(logits)):
@@ -2271,39 +2382,44 @@ class ApertisForCausalLM(nn.Module):
                                               "stock path over slots")
                 # (ids >= V are skipped by the occurrence table: it starts at zero, a row is rebuilt when a prompt moves in)
                 none = torch.full((S, 1), logits.shape[-1], dtype=torch.long, device=dev)
-                sampler = ops.Sampler(logits.expand(S, -1), none, do_sample=do_sample, temperature=temperature, top_k=top_k,
+                sampler = ops.Sampler(logits[:1].expand(S, -1), none, do_sample=do_sample, temperature=temperature, top_k=top_k,
                                       top_p=top_p, repetition_penalty=repetition_penalty, eos=eos, pad=pad)
                 if sampler.uniforms is not None:
                     raise ops.ApertisHipError("generate_many(): ops.sample.SAMPLE_UNIFORMS is generate()'s test hook")
                 in_place.extend(t for t in (sampler.counts, sampler.err) if t is not None)
             if sampler is None:
-                nxt, _ = _select_tokens(logits.float(), s_one, eos, pad)
-                first = int(nxt)
+                # (an argmax per row: the rows of a round select what each selects as the one row of its own call)
+                nxt, _ = _select_tokens(logits.float(), s_ones[:len(taken)], eos, pad)
+                firsts = nxt.tolist()
             else:
-                counts = None
-                if sampler.counts is not None:
-                    sampler.counts[b].copy_(ops.token_counts(prompt[None], logits.shape[-1], sampler.err)[0])
-                    counts = sampler.counts[b:b + 1]
-                # (the kernel sees row 0 here: the draw counters of the installs lie above every step of the call)
-                nxt = ops.sample_next(logits, s_one, sampler.err, do_sample=sampler.do_sample, temperature=sampler.temp,
-                                      top_k=sampler.top_k, top_p=sampler.top_p, repetition_penalty=sampler.penalty,
-                                      counts=counts, eos=sampler.eos, pad=sampler.pad, seed=sampler.seed,
-                                      step=sampler.zero_step, step_off=(1 << 40) + stats["prefills"],
-                                      alive_out=s_end, out=s_nxt[b:b + 1])
-                first, code = torch.cat((nxt, sampler.err.to(nxt.dtype))).tolist()
+                for j, (i, b) in enumerate(taken):
+                    counts = None
+                    if sampler.counts is not None:
+                        sampler.counts[b].copy_(ops.token_counts(ids[i][None], logits.shape[-1], sampler.err)[0])
+                        counts = sampler.counts[b:b + 1]
+                    # (the kernel sees row 0 here: the draw counters of the installs - the prompt's prefill ordinal, whatever
+                    #  the round it came in - lie above every step of the call)
+                    ops.sample_next(logits[j:j + 1], s_one, sampler.err, do_sample=sampler.do_sample, temperature=sampler.temp,
+                                    top_k=sampler.top_k, top_p=sampler.top_p, repetition_penalty=sampler.penalty,
+                                    counts=counts, eos=sampler.eos, pad=sampler.pad, seed=sampler.seed,
+                                    step=sampler.zero_step, step_off=(1 << 40) + ordinal + j,
+                                    alive_out=s_end, out=s_nxt[b:b + 1])
+                nxt = s_nxt[b:b + 1] if len(taken) == 1 else torch.cat([s_nxt[b:b + 1] for _, b in taken])
+                *firsts, code = torch.cat((nxt, sampler.err.to(nxt.dtype))).tolist()
                 sampler.check(code)
-            if sched.place(b, first, eos_set):
-                moved.append(b)
-                s_tok[b].copy_(nxt)
-                if cache is not None:
-                    cache.slot_install(b, past)
-                elif isinstance(state, _StackedPast):
-                    state.conv_all[:, b].copy_(torch.stack([c[0] for c, _ in past]))
-                    state.state_all[:, b].copy_(torch.stack([st[0].reshape(-1) for _, st in past]))
-                else:
-                    for (sc, ss), (c, st) in zip(state, past):
-                        sc[b].copy_(c[0])
-                        ss[b].copy_(st[0])
+            for j, ((i, b), first, past) in enumerate(zip(taken, firsts, pasts)):
+                if sched.place(b, first, eos_set):
+                    moved.append(b)
+                    s_tok[b].copy_(nxt[j:j + 1])
+                    if cache is not None:
+                        cache.slot_install(b, past)
+                    elif isinstance(state, _StackedPast):
+                        state.conv_all[:, b].copy_(torch.stack([c[0] for c, _ in past]))
+                        state.state_all[:, b].copy_(torch.stack([st[0].reshape(-1) for _, st in past]))
+                    else:
+                        for (sc, ss), (c, st) in zip(state, past):
+                            sc[b].copy_(c[0])
+                            ss[b].copy_(st[0])
 
         def body():
             if cache is not None:
@@ -2335,6 +2451,17 @@ class ApertisForCausalLM(nn.Module):
         want_graph = DECODE_GRAPH and bool(slotted) and max(slotted) - 1 >= DECODE_GRAPH_MIN_STEPS
         moved = [None]                 # slots filled or freed since s_alive was last written (None: not written yet)
         while not sched.finished():
+            # prefill_tokens: refill rounds - the waiting prompts one per free slot up to the token cap (prefill_round), two
+            # or more of them as one packed forward; a prompt that ends at its first token frees its slot for the next round
+            while prefill_tokens is not None and sched.head() is not None and sched.free():
+                free = sched.free()
+                wait = sched.waiting(len(free))
+                taken = [(wait[j], free[j]) for j in prefill_round([len(ids[i]) for i in wait], len(free), prefill_tokens)]
+                if len(taken) == 1:                        # (the alone call: the knob never makes a lone prefill slower)
+                    install(*taken[0])
+                else:
+                    settle(taken, *self.prefill_packed([ids[i] for i, _ in taken]))
+                stats["prefill_forwards"] += 1
             # every free slot takes the next prompts in arrival order until one stays (or none waits)
             for b in sched.free():
                 while sched.head() is not None and sched.slot[b] is None:

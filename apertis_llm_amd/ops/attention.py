@@ -119,10 +119,13 @@ def _positions(position_ids, B, L, max_pos, in_range=False):
     """(int64 tensor or None, batch stride).  Explicit positions are range-checked here, on the host: the stock module's
     cos_cached[position_ids] raises IndexError for them, so this does too (one sync; the model passes None for its own
     arange positions).  in_range: the caller vouches that every position lies in [0, L) (a document layout's positions:
-    ops.document_layout built them), so L against the table is the whole check and nothing is read back."""
+    ops.document_layout built them), so L against the table is the whole check and nothing is read back.  in_range = an
+    integer n (not True): the caller knows more - every position lies in [0, n), n the longest document of a packed row -
+    and n against the table is the check, so a row longer than the table passes when none of its documents is."""
     if position_ids is None or in_range:
-        if L > max_pos:
-            raise IndexError(f"sequence length {L} exceeds the rotary table ({max_pos} positions)")
+        n = L if position_ids is None or in_range is True else int(in_range)
+        if n > max_pos:
+            raise IndexError(f"sequence length {n} exceeds the rotary table ({max_pos} positions)")
     if position_ids is None:
         return None, 0
     pos = position_ids
@@ -175,7 +178,7 @@ def rope_qk(q, k, position_ids, cos, sin, in_range=False):
     """RotaryEmbedding.forward applied to q and k [B, L, W] in one launch (reference core.py:258-293: interleaved pairs over the
     FULL width).  cos / sin: the module's fp32 cos_cached / sin_cached [max_pos, W/2]; position_ids int64 [1 or B, L] or None
     (positions 0..L-1).  Bit-identical to the stock module for fp32 and bf16; q and k share a shape and a dtype.
-    in_range=True: the positions are known to lie in [0, L) (_positions), no host range check."""
+    in_range=True: the positions are known to lie in [0, L) (_positions), no host range check; an integer n: in [0, n)."""
     _require_gpu(q, k, position_ids, cos, sin)
     if q.shape != k.shape or q.dtype != k.dtype or q.dim() != 3:
         raise ApertisHipError(f"rope_qk: q {tuple(q.shape)} {q.dtype} and k {tuple(k.shape)} {k.dtype} must match, [B, L, W]")

@@ -3,7 +3,9 @@ produced, and when a slot is free for the next prompt.  Plain Python on host int
 that owns the GPU state (model.py) asks `head()` for the next prompt in arrival order, either installs it into a free slot
 (`place`, with the first token its prefill selected) or finishes it outside the slots (`complete`), and after every burst
 of token steps hands over what each slot's row emitted (`feed`).  A prompt's run ends with its first eos, inclusive, or at
-its budget; whatever a row emitted beyond that before the host looked is dropped here.
+its budget; whatever a row emitted beyond that before the host looked is dropped here.  With generate_many(prefill_tokens=N)
+the loop fills its free slots in rounds: `waiting(k)` lists the next prompts, `prefill_round` says how many of them one
+packed prefill takes.
 """
 
 
@@ -18,6 +20,20 @@ def mha_slot_overrun(lens, budgets, max_pos):
     """Index of the first prompt whose len_i + budget_i - 1 exceeds a rotary table of `max_pos` positions (its last step
     would be positioned at len_i + budget_i - 2 >= max_pos, or - budget 1 - its prefill does not fit), None when all fit."""
     return next((i for i, (n, m) in enumerate(zip(lens, budgets)) if int(n) + int(m) - 1 > max_pos), None)
+
+
+def prefill_round(waiting_lens, free_slots, cap):
+    """Which of the waiting prompts one refill round of generate_many(prefill_tokens=cap) takes, as indices into
+    `waiting_lens`, their lengths in arrival order.  A prefix - arrival order is kept - of at most `free_slots` prompts
+    (one per free slot) whose lengths sum to `cap` at the most, and never less than one prompt: a prompt longer than the
+    cap is taken alone.  Empty only when nothing waits or no slot is free."""
+    taken, total = [], 0
+    for j, n in enumerate(waiting_lens[:max(int(free_slots), 0)]):
+        if taken and total + int(n) > cap:
+            break
+        taken.append(j)
+        total += int(n)
+    return taken
 
 
 class SlotSchedule:
@@ -72,6 +88,16 @@ class SlotSchedule:
     def head(self):
         """Index of the next prompt in arrival order, None when none waits."""
         return self._next if self._next < self.n else None
+
+    def waiting(self, k):
+        """The next `k` prompts in arrival order (fewer when fewer wait), the head first: what k calls of place() or
+        complete() in a row would take.  Prompts with nothing to generate are skipped, as head() skips them."""
+        out, i = [], self._next
+        while i < self.n and len(out) < k:
+            if self.budgets[i] > 0:
+                out.append(i)
+            i += 1
+        return out
 
     def place(self, b, first, eos=()):
         """The head prompt goes into free slot b with `first`, the token its prefill selected.  Returns whether the slot is

@@ -7,14 +7,18 @@ create_apertis_model("125M"), standard_mha, bf16 autocast, greedy; 64 prompts of
 tokens per prompt drawn uniformly from 16 ... 256 and cut so that length + budget stays inside the 2 048-position rotary
 table (fixed seeds), no eos: a prompt is done at its budget.  Three legs, alternated in one process, --rounds times each:
   "many"           generate_many(slots=16) under ops.ATTN_SLOTS (the step replays as a graph: model.DECODE_GRAPH)
-  "leftpad"        the same prompts in arrival order as four left-padded generate() batches of 16 under ops.ATTN_LEFT_PAD,
+  "many_prefill_N" the same with prefill_tokens=N, N = 4 096, 8 192, 16 384, 32 768: the waiting prompts of a refill round
+                   as one packed row (prefill_packed).  A row length that the layout or the document kernels decline ends
+                   that leg, and its line says what declined it
+  "leftpad"       the same prompts in arrival order as four left-padded generate() batches of 16 under ops.ATTN_LEFT_PAD,
   "leftpad_graph"  each run to its group's largest budget - or to the end of the rotary table, whichever comes first: the
                    padded width is every row's position - from the eager loop and with ops.ATTN_DECODE_GRAPH; only each
                    row's own budgeted tokens count, and the line says how many of them the table cut off
   "alone"          64 batch-1 generate() calls, from the eager loop and with ops.ATTN_DECODE_GRAPH
   "alone_graph"
 The metric is the budgeted new tokens a leg produced over wall time, prefills included.  "many" also reports, from the call's
-stats, the token steps it ran and the share of slot-steps that were live.
+stats, the token steps it ran and the share of slot-steps that were live; the "many" legs also report the prefill forwards
+they made and the summed time of their refill phases (RefillClock: events, no synchronisation inside the call).
 
 Two more lines, measured once:
   "slot_step"      16 prompts of 1 024 tokens, 129 new tokens each (no refill): the replayed slot step's wall time (first to last
@@ -36,6 +40,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 N, SLOTS, LEN_LO, LEN_HI, NEW_LO, NEW_HI, TABLE = 64, 16, 200, 1920, 16, 256, 2048
+CAPS = (4096, 8192, 16384, 32768)                     # generate_many(prefill_tokens=...): the "many_prefill_<cap>" legs
+CAP_OF = {f"many_prefill_{cap}": cap for cap in CAPS}
 
 
 def workload():
@@ -43,6 +49,66 @@ def workload():
     lens = [rng.randint(LEN_LO, LEN_HI) for _ in range(N)]
     budgets = [min(rng.randint(NEW_LO, NEW_HI), TABLE - n) for n in lens]
     return lens, budgets
+
+
+class RefillClock:
+    """The refill phases of one generate_many() call, timed apart from its token steps with events and no synchronisation
+    of its own: a phase opens at the first prefill forward (a batch-1 forward without a cache, or prefill_packed) after a
+    step and closes when the next graph replay - or the graph's capture - is about to start, so it holds the prefill
+    forwards of the phase's rounds, the first-token selections with their host reads, the installs and the rewrite of the
+    alive flags.  ms() reads the events after the caller's own synchronize()."""
+
+    def __init__(self, model):
+        self.model, self.spans, self.open = model, [], None
+
+    def _event(self):
+        import torch
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+
+    def _close(self):
+        if self.open is not None:
+            self.spans.append((self.open, self._event()))
+            self.open = None
+
+    def __enter__(self):
+        import torch
+        model, clock = self.model, self
+        forward, packed, capture, self.replay = model.forward, model.prefill_packed, model._capture_step, torch.cuda.CUDAGraph.replay
+
+        def spy_forward(*a, **k):
+            if k.get("past_key_values") is not None:
+                clock._close()                         # (an eager token step ends the phase as a replay does)
+            elif clock.open is None:
+                clock.open = clock._event()
+            return forward(*a, **k)
+
+        def spy_packed(*a, **k):
+            if clock.open is None:
+                clock.open = clock._event()
+            return packed(*a, **k)
+
+        def spy_capture(*a, **k):
+            clock._close()
+            return capture(*a, **k)
+
+        def spy_replay(graph):
+            clock._close()
+            return clock.replay(graph)
+        model.forward, model.prefill_packed, model._capture_step = spy_forward, spy_packed, spy_capture
+        torch.cuda.CUDAGraph.replay = spy_replay
+        return self
+
+    def __exit__(self, *exc):
+        import torch
+        self._close()
+        del self.model.forward, self.model.prefill_packed, self.model._capture_step
+        torch.cuda.CUDAGraph.replay = self.replay
+        return False
+
+    def ms(self):
+        return sum(a.elapsed_time(b) for a, b in self.spans)
 
 
 def main():
@@ -77,9 +143,12 @@ def main():
     groups = [padded(prompts[g:g + SLOTS]) + (budgets[g:g + SLOTS],) for g in range(0, N, SLOTS)]
     common = dict(eos_token_id=[-1], pad_token_id=0, do_sample=False)
 
-    def many(n=N):
-        stats = model.generate_many(prompts[:n], max_new_tokens=budgets[:n], slots=SLOTS, return_stats=True, **common)[1]
-        return dict(stats, tokens=sum(budgets[:n]))
+    def many(n=N, cap=None):
+        with RefillClock(model) as clock:
+            stats = model.generate_many(prompts[:n], max_new_tokens=budgets[:n], slots=SLOTS, return_stats=True,
+                                        prefill_tokens=cap, **common)[1]
+        stats.setdefault("prefill_forwards", stats["prefills"])           # (without the knob every prefill is a forward)
+        return dict(stats, tokens=sum(budgets[:n]), refill=clock)
 
     def leftpad(n=N):
         steps = live = tokens = cut = 0
@@ -117,9 +186,12 @@ def main():
                     f.write(json.dumps(x) + "\n")
 
     # leg -> (function, ops.ATTN_SLOTS, ops.ATTN_LEFT_PAD, ops.ATTN_DECODE_GRAPH)
-    legs = {"many": (many, True, False, False), "leftpad": (leftpad, False, True, False),
-            "leftpad_graph": (leftpad, False, True, True), "alone": (alone, False, False, False),
-            "alone_graph": (alone, False, False, True)}
+    legs = {"many": (many, True, False, False)}
+    for cap in CAPS:
+        legs[f"many_prefill_{cap}"] = (lambda n=N, cap=cap: many(n, cap), True, False, False)
+    legs.update({"leftpad": (leftpad, False, True, False), "leftpad_graph": (leftpad, False, True, True),
+                 "alone": (alone, False, False, False), "alone_graph": (alone, False, False, True)})
+    declined = {}
     prev = ops.ATTN_SLOTS, ops.ATTN_LEFT_PAD, ops.ATTN_DECODE_GRAPH, A.model.DECODE_GRAPH
     base = {"what": "generate_many_mha", "config": "125M", "layers": cfg.num_hidden_layers, "hidden": cfg.hidden_size,
             "heads": cfg.num_attention_heads, "dtype": "bf16", "mode": "greedy"}
@@ -128,13 +200,24 @@ def main():
         for r in range(args.rounds + 1):              # round 0 is the warm-up, on the first group only
             for name, (fn, slots_on, pad_on, graph_on) in legs.items():
                 ops.ATTN_SLOTS, ops.ATTN_LEFT_PAD, ops.ATTN_DECODE_GRAPH = slots_on, pad_on, graph_on
-                if r == 0:
-                    timed(fn, SLOTS)
-                else:
-                    res.setdefault(name, []).append(timed(fn))
-                    t, st = res[name][-1]
+                if name in declined:
+                    continue
+                try:
+                    run = timed(fn, SLOTS) if r == 0 else timed(fn)
+                except (ValueError, IndexError, ops.ApertisHipError) as e:
+                    if not name.startswith("many_prefill_"):
+                        raise
+                    declined[name] = f"{type(e).__name__}: {e}"      # (a row length the layout or the kernels decline)
+                    res.pop(name, None)
+                    continue
+                if r:
+                    res.setdefault(name, []).append(run)
+                    t, st = run
                     print(f"[round {r}] {name}: {st['tokens'] / t:.1f} tokens/s", file=sys.stderr, flush=True)
         for name in legs:
+            if name in declined:
+                emit(dict(base, leg=name, prompts=N, slots=SLOTS, declined=declined[name]))
+                continue
             runs = res[name]
             best_t, stats = min(runs, key=lambda x: x[0])
             d = dict(base, leg=name, prompts=N, slots=1 if name.startswith("alone") else SLOTS, prompt_tokens=sum(lens),
@@ -148,6 +231,11 @@ def main():
             if "prefills" in stats:
                 d.update(prefills=stats["prefills"], graph_replays=stats["replays"], graphs=stats["graphs"],
                          fallbacks=len(stats["fallbacks"]))
+            if "refill" in stats:
+                d.update(prefill_tokens=CAP_OF.get(name), prefill_forwards=stats["prefill_forwards"],
+                         refill_phases=len(stats["refill"].spans), refill_ms=round(stats["refill"].ms(), 2),
+                         runs_seconds=[round(t, 4) for t, _ in runs],
+                         runs_refill_ms=[round(st["refill"].ms(), 2) for _, st in runs])
             emit(d)
 
         # ---- the replayed step, slots against the one-length kernels, and the launches of a slot step
