@@ -42,6 +42,7 @@ _FORWARDED = {
     "VIT_FUSED": attention,
     "SAMPLE_FUSED": sample, "SAMPLE_UNIFORMS": sample,
     "SWIGLU_FUSED": swiglu,
+    "LCE_PAD_VOCAB": loss,
 }
 for _m in _MODULES:
     for _k, _v in vars(_m).items():

@@ -71,8 +71,23 @@ _LCE_CHUNK_ROWS = int(_os.environ.get("APERTIS_LCE_CHUNK_ROWS", "16384"))
 # instead of a stock bf16 GEMM + add
 LCE_OWN_WGRAD = _os.environ.get("APERTIS_LCE_OWN_WGRAD", "1") == "1"
 LCE_FUSED_CE = _os.environ.get("APERTIS_LCE_FUSED_CE", "1") == "1"     # apertis_cross_entropy_fwd_bwd on the chunk (tests switch it off)
+# a vocabulary that is no multiple of the CE kernels' 16-byte chunk (GPT-2's 50 257) on the fused path too: the chunk's logits
+# are formed Vp = ceil(V / VN) * VN wide and the columns [V, Vp) hold -inf (opt-in; _LinearCrossEntropy)
+LCE_PAD_VOCAB = _os.environ.get("APERTIS_LCE_PAD_VOCAB", "0") == "1"
 # (the chunk's logits on the library's NT kernel instead: 761 against 760 us alone, the step within noise - stays on hipBLASLt;
 # d hidden = dl @ W, K = 32000: 1 019 against 802 us - stays too.  tools/prof_lm_head.py)
+
+
+def _lce_padded_vocab(V, compute_dtype):
+    """Vp: V rounded up to whole 16-byte chunks of the compute dtype (VN = 8 bf16 / 4 fp32 logits), the width the cross
+    entropy entry points take."""
+    vn = 8 if compute_dtype == torch.bfloat16 else 4
+    return -(-V // vn) * vn
+
+
+def _lce_vocab_ok(V, compute_dtype):
+    """The vocabulary term of linear_cross_entropy_supported: whole chunks, or any V >= 1 under LCE_PAD_VOCAB."""
+    return V >= 1 and (LCE_PAD_VOCAB or V == _lce_padded_vocab(V, compute_dtype))
 
 
 class _LinearCrossEntropy(torch.autograd.Function):
@@ -80,7 +95,20 @@ class _LinearCrossEntropy(torch.autograd.Function):
     a few sequences at a time - logits of the chunk (hipBLASLt GEMM), apertis_cross_entropy_fwd (log-sum-exp + loss),
     apertis_cross_entropy_bwd IN PLACE on the chunk (softmax - onehot, already scaled by 1 / #targets), and the chunk's
     two gradient GEMMs (d hidden, and d W accumulated in fp32) - so only one chunk of logits ever exists and nothing is
-    recomputed in the backward, which just scales the stored gradients by the incoming scalar."""
+    recomputed in the backward, which just scales the stored gradients by the incoming scalar.
+
+    The padded-vocabulary form (LCE_PAD_VOCAB, and V no multiple of VN; an aligned V runs the lines above unchanged): the
+    compute-dtype weight is built [Vp, H] with exact zero rows [V, Vp), the chunk's logits come out [n L, Vp] and their
+    columns [V, Vp) are set to -inf before any CE kernel, which is then called with V = Vp.  The pads are exact: a -inf
+    logit adds exactly 0 to a row's sum (ce_chunk_base) and leaves the backward as exp2(-inf) * g = 0, a row without a
+    target is written as zeros, so after the in-place backward the pad columns of dl are exact zeros - d hidden = dl @ w_p
+    meets them with zero rows, and the rows [V, Vp) of the [Vp, H] weight gradient are exact zeros that are dropped.  No
+    target lands on a pad: labels in [V, Vp) are out of range for the caller's V and are skipped like every other
+    out-of-range label (they are turned into ignore_index before the kernels, which test against Vp; the host count tests
+    against V).  The backward overwrites the pads, so the fill runs for every chunk.  Cost: the fill (at most 7 columns of a
+    strided view per chunk), and the padded weight - in bf16 from an fp32 master it IS today's cast, written into a
+    [Vp, H] buffer; where the weight already has the compute dtype (fp32 training, a bf16 model) it is one V x H copy that
+    today's alias does not make."""
 
     @staticmethod
     def forward(ctx, hidden, weight, labels, ignore_index, compute_dtype):
@@ -92,9 +120,18 @@ class _LinearCrossEntropy(torch.autograd.Function):
         n_pos = min(L, labels.shape[1]) - 1
         need = _grad_wanted(ctx, 2)
         x = hidden.to(compute_dtype).contiguous()
-        w = weight.detach().to(compute_dtype)
+        Vc = V                                                                # the caller's vocabulary: count, and d W's rows
+        Vp = _lce_padded_vocab(V, compute_dtype) if LCE_PAD_VOCAB else V
+        if V < Vp:
+            w = torch.empty(Vp, H, device=hidden.device, dtype=compute_dtype)
+            w[:V].copy_(weight.detach())                                      # (the cast, as .to(compute_dtype) below)
+            w[V:].zero_()
+            labels = torch.where((labels >= V) & (labels < Vp), ignore_index, labels)
+            V = Vp                                                            # every launch below sees the padded width
+        else:
+            w = weight.detach().to(compute_dtype)
         tgt = labels[:, 1:n_pos + 1]
-        count = ((tgt != ignore_index) & (tgt >= 0) & (tgt < V)).sum().to(torch.float32)
+        count = ((tgt != ignore_index) & (tgt >= 0) & (tgt < Vc)).sum().to(torch.float32)
         gscale = (1.0 / count).reshape(1).contiguous()
         dev = hidden.device
         code = dtype_code(x)
@@ -113,6 +150,8 @@ class _LinearCrossEntropy(torch.autograd.Function):
             n = min(nb, B - b0)
             xb = x[b0:b0 + n].reshape(n * L, H)
             logits = torch.matmul(xb, w.t()).reshape(n, L, V)                 # n sequences of logits
+            if Vc < V:
+                logits[..., Vc:].fill_(float("-inf"))
             lab = labels[b0:b0 + n]
             # (with gradients wanted: log-sum-exp, loss and softmax - onehot of a row in ONE pass over it - the row waits in its
             #  work-group's registers - when the vocabulary fits; else, and without gradients, the two kernels)
@@ -146,7 +185,7 @@ class _LinearCrossEntropy(torch.autograd.Function):
                     dw.add_(torch.matmul(dl.t(), xb))
                 else:
                     dw.copy_(torch.matmul(dl.t(), xb))
-        ctx.save_for_backward(dx, dw)
+        ctx.save_for_backward(dx, dw[:Vc] if need and Vc < V else dw)
         ctx.cfg = (hidden.dtype, weight.dtype)
         return loss_sum / count
 
@@ -164,11 +203,12 @@ def linear_cross_entropy_supported(hidden, weight, labels):
     cd = torch.bfloat16 if torch.is_autocast_enabled() else hidden.dtype
     return (hidden.is_cuda and weight.is_cuda and labels.is_cuda and hidden.dim() == 3 and labels.dim() == 2 and
             labels.dtype == torch.int64 and hidden.shape[0] == labels.shape[0] and cd in (torch.float32, torch.bfloat16) and
-            V % (8 if cd == torch.bfloat16 else 4) == 0 and hidden.shape[1] >= 2)
+            _lce_vocab_ok(V, cd) and hidden.shape[1] >= 2)
 
 
 def linear_cross_entropy(hidden, weight, labels, ignore_index=-100, compute_dtype=None):
     """mean over valid (b, l) of CE((hidden @ weight.T)[b, l], labels[b, l + 1]): the LM head (reference core.py:1412) and
     the shifted cross entropy (core.py:1417-1450) as one op that never holds more than one sequence of logits.
-    hidden [B, L, H], weight [V, H] (the tied embedding), labels [B, >= L] int64."""
+    hidden [B, L, H], weight [V, H] (the tied embedding), labels [B, >= L] int64.  V must be whole 16-byte chunks of the
+    compute dtype (a multiple of 8 in bf16, of 4 in fp32) unless LCE_PAD_VOCAB is on."""
     return _apply(_LinearCrossEntropy, hidden, weight, labels, ignore_index, compute_dtype or hidden.dtype)
